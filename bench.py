@@ -13,12 +13,20 @@ by the one real exchange of the path: a sum all-reduce (RCCL) of the integer
 statistics vector.  Lines shard contiguously over ranks (weak scaling: the
 per-GPU shard is fixed, config.workload names it); there is no other collective.
 
-Prints ONE JSON line on rank 0.  Beside the headline fields (BASELINE configs[1]:
-random-uint32 64 B blocks) the line carries, outside the timed region,
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up (the streaming-read probe, whose
+rate goes into roofline.read_probe_gbps, then the warm-up steps), times the steps and prints the
+headline fields (BASELINE configs[1]: random-uint32 64 B blocks).  With --full it also runs,
+outside the timed region, the known-answer and byte-sum checks of the timed trace and measures
+board power, the CPU baseline and
   "workloads": N = 1 -- the other BASELINE workloads (fp32 sine, mixed int/fp, zeros,
                128 B pointer qwords) through VPC and BDI: kernel, kernel_ms_avg, roofline, ratio;
+  "layouts":   N = 1 -- VPC configurations of other layouts on the random trace;
   "config4":   N > 1 -- BASELINE configs[3] (mixed int/fp, 512 Mi blocks per GPU, sharded
                contiguously, one all-reduce per pass): rccl_ranks, pass time, all-reduce share.
+
+--dump-outputs DIR writes the statistics the timed path computed in its last step (the
+evaluator's integer statistics vector, all-reduced over the ranks for N > 1) as DIR/stats.npy
+(float64); the synthetic trace is seeded, so equal arguments give equal inputs.
 """
 import argparse
 import ctypes
@@ -307,9 +315,10 @@ def main():
     ap.add_argument("--workload", default="random_u32", choices=sorted(WORKLOADS))
     ap.add_argument("--lines", type=int, default=256 << 20, help="blocks per GPU (default 256 Mi = 16 GiB at 64 B)")
     ap.add_argument("--algo", default="VPC", choices=["VPC", "BDI", "FPC", "BPC"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="skip the sub-records of the other BASELINE workloads (sine, mixed, zeros, 128 B pointers; VPC and BDI)")
+                    help="with --full: skip the sub-records of the other BASELINE workloads (sine, mixed, zeros, 128 B pointers; "
+                         "VPC and BDI), the layouts and board power")
     ap.add_argument("--config4-lines", type=int, default=None,
                     help="N > 1: blocks per GPU of the BASELINE config 4 sub-record (mixed int/fp, 4 Gi blocks over 8 GPUs; "
                          "default 512 Mi, or --lines in a single-GPU rehearsal)")
@@ -318,6 +327,11 @@ def main():
                          "(a 1-GPU box cannot host an RCCL group); never used for reported numbers")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc pass (profiles/), copied into roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the known-answer and byte-sum checks, "
+                         "board power, the CPU baseline, the other workloads and layouts (N = 1), config 4 (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the statistics vector of the last timed step to DIR/stats.npy (float64)")
     args = ap.parse_args()
 
     import torch
@@ -414,10 +428,19 @@ def main():
         last = ev.stats_from_raw(scratch.cpu().numpy().view(np.uint64))
         assert int(last[0]) == world * n * args.steps, (int(last[0]), world * n * args.steps)
     ratio = float(v[1]) / float(v[2])
-    if rank == 0 and args.lines % 4096 == 0:
+    if args.dump_outputs and rank == 0:
+        # every step evaluates the same lines, so the accumulators hold `steps` equal contributions: the last step's is a
+        # whole fraction of them
+        acc = last if world > 1 else v
+        assert (acc % np.uint64(args.steps) == 0).all(), "every pass counts the same"
+        out_step = acc // np.uint64(args.steps)
+        assert (out_step < (1 << 53)).all(), "a statistic beyond float64's exact integers"
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "stats.npy"), out_step.astype(np.float64))
+    if args.full and rank == 0 and args.lines % 4096 == 0:
         check_known_ratio(args.algo, args.workload, L, n, ratio)
 
-    if args.algo == "VPC" and rank == 0:
+    if args.full and args.algo == "VPC" and rank == 0:
         # a full-size property no smaller run can stand in for: the byte sum behind cluster -1's MAE (VPC.cpp:417-443 with r = line[i])
         # against a sum of the resident buffer computed by torch -- they differ by at most 255 per byte of the lines that went to
         # another cluster
@@ -426,13 +449,13 @@ def main():
         assert int(v[3]) % args.steps == 0 and int(v[3 + 4]) % args.steps == 0, "every pass counts the same"
         assert abs(total - sum_r_unc) <= (n - count_unc) * L * 255, (total, sum_r_unc, n - count_unc)
     kernel_name = kernel_label(mpc, ev, args.algo, L)
-    power = PowerProbe(torch, local_rank) if (world == 1 and not args.no_workloads) else None      # (not under tools/profile_round.sh)
+    power = PowerProbe(torch, local_rank) if (args.full and world == 1 and not args.no_workloads) else None
     headline_power = power.run(torch, lambda: ev.compress_device(buf.data_ptr(), n, stream=sp), stream, 1.5) if power else None
 
     # ---- sub-records (not part of the timed region above) ----
     # N = 1: every other BASELINE workload through the same entry point, VPC and BDI, 16 GiB each.
     workloads = None
-    if world == 1 and not args.no_workloads:
+    if args.full and world == 1 and not args.no_workloads:
         workloads = []
         for wl, algo in SUB_WORKLOADS:
             if (wl, algo) == (args.workload, args.algo):
@@ -440,7 +463,7 @@ def main():
             workloads.append(time_workload(torch, mpc, configs, buf, stream, local_rank, wl, algo, n * L, power=power))
     # ... and the random-u32 trace through configurations of other layouts (general-layout twins, run-time compiled sequence)
     layouts = None
-    if world == 1 and not args.no_workloads and args.workload == "random_u32" and L == 64:
+    if args.full and world == 1 and not args.no_workloads and args.workload == "random_u32" and L == 64:
         os.environ.setdefault("MPC_JIT_CACHE", "")      # (a measurement run leaves no code-object cache behind; ~3 s of compilation)
         mpc.synth_fill(buf.data_ptr(), n, L, kind, first_line=0)
         torch.cuda.synchronize()
@@ -458,7 +481,7 @@ def main():
     # all-reduce of the statistics per pass -- as its own sub-record next to the primary value (which
     # stays on the N = 1 workload so that the scaling curve is comparable).
     config4 = None
-    if world > 1:
+    if args.full and world > 1:
         n4 = args.config4_lines if args.config4_lines else (min(512 << 20, args.lines) if args.rehearse_single_gpu else 512 << 20)
         del buf
         torch.cuda.empty_cache()
@@ -532,7 +555,7 @@ def main():
         }
         if headline_power is not None:
             out["power"] = headline_power
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(configs, traces, args.workload, L, algo=args.algo)
         else:
             out["cpu_baseline"] = None

@@ -1007,7 +1007,7 @@ def test_bench_two_rank_rehearsal_child_process(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), "--log-dir", str(tmp_path / "elastic"),      # (else /tmp/torchelastic_*)
            os.path.join(root, "bench.py"),
-           "--gpus", "2", "--rehearse-single-gpu", "--lines", "1048576", "--steps", "2", "--warmup", "1",
+           "--gpus", "2", "--rehearse-single-gpu", "--full", "--lines", "1048576", "--steps", "2", "--warmup", "1",
            # a config-4 shard LARGER than the primary buffer: the primary buffer is released and the shard allocated anew
            "--config4-lines", "3145728"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -1029,6 +1029,32 @@ def test_bench_two_rank_rehearsal_child_process(tmp_path):
     # random u32 blocks stay uncompressed at 515 bits, mixed blocks compress
     assert abs(d["config"]["compression_ratio"] - 512.0 / 515.0) < 1e-6
     assert c4["compression_ratio"] > 1.0
+
+
+def test_bench_plain_run_dumps_last_step_statistics(oracle, configs, traces, tmp_path):
+    """A plain bench.py run (no --full) in a fresh child process: --steps sets the number of timed steps, the line
+    carries the headline fields and none of the --full extras, and --dump-outputs writes the statistics of the last
+    timed step -- the oracle's statistics of the same seeded lines."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 1 << 16
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--lines", str(n), "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    line = [l for l in p.stdout.split("\n") if l.startswith("{")]
+    assert len(line) == 1, p.stdout[-2000:]
+    d = json.loads(line[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "blocks/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert d["cpu_baseline"] is None and not {"workloads", "layouts", "power", "config4"} & set(d)
+    got = np.load(tmp_path / "out" / "stats.npy")
+    assert got.dtype == np.float64
+    o = oracle.VpcOracle(configs.probe_config(64))
+    o.compress(traces.random_u32(n, 64))
+    assert (got == o.stats_vector().astype(np.float64)).all()
 
 
 ROUTE_NAMES = ["vpc_deferred", "vpc_drains", "vpc_paired_blocks", "vpc_plain_blocks", "vpc_to_paired", "vpc_to_plain",

@@ -1,7 +1,8 @@
 """CPU oracle pinned against (a) the known answers SURVEY.md 8c / BASELINE.md 2
 captured from the reference's object code, (b) vectors produced by the
 reference's own stage classes (tests/golden/ref_stage_vectors.json), and
-(c) that same reference build live, where /root/reference is mounted."""
+(c) the outputs of that same reference build for further seeded inputs
+(tests/golden/ref_live_vectors.npz), checked live as well where oracle/_ref is built."""
 import ctypes as C
 import json
 import os
@@ -129,89 +130,59 @@ def test_oracle_matches_golden_stage_vectors(oracle, golden_dir):
 
 
 # ------------------------------------------------------ live reference stage build
+def _live_vectors():
+    """The seeded case generators of tests/golden/make_ref_live_vectors.py and the reference outputs it stored."""
+    import importlib.util
+    here = os.path.dirname(os.path.abspath(__file__))
+    spec = importlib.util.spec_from_file_location("make_ref_live_vectors",
+                                                  os.path.join(here, "golden", "make_ref_live_vectors.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen, np.load(gen.FIXTURE)
+
+
 def test_oracle_matches_live_reference_stages(oracle, configs):
+    """The probe configuration's prediction modules on random, sparse, ramp and sine lines: scanned arrays and
+    common-encoder sizes of the reference's compiled classes (stored in tests/golden/ref_live_vectors.npz; where
+    oracle/_ref is built, the live build is checked against the stored outputs as well)."""
+    gen, fx = _live_vectors()
+    cases = gen.stage_cases(oracle, configs)
+    assert gen.digest(cases) == str(fx["stage_inputs_sha256"]), "regenerated inputs differ from the fixture's"
+    ref_scs = gen.split(fx["stage_scanned"], cases, lambda L: 8 * L // 16)
     R = oracle.ref_lib()
-    if R is None:
-        pytest.skip("oracle/_ref not built (reference tree not mounted)")
     lib = oracle.lib()
-    rng = np.random.default_rng(99)
-    for L in (32, 64, 128):
-        oc = oracle.config_from_json(configs.probe_config(L))
-        for mi in range(2, 6):
-            m = oc.modules[mi]
-            base = np.array(list(m.base)[:L], dtype=np.int32)
-            weight = np.array(list(m.weight)[:L], dtype=np.float32)
-            if m.pred_kind != 0:
-                weight[:] = 1.0
-            diff = np.array(list(m.diff)[:L], dtype=np.int32)
-            rows = np.array(list(m.rows)[: m.table_size], dtype=np.int32)
-            cols = np.array(list(m.cols)[: m.table_size], dtype=np.int32)
-            for trial in range(300):
-                kind = trial % 4
-                if kind == 0:
-                    line = rng.integers(0, 256, L, dtype=np.uint8)
-                elif kind == 1:
-                    line = np.zeros(L, np.uint8)
-                    line[rng.integers(0, L, 3)] = rng.integers(0, 256, 3)
-                elif kind == 2:
-                    w = (rng.integers(0, 1000) + np.arange(L // 4) * rng.integers(0, 5)).astype("<u4")
-                    line = w.view(np.uint8).copy()
-                else:
-                    t = rng.integers(0, 1 << 20) + np.arange(L // 4)
-                    line = np.sin(2 * np.pi * t / 1024).astype("<f4").view(np.uint8).copy()
-                ref_sc = np.zeros(8 * L // 16, np.uint16)
-                my_sc = np.zeros(8 * L // 16, np.uint16)
-                R.ref_scanned(m.pred_kind, m.root, L, base.ctypes.data, weight.ctypes.data,
-                              diff.ctypes.data, m.consecutive_xor, m.table_size, rows.ctypes.data,
-                              cols.ctypes.data, line.ctypes.data, ref_sc.ctypes.data)
-                lib.mpc_o_scanned(C.byref(m), L, line.ctypes.data, my_sc.ctypes.data)
-                assert (ref_sc == my_sc).all()
-                assert R.ref_fpc_size(ref_sc.ctypes.data, len(ref_sc)) == \
-                    lib.mpc_o_fpc_size(my_sc.ctypes.data, len(my_sc))
+    for i, (c, ref_sc, ref_fpc) in enumerate(zip(cases, ref_scs, fx["stage_fpc"])):
+        if R is not None:
+            assert (gen.ref_scanned(R, c) == ref_sc).all(), i
+            assert R.ref_fpc_size(ref_sc.ctypes.data, len(ref_sc)) == ref_fpc, i
+        my_sc = np.zeros(8 * c.L // 16, np.uint16)
+        lib.mpc_o_scanned(C.byref(c.m), c.L, c.line.ctypes.data, my_sc.ctypes.data)
+        assert (ref_sc == my_sc).all(), i
+        assert ref_fpc == lib.mpc_o_fpc_size(my_sc.ctypes.data, len(my_sc)), i
 
 
 def test_oracle_matches_live_reference_odd_weights(oracle):
     """WeightBase tables with weights that are not powers of two and with extreme weights:
-    (int)log2f(w) truncates toward zero (PredictorModule.cpp:30).  Live against the reference's
-    compiled classes; the same kind of tables are also in the committed golden vectors."""
+    (int)log2f(w) truncates toward zero (PredictorModule.cpp:30).  Against the outputs of the reference's
+    compiled classes (stored in tests/golden/ref_live_vectors.npz; live as well where oracle/_ref is built);
+    the same kind of tables are also in the committed stage vectors."""
+    gen, fx = _live_vectors()
+    cases = gen.odd_weight_cases(oracle)
+    assert gen.digest(cases) == str(fx["odd_inputs_sha256"]), "regenerated inputs differ from the fixture's"
+    ref_ps = gen.split(fx["odd_pred"], cases, lambda L: L)
+    ref_scs = gen.split(fx["odd_scanned"], cases, lambda L: 8 * L // 16)
     R = oracle.ref_lib()
-    if R is None:
-        pytest.skip("oracle/_ref not built (reference tree not mounted)")
     lib = oracle.lib()
-    rng = np.random.default_rng(4321)
-    weights = [0.3, 0.7, 3.0, 5.5, 300.0, 0.001, 1.0, 0.5, 1.5, 0.99, 1.99, 2.0, 4.01, 0.26, 0.24, 127.9,
-               128.0, 0.0079, 0.0078125, 255.0, 0.126, 1e-6, 1e6]
-    for L in (32, 64, 128):
-        for trial in range(40):
-            m = oracle.OModule()
-            m.kind, m.pred_kind = oracle.KIND_PREDCOMP, 0
-            m.root = int(rng.integers(0, L)) if trial % 2 else 0
-            m.consecutive_xor = trial % 3 != 0
-            for j in range(L):
-                m.base[j] = int(rng.integers(0, L)) if trial % 4 else max(j - 4, 0)
-                m.weight[j] = weights[int(rng.integers(0, len(weights)))]
-            m.table_size = 8 * L
-            for j in range(8 * L):
-                m.rows[j], m.cols[j] = j // L, j % L
-            base = np.array(list(m.base)[:L], dtype=np.int32)
-            weight = np.array(list(m.weight)[:L], dtype=np.float32)
-            diff = np.zeros(L, dtype=np.int32)
-            rows = np.array(list(m.rows)[: 8 * L], dtype=np.int32)
-            cols = np.array(list(m.cols)[: 8 * L], dtype=np.int32)
-            for k in range(25):
-                line = rng.integers(0, 256, L, dtype=np.uint8) if k % 2 else \
-                    (rng.integers(0, 256) + np.arange(L) * rng.integers(0, 3)).astype(np.uint8)
-                ref_p, my_p = np.zeros(L, np.uint8), np.zeros(L, np.uint8)
-                R.ref_predict(0, m.root, L, base.ctypes.data, weight.ctypes.data, diff.ctypes.data,
-                              line.ctypes.data, ref_p.ctypes.data)
-                lib.mpc_o_predict(C.byref(m), L, line.ctypes.data, my_p.ctypes.data)
-                assert (ref_p == my_p).all()
-                ref_sc, my_sc = np.zeros(8 * L // 16, np.uint16), np.zeros(8 * L // 16, np.uint16)
-                R.ref_scanned(0, m.root, L, base.ctypes.data, weight.ctypes.data, diff.ctypes.data,
-                              m.consecutive_xor, 8 * L, rows.ctypes.data, cols.ctypes.data, line.ctypes.data,
-                              ref_sc.ctypes.data)
-                lib.mpc_o_scanned(C.byref(m), L, line.ctypes.data, my_sc.ctypes.data)
-                assert (ref_sc == my_sc).all()
+    for i, (c, ref_p, ref_sc) in enumerate(zip(cases, ref_ps, ref_scs)):
+        if R is not None:
+            assert (gen.ref_predict(R, c) == ref_p).all(), i
+            assert (gen.ref_scanned(R, c) == ref_sc).all(), i
+        my_p = np.zeros(c.L, np.uint8)
+        lib.mpc_o_predict(C.byref(c.m), c.L, c.line.ctypes.data, my_p.ctypes.data)
+        assert (ref_p == my_p).all(), i
+        my_sc = np.zeros(8 * c.L // 16, np.uint16)
+        lib.mpc_o_scanned(C.byref(c.m), c.L, c.line.ctypes.data, my_sc.ctypes.data)
+        assert (ref_sc == my_sc).all(), i
 
 
 # ------------------------------------------------- reference-derived whole-line vectors

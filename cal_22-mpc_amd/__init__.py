@@ -23,7 +23,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPC_HIP_LIB") or os.path.join(HERE, "libmpc_hip.so")   # override: development builds only
 
-MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC = 1, 2, 3, 4, 5
+MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2 = 1, 2, 3, 4, 5, 6
 SYNTH_KINDS = {"zeros": 0, "random_u32": 1, "sine_f32": 2, "mixed": 3, "pointers_u64": 4}
 
 
@@ -76,6 +76,10 @@ def lib() -> C.CDLL:
             "mpc_create_bdi": ([C.c_uint, C.c_int, C.POINTER(H)], C.c_int),
             "mpc_create_fpc": ([C.c_uint, C.c_int, C.POINTER(H)], C.c_int),
             "mpc_create_bpc": ([C.c_uint, C.c_int, C.POINTER(H)], C.c_int),
+            "mpc_create_sc2": ([C.c_uint, C.c_uint64, C.c_int, C.POINTER(H)], C.c_int),
+            "mpc_sc2_sampling_lines": ([C.c_uint64], C.c_uint64),
+            "mpc_sc2_code_lengths": ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
+            "mpc_sc2_table": ([H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
             "mpc_destroy": ([H], None),
             "mpc_get_info": ([H, C.POINTER(Info)], C.c_int),
             "mpc_last_error": ([H], C.c_char_p),
@@ -117,6 +121,9 @@ EXPORTED_SYMBOLS = [
     "mpc_compress_npy", "mpc_npy_shape", "mpc_compress_gpgpusim_log", "mpc_gpgpusim_log_line_size",
     "mpc_synth_fill", "mpc_read_bandwidth_probe",
 ]
+# The SC2 entry points of include/mpc_hip.h.  Kept apart from EXPORTED_SYMBOLS, which lists the names of the
+# header's lowercase-letter form (mpc_[a-z_]+) only; every one of both lists is exported by libmpc_hip.so.
+EXPORTED_SC2_SYMBOLS = ["mpc_create_sc2", "mpc_sc2_sampling_lines", "mpc_sc2_code_lengths", "mpc_sc2_table"]
 
 
 def gpgpusim_log_line_size(path: str) -> int:
@@ -329,6 +336,60 @@ class BPC(_Evaluator):
         return {"lines": int(v[0]), "original_bits": int(v[1]), "compressed_bits": int(v[2]),
                 "comp_ratio": (float(v[1]) / float(v[2])) if v[2] else 0.0,
                 "total_words": int(v[3]), "counts": [int(x) for x in v[4:11]]}
+
+
+class SC2(_Evaluator):
+    """``comp::SC2(lineSize, warmupCnt)`` (reference ``SC2.h:100-107``): lines 0 .. sampling_lines-1 of the trace, counted
+    across every call on this object, are the warm-up sample; the code table is built when the next line arrives.
+    Per-line ``selected``: 0 for a warm-up line, 1 for a line sized against the table."""
+
+    def __init__(self, line_size: int, sampling_lines: int, device: int = -1):
+        super().__init__()
+        rc = lib().mpc_create_sc2(line_size, sampling_lines, device, C.byref(self._h))
+        if rc != 0:
+            raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
+        self._finish()
+        self.sampling_lines = int(sampling_lines)
+        self.kernel_path = self.info.kernel_path
+
+    @property
+    def kernel_form(self) -> str:
+        """"warm-up counting" before line S, "table sizing" after."""
+        return (lib().mpc_kernel_form(self._h) or b"").decode()
+
+    def result(self) -> Dict:
+        """``CompResult`` (OriginalSize, CompressedSize, CompRatio; name "SC2-Huffman") plus the SC2 counters."""
+        v = self.stats_vector()
+        return {"name": "SC2-Huffman", "lines": int(v[0]), "original_bits": int(v[1]), "compressed_bits": int(v[2]),
+                "comp_ratio": (float(v[1]) / float(v[2])) if v[2] else 0.0, "warmup_lines": int(v[3]),
+                "table_symbols": int(v[4]), "words_in_table": int(v[5])}
+
+    def table(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(symbols uint32, code lengths uint16) in ascending symbol order; empty before line S."""
+        sym = np.zeros(1024, dtype=np.uint32)
+        lens = np.zeros(1024, dtype=np.uint16)
+        n = C.c_size_t()
+        self._check(lib().mpc_sc2_table(self._h, sym.ctypes.data, lens.ctypes.data, 1024, C.byref(n)))
+        return sym[:n.value].copy(), lens[:n.value].copy()
+
+
+def sc2_sampling_lines(num_lines: int) -> int:
+    """The reference driver's SC2 warm-up length for a trace of ``num_lines`` lines (``main.cpp:110-113``)."""
+    return int(lib().mpc_sc2_sampling_lines(num_lines))
+
+
+def sc2_code_lengths(symbols, freqs) -> np.ndarray:
+    """The library's SC2 table builder (no device): code lengths of distinct ``symbols`` with warm-up ``freqs``, in
+    input order; 0xFFFF for symbols outside the 1024 kept ones."""
+    sym = np.ascontiguousarray(symbols, dtype=np.uint32)
+    fr = np.ascontiguousarray(freqs, dtype=np.uint64)
+    if sym.shape != fr.shape or sym.ndim != 1:
+        raise ValueError("symbols and freqs must be 1-D arrays of one length")
+    out = np.zeros(len(sym), dtype=np.uint16)
+    rc = lib().mpc_sc2_code_lengths(sym.ctypes.data, fr.ctypes.data, len(sym), out.ctypes.data)
+    if rc != 0:
+        raise MpcError(rc, "mpc_sc2_code_lengths: empty input or repeated symbol")
+    return out
 
 
 def vpc_result_from_vector(v: np.ndarray, M: int, bins: int, L: int) -> Dict:

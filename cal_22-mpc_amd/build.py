@@ -52,7 +52,8 @@ def build_lib(force: bool = False, verbose: bool = False, test: bool = False) ->
     os.makedirs(objdir, exist_ok=True)
     lane = os.path.join(CSRC, "mpc_vpc_lane.hip")
     units = [(lane, f"lane_w{w}.o", [f"-DMPC_LANE_W={w}"]) for w in (16, 32, 8, 0)]
-    units += [(os.path.join(CSRC, "mpc_kernels.hip"), "kernels.o", []), (os.path.join(CSRC, "mpc_capi.hip"), "capi.o", [])]
+    units += [(os.path.join(CSRC, "mpc_kernels.hip"), "kernels.o", []), (os.path.join(CSRC, "mpc_sc2.hip"), "sc2.o", []),
+              (os.path.join(CSRC, "mpc_capi.hip"), "capi.o", [])]
     tflag = ["-DMPC_TESTING=1"] if test else []
     procs = []
     for src, obj, extra in units:

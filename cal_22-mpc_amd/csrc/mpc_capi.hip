@@ -22,6 +22,7 @@
 
 #include "mpc_config.h"
 #include "mpc_device.h"
+#include "mpc_sc2.h"
 
 // libmpc_hip_test.so (build.py, -DMPC_TESTING=1): route counters behind the raw statistics and a cap on the launch grid,
 // see mpc_kernel_common.h.  Must agree with the kernels' translation units.
@@ -47,6 +48,10 @@ hipError_t mpc_launch_vpc_lane_jit(hipFunction_t, hipFunction_t, const void *, u
 size_t mpc_vpc_lane_smem(const MpcVpcParams *);
 int mpc_vpc_lane_unrolled(const MpcVpcParams *);
 size_t mpc_vpc_generic_smem(const MpcVpcParams *);
+hipError_t mpc_launch_sc2_count(const void *, u64, int, u64 *, u64, uint16_t *, int8_t *, u64 *, hipStream_t);
+hipError_t mpc_launch_sc2_hist(const u64 *, u64, u64, int, uint32_t *, int, hipStream_t);
+hipError_t mpc_launch_sc2_collect(const u64 *, u64, u64, u64 *, uint32_t *, int, hipStream_t);
+hipError_t mpc_launch_sc2_size(const void *, u64, int, const MpcSc2Table *, uint16_t *, int8_t *, u64 *, int, hipStream_t);
 }
 
 namespace {
@@ -73,7 +78,7 @@ struct Slot {
 }  // namespace
 
 struct mpc_handle {
-  int algorithm = 0;   // 0 VPC, 1 BDI, 2 FPC, 3 BPC
+  int algorithm = 0;   // 0 VPC, 1 BDI, 2 FPC, 3 BPC, 4 SC2
   int device = 0;
   int L = 0;
   int num_cus = 256;
@@ -94,6 +99,19 @@ struct mpc_handle {
   // no staging copies, no 64 MiB slots; a call is one launch and one stream synchronisation
   uint8_t *mini = nullptr;       // [kMiniLines * L] lines | [kMiniLines] uint16 sizes | [kMiniLines] int8 clusters
   mpcjit::Kernels jit;           // VPC: the unrolled kernels of a sequence without a built-in instantiation (mpc_jit.h)
+  // SC2: lines 0 .. S-1 of the trace (counted across calls) are warm-up lines, the table is built when line S arrives
+  struct {
+    u64 S = 0;                   // warm-up lines (the reference's m_maxSamplingCnt)
+    u64 seen = 0;                // lines evaluated since creation (m_samplingCnt, not capped); not reset by mpc_stats_reset
+    u64 lines = 0, warm = 0;     // statistics [0] and [3] since creation or the last reset (counted on the host)
+    u64 *d_hash = nullptr;       // warm-up frequency table (mpc_sc2.hip), freed once the code table is built
+    u64 hash_mask = 0;
+    uint4 *d_buckets = nullptr;  // the code table's bucket image
+    MpcSc2Table tab{};
+    bool built = false;
+    std::vector<uint32_t> symbols;   // the table, ascending symbol order
+    std::vector<uint16_t> lengths;
+  } sc2;
   std::string error;
 };
 
@@ -300,9 +318,12 @@ int grid_for(const mpc_handle *h, u64 work_items, int block, int per_cu)
   return (int)(need < cap ? need : cap);
 }
 
+int launch_sc2(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
+
 int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s)
 {
   if (n == 0) return MPC_OK;
+  if (h->algorithm == 4) return launch_sc2(h, d_lines, n, d_sizes, d_sel, s);
   hipError_t e;
   if (h->algorithm == 3) {
     e = mpc_launch_bpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
@@ -319,6 +340,107 @@ int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t 
     e = mpc_launch_vpc_generic(d_lines, n, &h->plan.params, d_sizes, d_sel, h->d_raw, grid_for(h, n, 128, 8), s);
   }
   if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return MPC_OK;
+}
+
+// SC2: the code table from the warm-up counts.  The one blocking point of an SC2 handle: every stream that may still
+// run a warm-up count (the call's, the handle's, both staging slots') is synchronised, the 1024 largest slots are
+// selected on the device (radix select, 8 bits per pass from the top), only those <= 1024 (symbol, count) pairs come
+// to the host, the heap is replayed there (mpc_sc2.h) and the bucket image goes back to the device.
+int sc2_build(mpc_handle *h, hipStream_t s)
+{
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int i = 0; i < 2; i++)
+    if (h->slots[i].stream) HIPCHK(h, hipStreamSynchronize(h->slots[i].stream));
+  const u64 n_slots = h->sc2.hash_mask + 1;
+  const int grid = (int)std::min<u64>((n_slots + 255) / 256, (u64)h->num_cus * 8);
+  uint32_t *d_work = nullptr;           // [256] histogram | [1] count | pad | [1024] uint64 slots
+  HIPCHK(h, hipMalloc((void **)&d_work, 272 * sizeof(uint32_t) + MPC_SC2_ENTRIES * sizeof(u64)));
+  u64 *d_out = reinterpret_cast<u64 *>(d_work + 272);
+  auto fail = [&](const char *what, hipError_t e) {
+    (void)hipFree(d_work);
+    return set_err(h, MPC_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  };
+  hipError_t e;
+  uint32_t hist[256];
+  u64 need = MPC_SC2_ENTRIES, prefix = 0, threshold = 1;
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    if ((e = hipMemsetAsync(d_work, 0, 256 * sizeof(uint32_t), h->stream)) != hipSuccess) return fail("hipMemsetAsync", e);
+    if ((e = mpc_launch_sc2_hist(h->sc2.d_hash, n_slots, prefix, shift, d_work, grid, h->stream)) != hipSuccess) return fail("sc2 select", e);
+    if ((e = hipMemcpyAsync(hist, d_work, sizeof(hist), hipMemcpyDeviceToHost, h->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(h->stream)) != hipSuccess)
+      return fail("sc2 select", e);
+    if (shift == 56) {
+      u64 total = 0;
+      for (int d = 0; d < 256; d++) total += hist[d];
+      if (total <= MPC_SC2_ENTRIES) break;          // no eviction: every nonzero slot (threshold 1)
+    }
+    int d = 255;
+    for (; d > 0 && hist[d] < need; d--) need -= hist[d];
+    prefix = (prefix << 8) | (u64)d;
+    if (shift == 0) threshold = prefix;             // the 1024th largest slot (slots are distinct)
+  }
+  if ((e = hipMemsetAsync(d_work + 256, 0, sizeof(uint32_t), h->stream)) != hipSuccess ||
+      (e = mpc_launch_sc2_collect(h->sc2.d_hash, n_slots, threshold, d_out, d_work + 256, grid, h->stream)) != hipSuccess)
+    return fail("sc2 collect", e);
+  uint32_t count = 0;
+  std::vector<u64> kept(MPC_SC2_ENTRIES);
+  if ((e = hipMemcpyAsync(&count, d_work + 256, sizeof(count), hipMemcpyDeviceToHost, h->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(kept.data(), d_out, kept.size() * sizeof(u64), hipMemcpyDeviceToHost, h->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(h->stream)) != hipSuccess)
+    return fail("sc2 collect", e);
+  (void)hipFree(d_work);
+  if (count == 0 || count > MPC_SC2_ENTRIES) return set_err(h, MPC_E_HIP, "sc2: selection returned " + std::to_string(count) + " symbols");
+  kept.resize(count);
+  std::sort(kept.begin(), kept.end(), [](u64 a, u64 b) { return (uint32_t)a < (uint32_t)b; });
+  std::vector<uint32_t> sym(count);
+  std::vector<uint64_t> freq(count);
+  for (uint32_t i = 0; i < count; i++) {
+    sym[i] = (uint32_t)kept[i];
+    freq[i] = kept[i] >> 32;
+  }
+  std::vector<uint16_t> len(count);
+  if (mpcsc2::code_lengths(sym.data(), freq.data(), count, len.data()) != 0) return set_err(h, MPC_E_INVAL, "sc2: empty warm-up sample");
+  std::vector<uint32_t> image;
+  MpcSc2Table t{};
+  if (!mpcsc2::layout(sym, len, image, t)) return set_err(h, MPC_E_HIP, "sc2: no bucket layout found for the code table");
+  HIPCHK(h, hipMemcpy(h->sc2.d_buckets, image.data(), image.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  t.buckets = h->sc2.d_buckets;
+  h->sc2.tab = t;
+  h->sc2.symbols = std::move(sym);
+  h->sc2.lengths = std::move(len);
+  h->sc2.built = true;
+  (void)hipFree(h->sc2.d_hash);                     // the counts are not needed again
+  h->sc2.d_hash = nullptr;
+  return MPC_OK;
+}
+
+// SC2: a call's lines split at line S of the trace -- warm-up counts before it, the table build at it, sizing after
+int launch_sc2(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s)
+{
+  const u64 warm = h->sc2.seen < h->sc2.S ? std::min<u64>(n, h->sc2.S - h->sc2.seen) : 0;
+  if (warm) {
+    hipError_t e = mpc_launch_sc2_count(d_lines, warm, h->L, h->sc2.d_hash, h->sc2.hash_mask, d_sizes, d_sel, h->d_raw, s);
+    if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    h->sc2.seen += warm;
+    h->sc2.lines += warm;
+    h->sc2.warm += warm;
+  }
+  if (warm == n) return MPC_OK;
+  if (!h->sc2.built) {
+    int rc = sc2_build(h, s);
+    if (rc != MPC_OK) return rc;
+  }
+  const u64 rest = n - warm;
+  // persistent: a workgroup loads the table once; 32 KiB of LDS for the largest table leaves room for 4 per CU
+  const int per_cu = h->sc2.tab.mask + 1 > 1024 ? 4 : 8;
+  hipError_t e = mpc_launch_sc2_size(static_cast<const uint8_t *>(d_lines) + warm * (u64)h->L, rest, h->L, &h->sc2.tab,
+                                     d_sizes ? d_sizes + warm : nullptr, d_sel ? d_sel + warm : nullptr, h->d_raw,
+                                     grid_for(h, rest * (u64)h->L / 16 + 1, 256 * 4, per_cu), s);
+  if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  h->sc2.seen += rest;
+  h->sc2.lines += rest;
   return MPC_OK;
 }
 
@@ -420,6 +542,16 @@ int sync_all(mpc_handle *h)
 // raw device statistics -> ABI vector (added into `vec`)
 void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<u64> &vec)
 {
+  if (h->algorithm == 4) {
+    // lines and warm-up lines are counted by the host (it splits every call at line S); bits and hits on the device
+    vec[0] += h->sc2.lines;
+    vec[1] += h->sc2.lines * 8ull * (u64)h->L;
+    vec[2] += raw[0];
+    vec[3] += h->sc2.warm;
+    vec[4] += h->sc2.symbols.size();
+    vec[5] += raw[1];
+    return;
+  }
   if (h->algorithm == 3) {
     // lines are not recoverable from the pattern counts: the kernel counts compressed bits per line,
     // and every line contributes exactly 33 planes = TotalWords / 33
@@ -633,6 +765,77 @@ int mpc_create_fpc(unsigned line_size, int device, mpc_handle **out)
   return MPC_OK;
 }
 
+uint64_t mpc_sc2_sampling_lines(uint64_t num_lines)
+{
+  // main.cpp:110-113: max(10000, min(numLines / 100, WARM_UP_CNT))
+  return std::max<uint64_t>(10000, std::min<uint64_t>(num_lines / 100, 1000000));
+}
+
+int mpc_sc2_code_lengths(const uint32_t *symbols, const uint64_t *freqs, size_t n, uint16_t *len_out)
+{
+  if (n == 0 || !symbols || !freqs || !len_out) return MPC_E_INVAL;
+  std::vector<uint32_t> sorted(symbols, symbols + n);
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return MPC_E_INVAL;   // a frequency map has distinct keys
+  return mpcsc2::code_lengths(symbols, freqs, n, len_out) == 0 ? MPC_OK : MPC_E_INVAL;
+}
+
+int mpc_create_sc2(unsigned line_size, uint64_t sampling_lines, int device, mpc_handle **out)
+{
+  if (!out) return MPC_E_INVAL;
+  *out = nullptr;
+  if (line_size < 4 || line_size > MPC_MAX_LINE || (line_size % 4)) {
+    g_create_error = "SC2 line size must be a multiple of 4 in 4.." + std::to_string(MPC_MAX_LINE) + " bytes";
+    return MPC_E_INVAL;
+  }
+  if (sampling_lines == 0) {
+    g_create_error = "SC2 needs at least one warm-up line (the reference builds its table from an empty map otherwise)";
+    return MPC_E_INVAL;
+  }
+  const u64 words = sampling_lines * (u64)(line_size / 4);
+  if (sampling_lines > (1ull << 28) || words > (1ull << 28)) {
+    g_create_error = "SC2 warm-up sample of more than 2^28 words (its frequency table would exceed 4 GiB)";
+    return MPC_E_INVAL;
+  }
+  mpc_handle *h = new (std::nothrow) mpc_handle();
+  if (!h) return MPC_E_NOMEM;
+  h->algorithm = 4;
+  h->L = (int)line_size;
+  h->raw_len = MPC_SC2_RAW_LEN;
+  h->stats_len = 6;
+  h->sc2.S = sampling_lines;
+  u64 slots = 2;
+  while (slots < 2 * words) slots <<= 1;
+  h->sc2.hash_mask = slots - 1;
+  int rc = pick_device(device, &h->device, &h->num_cus);
+  if (rc == MPC_OK) rc = finish_create(h);
+  if (rc == MPC_OK && (hipMalloc((void **)&h->sc2.d_hash, slots * sizeof(u64)) != hipSuccess ||
+                       hipMalloc((void **)&h->sc2.d_buckets, MPC_SC2_MAX_BUCKETS * sizeof(uint4)) != hipSuccess ||
+                       hipMemset(h->sc2.d_hash, 0, slots * sizeof(u64)) != hipSuccess ||
+                       hipDeviceSynchronize() != hipSuccess)) {        // (the kernels run on non-blocking streams)
+    g_create_error = "hipMalloc of the SC2 frequency table (" + std::to_string(slots * sizeof(u64)) + " bytes) failed";
+    rc = MPC_E_NOMEM;
+  }
+  if (rc != MPC_OK) {
+    mpc_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return MPC_OK;
+}
+
+int mpc_sc2_table(mpc_handle *h, uint32_t *symbols, uint16_t *lengths, size_t cap, size_t *n)
+{
+  if (!h || !n || h->algorithm != 4) return MPC_E_INVAL;
+  const size_t m = h->sc2.symbols.size();
+  *n = m;
+  if (m == 0) return MPC_OK;
+  if (cap < m || !symbols || !lengths) return MPC_E_INVAL;
+  std::memcpy(symbols, h->sc2.symbols.data(), m * sizeof(uint32_t));
+  std::memcpy(lengths, h->sc2.lengths.data(), m * sizeof(uint16_t));
+  return MPC_OK;
+}
+
 void mpc_destroy(mpc_handle *h)
 {
   if (!h) return;
@@ -658,6 +861,8 @@ void mpc_destroy(mpc_handle *h)
   if (h->d_tab) (void)hipFree(h->d_tab);
   if (h->d_gtab) (void)hipFree(h->d_gtab);
   if (h->d_raw) (void)hipFree(h->d_raw);
+  if (h->sc2.d_hash) (void)hipFree(h->sc2.d_hash);
+  if (h->sc2.d_buckets) (void)hipFree(h->sc2.d_buckets);
   delete h;
 }
 
@@ -668,9 +873,9 @@ int mpc_get_info(const mpc_handle *h, mpc_info *info)
   info->algorithm = h->algorithm;
   info->line_size = h->L;
   info->num_modules = h->algorithm == 0 ? h->cfg.M : 0;
-  info->num_clusters = h->algorithm == 0 ? h->cfg.M + 1 : (h->algorithm == 1 ? 9 : (h->algorithm == 2 ? 8 : 7));
+  info->num_clusters = h->algorithm == 0 ? h->cfg.M + 1 : (h->algorithm == 1 ? 9 : (h->algorithm == 2 ? 8 : h->algorithm == 3 ? 7 : 2));
   info->hist_bins = h->algorithm == 0 ? h->cfg.hist_bins : 0;
-  info->kernel_path = h->algorithm == 3 ? MPC_PATH_BPC : h->algorithm == 2 ? MPC_PATH_FPC
+  info->kernel_path = h->algorithm == 4 ? MPC_PATH_SC2 : h->algorithm == 3 ? MPC_PATH_BPC : h->algorithm == 2 ? MPC_PATH_FPC
                       : h->algorithm == 1 ? MPC_PATH_BDI : (h->plan.fast ? MPC_PATH_VPC_FAST : MPC_PATH_VPC_GENERIC);
   info->device = h->device;
   info->stats_len = h->stats_len;
@@ -708,6 +913,7 @@ long long mpc_jit_compile_check(const char *json_text, char *log, size_t cap)
 const char *mpc_kernel_form(const mpc_handle *h)
 {
   if (!h) return "";
+  if (h->algorithm == 4) return h->sc2.built ? "table sizing" : "warm-up counting";
   if (h->algorithm != 0) return "unrolled";
   if (!h->plan.fast) return "generic";
   if (h->jit.mod) return h->jit.from_cache ? "unrolled, compiled at creation (from the cache)" : "unrolled, compiled at creation";
@@ -1011,6 +1217,7 @@ int mpc_stats_reset(mpc_handle *h)
   HIPCHK(h, hipDeviceSynchronize());
   HIPCHK(h, hipMemset(h->d_raw, 0, (h->raw_len + kRouteWords) * sizeof(u64)));
   h->extra.assign(h->stats_len, 0);
+  h->sc2.lines = h->sc2.warm = 0;     // SC2: the table and the line counter stay
   return MPC_OK;
 }
 

@@ -46,13 +46,14 @@ typedef struct mpc_handle mpc_handle;
 #define MPC_PATH_BDI          3
 #define MPC_PATH_FPC          4
 #define MPC_PATH_BPC          5
+#define MPC_PATH_SC2          6
 
 typedef struct {
   int32_t abi_version;
-  int32_t algorithm;        /* 0 = VPC, 1 = BDI, 2 = FPC, 3 = BPC */
+  int32_t algorithm;        /* 0 = VPC, 1 = BDI, 2 = FPC, 3 = BPC, 4 = SC2 */
   int32_t line_size;        /* bytes per line (L) */
   int32_t num_modules;      /* VPC: M; BDI: 0 */
-  int32_t num_clusters;     /* VPC: M+1 (cluster -1 .. M-1); BDI: 9 states; FPC: 8 prefixes; BPC: 7 patterns */
+  int32_t num_clusters;     /* VPC: M+1 (cluster -1 .. M-1); BDI: 9 states; FPC: 8 prefixes; BPC: 7 patterns; SC2: 2 (warm-up, table) */
   int32_t hist_bins;        /* VPC: bins per cluster in the stats vector */
   int32_t kernel_path;      /* MPC_PATH_* */
   int32_t device;           /* HIP device ordinal the handle is bound to */
@@ -81,6 +82,31 @@ int mpc_create_fpc(unsigned line_size, int device, mpc_handle **out);
  * BPC.cpp:98).  Defined where the source is undefined: words are zero-extended to 64 bits
  * (BPC.cpp:42-44 copies 4 bytes into an uninitialised int64_t).  Parity is unpinned.       */
 int mpc_create_bpc(unsigned line_size, int device, mpc_handle **out);
+/* `new comp::SC2(lineSize, warmupCnt)` (SC2.h:100-107): a Huffman code over the line's 32-bit little-endian words
+ * (SC2.cpp:270-333), with its table built once from a warm-up sample.  Lines 0 .. S-1 of the trace (S =
+ * sampling_lines; lines are counted across every call on the handle, whichever ingestion path they come through)
+ * only add their words to the frequency counts and cost W x 33 bits each (W = line_size / 4, the table is still
+ * empty).  When line S arrives the table is built: the 1024 most frequent words (ties: the larger word is kept),
+ * the reference's own heap replayed on the host (mpc_sc2_code_lengths), code length = depth in the tree (a table of
+ * one symbol has length 0).  Line S and every later line cost, per word, its code length if it is in the table and
+ * 33 bits if not.  Per-line output: size in bits; `selected` is 0 for a warm-up line and 1 for a table line.
+ * That build is the one blocking point of an SC2 handle: it synchronises the stream of the call that reaches line S
+ * (for mpc_compress_batch_device the caller's hip_stream, which must also carry or have completed the earlier
+ * warm-up calls), selects the table on the device, builds it on the host and uploads it.
+ * line_size: a multiple of 4 up to 256.  sampling_lines: 1 .. with sampling_lines x line_size / 4 <= 2^28 (the
+ * warm-up frequency table, two 8-byte slots per sampled word rounded up to a power of two, is allocated at creation
+ * and freed after the build).  S = 0 is undefined in the reference (MPC_E_INVAL).  A new trace needs a new handle.  */
+int mpc_create_sc2(unsigned line_size, uint64_t sampling_lines, int device, mpc_handle **out);
+/* The reference driver's warm-up length for a trace of num_lines lines (main.cpp:110-113; numLines is the loader's
+ * GetNumLines(): every row of a .npy, every complete record of a GPGPU-Sim .log): max(10000, min(num_lines / 100, 10^6)). */
+uint64_t mpc_sc2_sampling_lines(uint64_t num_lines);
+/* The host table builder every SC2 handle uses, without a device: code lengths of n distinct symbols with their
+ * warm-up frequencies, written in input order; when n > 1024 the symbols outside the 1024 largest (freq, symbol)
+ * pairs get 0xFFFF.  MPC_E_INVAL for n == 0 or a repeated symbol.                                                 */
+int mpc_sc2_code_lengths(const uint32_t *symbols, const uint64_t *freqs, size_t n, uint16_t *len_out);
+/* The handle's code table in ascending symbol order: *n symbols (0 before line S has been seen); symbols and lengths
+ * need room for *n entries (at most 1024).                                                                          */
+int mpc_sc2_table(mpc_handle *h, uint32_t *symbols, uint16_t *lengths, size_t cap, size_t *n);
 void mpc_destroy(mpc_handle *h);
 
 int mpc_get_info(const mpc_handle *h, mpc_info *info);
@@ -139,6 +165,9 @@ int mpc_sync(mpc_handle *h);
  *             Prefix0..7 (FPC.h:13-23); TotalWords = their sum.
  * BPC layout: [0] lines [1] original_bits [2] compressed_bits [3] TotalWords [4..10] Counts in
  *             BPCPattern order (BPC.h:12-21).
+ * SC2 layout: [0] lines [1] original_bits [2] compressed_bits [3] warm-up lines [4] table symbols
+ *             [5] words found in the table.  mpc_stats_reset clears the statistics only: the table and the
+ *             handle's line counter (which line is line S) stay.
  */
 int mpc_stats_len(const mpc_handle *h, uint64_t *len);
 int mpc_stats_get(mpc_handle *h, uint64_t *vec, size_t n);      /* syncs */
@@ -147,12 +176,13 @@ int mpc_stats_set(mpc_handle *h, const uint64_t *vec, size_t n);   /* = (after a
 
 /* Device-side exchange (multi-GPU without a host round trip).  The handle's device
  * accumulators ("raw" statistics: VPC [sum_r(K)] [sum_r2(K)] [histogram(K x B)], BDI
- * [Counts(9)] [compressed_bits], FPC [Counts(8)] [compressed_bits], BPC [Counts(7)] [TotalWords] [compressed_bits]) are plain
- * uint64 sums, so ranks may all-reduce them
+ * [Counts(9)] [compressed_bits], FPC [Counts(8)] [compressed_bits], BPC [Counts(7)] [TotalWords] [compressed_bits], SC2
+ * [compressed_bits] [words_in_table]) are plain uint64 sums, so ranks may all-reduce them
  * directly: mpc_stats_copy_raw_device enqueues an asynchronous device-to-device copy of
  * the raw_len words into d_dst on hip_stream (after everything already enqueued there),
  * and mpc_stats_from_raw turns such an array -- on the host, e.g. after the all-reduce --
- * into the statistics vector described above (merged-in host statistics not included). */
+ * into the statistics vector described above (merged-in host statistics not included; SC2 takes [0], [1], [3] and
+ * [4], which the host counts, from this handle). */
 int mpc_stats_raw_len(const mpc_handle *h, uint64_t *raw_len);
 int mpc_stats_copy_raw_device(mpc_handle *h, void *d_dst, void *hip_stream);
 int mpc_stats_from_raw(const mpc_handle *h, const uint64_t *raw, size_t raw_len, uint64_t *vec, size_t n);

@@ -75,6 +75,10 @@ struct Slot {
   bool busy = false;
 };
 
+// the kernel a VPC configuration runs (route_vpc), and why it is the generic one
+enum class VpcKernel { BuiltIn, BuiltInGeneral, AtCreation, RuntimeLoop, Generic };
+struct VpcRoute { VpcKernel kernel = VpcKernel::Generic; std::string why_generic; };
+
 }  // namespace
 
 struct mpc_handle {
@@ -84,6 +88,8 @@ struct mpc_handle {
   int num_cus = 256;
   mpc::VpcConfig cfg;
   mpc::VpcPlan plan;
+  MpcVpcParams params;           // VPC: plan.params with the device addresses of the tables, what the kernels get
+  VpcRoute route;                // VPC: decided once, at creation
   hipStream_t stream = nullptr;
   uint32_t *d_tab = nullptr;
   uint8_t *d_gtab = nullptr;
@@ -98,7 +104,7 @@ struct mpc_handle {
   // device-visible buffer the kernel reads the lines from and writes the results to directly --
   // no staging copies, no 64 MiB slots; a call is one launch and one stream synchronisation
   uint8_t *mini = nullptr;       // [kMiniLines * L] lines | [kMiniLines] uint16 sizes | [kMiniLines] int8 clusters
-  mpcjit::Kernels jit;           // VPC: the unrolled kernels of a sequence without a built-in instantiation (mpc_jit.h)
+  mpcjit::Kernels jit;           // VPC: the unrolled kernels compiled at creation (mpc_jit.h; route AtCreation)
   // SC2: lines 0 .. S-1 of the trace (counted across calls) are warm-up lines, the table is built when line S arrives
   struct {
     u64 S = 0;                   // warm-up lines (the reference's m_maxSamplingCnt)
@@ -168,6 +174,28 @@ int finish_create(mpc_handle *h)
   return MPC_OK;
 }
 
+// The one place that picks the kernel of a VPC configuration.  `jit`: a compilation at creation (mpc_jit.h) is only
+// predicted (describe, compile check), still to be tried or tried and failed (a handle).
+enum class Jit { Predicted, Pending, Failed };
+
+VpcRoute route_vpc(const mpc::VpcPlan &plan, Jit jit)
+{
+  const MpcVpcParams &P = plan.params;
+  if (!plan.fast) return {VpcKernel::Generic, plan.why_generic};
+  if (mpc_vpc_lane_unrolled(&P)) return {P.gen_layout ? VpcKernel::BuiltInGeneral : VpcKernel::BuiltIn, ""};  // (never runtime_only)
+  // switched on, a layout the generated source has, a sequence not too long, rings that fit beside the histogram with some
+  // workgroup size (a fast plan has 32-, 64- or 128-byte lines)
+  const char *env = std::getenv("MPC_JIT");
+  const bool compilable = !(env && std::strcmp(env, "0") == 0) && (!P.runtime_only || plan.jit_needs) && P.n_pred >= 1 &&
+                          P.n_pred <= mpcjit::max_modules() && mpc_vpc_lane_ring_plan(&P, nullptr, nullptr) != 0;
+  if (compilable && jit != Jit::Failed) return {VpcKernel::AtCreation, ""};
+  const unsigned no_loop = plan.jit_needs & mpc::JIT_NO_LOOP;      // (layouts the run-time module loop lacks too)
+  if (!no_loop) return {VpcKernel::RuntimeLoop, ""};
+  const std::string it = (no_loop & mpc::JIT_PLANES) ? "them" : "it";
+  return {VpcKernel::Generic, mpc::jit_need_text(no_loop) + (jit == Jit::Predicted ? ", and run-time compilation is not available for " + it
+                                                                                   : ", and the kernel for " + it + " could not be compiled at creation")};
+}
+
 int create_vpc_from_text(const std::string &text, int device, mpc_handle **out)
 {
   if (!out) return MPC_E_INVAL;
@@ -198,29 +226,24 @@ int create_vpc_from_text(const std::string &text, int device, mpc_handle **out)
     }
   }
   if (rc == MPC_OK) {
-    h->plan.params.tab = h->d_tab;
-    h->plan.params.gtab = h->d_gtab;
-    // a module sequence without a built-in unrolled instantiation: compile it now (mpc_jit.h); when that is not
-    // possible the run-time module loop takes the configuration, and says so
-    if (mpcjit::eligible(h->plan.params, h->plan.fast)) {
+    h->params = h->plan.params;
+    h->params.tab = h->d_tab;
+    h->params.gtab = h->d_gtab;
+    // no built-in instantiation: compile it now (mpc_jit.h); when that fails, the configuration is routed without it and says so
+    h->route = route_vpc(h->plan, Jit::Pending);
+    if (h->route.kernel == VpcKernel::AtCreation) {
       std::string why;
       (void)hipSetDevice(h->device);
-      if (!mpcjit::build(h->plan.params, MPC_TESTING, h->jit, why, h->plan.gtab.data()))
+      if (!mpcjit::build(h->plan, MPC_TESTING, h->jit, why)) {
+        h->route = route_vpc(h->plan, Jit::Failed);
         std::fprintf(stderr, "libmpc_hip: module sequence [%s] runs the %s: %s\n", mpcjit::kinds_of(h->plan.params).c_str(),
-                     (h->plan.params.planes_differ || h->plan.params.gather_unrolled || h->plan.params.wshift_unrolled) ? "generic kernel (some hundred times slower)" : "run-time module loop (several times slower)",
+                     h->route.kernel == VpcKernel::Generic ? "generic kernel (some hundred times slower)" : "run-time module loop (several times slower)",
                      why.c_str());
-    }
-    if (h->plan.fast && (h->plan.params.planes_differ || h->plan.params.gather_unrolled || h->plan.params.wshift_unrolled) && !h->jit.mod) {
-      // scan tables of different sizes, base tables that are not windowed: only a kernel compiled at creation evaluates them
-      // on the fast path
-      h->plan.fast = false;
-      h->plan.why_generic = h->plan.params.planes_differ ? "scan tables of different sizes, and the kernel for them could not be compiled at creation"
-                                                         : h->plan.params.gather_unrolled ? "BaseIndexTable is not windowed (own/previous dword), and the kernel for it could not be compiled at creation"
-                                                         : "WeightTable uses more than two shift distances, and the kernel for it could not be compiled at creation";
+      }
     }
     // the statistics accumulators of a workgroup live in LDS
-    const size_t smem = h->jit.mod ? mpc_vpc_lane_ring_plan(&h->plan.params, nullptr, nullptr)
-                        : h->plan.fast ? mpc_vpc_lane_smem(&h->plan.params) : mpc_vpc_generic_smem(&h->plan.params);
+    const size_t smem = h->route.kernel == VpcKernel::AtCreation ? mpc_vpc_lane_ring_plan(&h->plan.params, nullptr, nullptr)
+                        : h->route.kernel == VpcKernel::Generic ? mpc_vpc_generic_smem(&h->plan.params) : mpc_vpc_lane_smem(&h->plan.params);
     if (smem > 160 * 1024) {
       g_create_error = "histogram does not fit the 160 KiB LDS (too many clusters x bins)";
       rc = MPC_E_INVAL;
@@ -331,13 +354,13 @@ int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t 
     e = mpc_launch_fpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
   } else if (h->algorithm == 1) {
     e = mpc_launch_bdi(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
-  } else if (h->jit.mod) {
-    e = mpc_launch_vpc_lane_jit(h->jit.stats, h->jit.lines, d_lines, n, &h->plan.params, d_sizes, d_sel, h->d_raw,
+  } else if (h->route.kernel == VpcKernel::AtCreation) {
+    e = mpc_launch_vpc_lane_jit(h->jit.stats, h->jit.lines, d_lines, n, &h->params, d_sizes, d_sel, h->d_raw,
                                 grid_for(h, n, 256, kWgPerCu), s);
-  } else if (h->plan.fast) {
-    e = mpc_launch_vpc_lane(d_lines, n, &h->plan.params, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
-  } else {
-    e = mpc_launch_vpc_generic(d_lines, n, &h->plan.params, d_sizes, d_sel, h->d_raw, grid_for(h, n, 128, 8), s);
+  } else if (h->route.kernel == VpcKernel::Generic) {
+    e = mpc_launch_vpc_generic(d_lines, n, &h->params, d_sizes, d_sel, h->d_raw, grid_for(h, n, 128, 8), s);
+  } else {     // built in or the run-time module loop: the lane launcher finds which
+    e = mpc_launch_vpc_lane(d_lines, n, &h->params, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
   }
   if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   return MPC_OK;
@@ -857,7 +880,6 @@ void mpc_destroy(mpc_handle *h)
     (void)hipStreamDestroy(h->stream);
   }
   if (h->mini) (void)hipHostFree(h->mini);
-  mpcjit::unload(h->jit);
   if (h->d_tab) (void)hipFree(h->d_tab);
   if (h->d_gtab) (void)hipFree(h->d_gtab);
   if (h->d_raw) (void)hipFree(h->d_raw);
@@ -876,7 +898,7 @@ int mpc_get_info(const mpc_handle *h, mpc_info *info)
   info->num_clusters = h->algorithm == 0 ? h->cfg.M + 1 : (h->algorithm == 1 ? 9 : (h->algorithm == 2 ? 8 : h->algorithm == 3 ? 7 : 2));
   info->hist_bins = h->algorithm == 0 ? h->cfg.hist_bins : 0;
   info->kernel_path = h->algorithm == 4 ? MPC_PATH_SC2 : h->algorithm == 3 ? MPC_PATH_BPC : h->algorithm == 2 ? MPC_PATH_FPC
-                      : h->algorithm == 1 ? MPC_PATH_BDI : (h->plan.fast ? MPC_PATH_VPC_FAST : MPC_PATH_VPC_GENERIC);
+                      : h->algorithm == 1 ? MPC_PATH_BDI : (h->route.kernel != VpcKernel::Generic ? MPC_PATH_VPC_FAST : MPC_PATH_VPC_GENERIC);
   info->device = h->device;
   info->stats_len = h->stats_len;
   return MPC_OK;
@@ -896,11 +918,10 @@ long long mpc_jit_compile_check(const char *json_text, char *log, size_t cap)
   if (rc == 0) {
     mpc::VpcPlan plan;
     mpc::build_vpc_plan(cfg, plan);
-    if (!mpcjit::eligible(plan.params, plan.fast)) return 0;
-    unsigned ring_cfg = 0;
-    const size_t smem = mpc_vpc_lane_ring_plan(&plan.params, &ring_cfg, nullptr);
+    if (route_vpc(plan, Jit::Predicted).kernel != VpcKernel::AtCreation) return 0;
+    const size_t smem = mpc_vpc_lane_ring_plan(&plan.params, nullptr, nullptr);
     std::string code;
-    if (mpcjit::compile(mpcjit::source_of(plan.params, smem, MPC_TESTING, plan.gtab.data()), "gfx950", mpcjit::source_dir(), code, err)) return (long long)code.size();
+    if (mpcjit::compile(mpcjit::source_of(plan, smem, MPC_TESTING), "gfx950", mpcjit::source_dir(), code, err)) return (long long)code.size();
     rc = MPC_E_HIP;
   }
   if (log && cap) {
@@ -915,15 +936,14 @@ const char *mpc_kernel_form(const mpc_handle *h)
   if (!h) return "";
   if (h->algorithm == 4) return h->sc2.built ? "table sizing" : "warm-up counting";
   if (h->algorithm != 0) return "unrolled";
-  if (!h->plan.fast) return "generic";
-  if (h->jit.mod) return h->jit.from_cache ? "unrolled, compiled at creation (from the cache)" : "unrolled, compiled at creation";
-  if (!mpc_vpc_lane_unrolled(&h->plan.params)) return "run-time loop";
-  return h->plan.params.gen_layout ? "unrolled, general layout" : "unrolled";
+  if (h->route.kernel == VpcKernel::AtCreation && h->jit.from_cache) return "unrolled, compiled at creation (from the cache)";
+  static const char *const form[] = {"unrolled", "unrolled, general layout", "unrolled, compiled at creation", "run-time loop", "generic"};
+  return form[(int)h->route.kernel];      // (VpcKernel order)
 }
 
 const char *mpc_path_reason(const mpc_handle *h)
 {
-  return (h && h->algorithm == 0 && !h->plan.fast) ? h->plan.why_generic.c_str() : "";
+  return (h && h->algorithm == 0) ? h->route.why_generic.c_str() : "";
 }
 
 int mpc_compress_batch_device(mpc_handle *h, const void *d_lines, uint64_t n, uint16_t *d_sizes, int8_t *d_sel,
@@ -1244,21 +1264,16 @@ int mpc_config_describe(const char *json_text, char *out, size_t cap)
   } else {
     mpc::VpcPlan plan;
     mpc::build_vpc_plan(cfg, plan);
-    if (plan.fast && (plan.params.planes_differ || plan.params.gather_unrolled || plan.params.wshift_unrolled) && !mpcjit::eligible(plan.params, true)) {      // (as mpc_create_vpc* decides)
-      plan.fast = false;
-      plan.why_generic = plan.params.planes_differ ? "scan tables of different sizes, and run-time compilation is not available for them"
-                                                   : plan.params.gather_unrolled ? "BaseIndexTable is not windowed (own/previous dword), and run-time compilation is not available for it"
-                                                   : "WeightTable uses more than two shift distances, and run-time compilation is not available for it";
-    }
+    const VpcRoute r = route_vpc(plan, Jit::Predicted);
+    const bool fast = r.kernel != VpcKernel::Generic, unrolled = fast && r.kernel != VpcKernel::RuntimeLoop;
     s = "{\"L\": " + std::to_string(cfg.L) + ", \"M\": " + std::to_string(cfg.M) + ", \"n_pred\": " + std::to_string(cfg.n_pred) +
         ", \"has_aws\": " + (cfg.has_aws ? "true" : "false") + ", \"hist_bins\": " + std::to_string(cfg.hist_bins) + ", \"enc_bits\": [";
     for (size_t i = 0; i < cfg.enc_bits.size(); i++) s += (i ? ", " : "") + std::to_string(cfg.enc_bits[i]);
-    s += "], \"path\": \"" + std::string(plan.fast ? "fast" : "generic") + "\", \"why_generic\": \"" + plan.why_generic +
-         "\", \"sequence\": \"" + std::string(!plan.fast ? "" : (mpc_vpc_lane_unrolled(&plan.params) || mpcjit::eligible(plan.params, plan.fast) ? "unrolled" : "run-time loop")) +
-         "\", \"compiled\": \"" + std::string(!plan.fast ? "" : mpc_vpc_lane_unrolled(&plan.params) ? "built in" :
-                                            mpcjit::eligible(plan.params, plan.fast) ? "at creation" : "") +
-         "\", \"general_layout\": \"" + std::string(plan.fast && plan.params.gen_layout && (mpc_vpc_lane_unrolled(&plan.params) || mpcjit::eligible(plan.params, plan.fast)) ? "yes" : "no") +
-         "\", \"scan_order\": \"" + std::string(!plan.fast ? "" : (plan.params.byte_major ? "byte-major" : "plane-major")) +
+    s += "], \"path\": \"" + std::string(fast ? "fast" : "generic") + "\", \"why_generic\": \"" + r.why_generic +
+         "\", \"sequence\": \"" + std::string(!fast ? "" : unrolled ? "unrolled" : "run-time loop") +
+         "\", \"compiled\": \"" + std::string(!unrolled ? "" : r.kernel == VpcKernel::AtCreation ? "at creation" : "built in") +
+         "\", \"general_layout\": \"" + std::string(unrolled && plan.params.gen_layout ? "yes" : "no") +
+         "\", \"scan_order\": \"" + std::string(!fast ? "" : (plan.params.byte_major ? "byte-major" : "plane-major")) +
          "\", \"modules\": [";
     for (int i = 0; i < cfg.M; i++) {
       const mpc::Module &m = cfg.modules[(size_t)i];

@@ -187,10 +187,23 @@ inline int parse_vpc_config(const std::string &text, VpcConfig &cfg, std::string
 // kernel plan
 // ---------------------------------------------------------------------------
 
+// layouts only a lane kernel compiled at creation evaluates (the -DMPC_JIT_* switches of mpc_jit.h); the run-time module
+// loop has the first two, the others (JIT_NO_LOOP) only the generic kernel
+enum JitNeed : unsigned { JIT_BM = 1, JIT_ANYROOT = 2, JIT_PLANES = 4, JIT_GATHER = 8, JIT_WSHIFT = 16,
+                          JIT_NO_LOOP = JIT_PLANES | JIT_GATHER | JIT_WSHIFT };
+
+// the subject of the reason texts of a configuration with JIT_NO_LOOP needs
+inline const char *jit_need_text(unsigned needs)
+{
+  return (needs & JIT_PLANES) ? "scan tables of different sizes" : (needs & JIT_GATHER) ? "BaseIndexTable is not windowed (own/previous dword)"
+                                                                  : "WeightTable uses more than two shift distances";
+}
+
 struct VpcPlan {
   bool fast = false;
   std::string why_generic;         // reason the fast path was not taken
-  MpcVpcParams params;             // tab / gtab left null; filled by the caller
+  unsigned jit_needs = 0;          // JitNeed bits of a fast configuration
+  MpcVpcParams params;             // tab / gtab left null: the handle's launch copy gets them
   std::vector<uint32_t> tab;       // fast-path dword tables
   std::vector<uint8_t> gtab;       // generic-path byte tables
 };
@@ -266,7 +279,10 @@ inline void build_vpc_plan(const VpcConfig &cfg, VpcPlan &plan)
   // ---- fast-path classification ----
   plan.fast = true;
   plan.why_generic.clear();
+  plan.jit_needs = 0;
   plan.tab.clear();
+  bool planes_differ = false, any_gather = false, any_wshift = false;
+  int max_root = 0;
   auto no = [&](const std::string &why) { plan.fast = false; if (plan.why_generic.empty()) plan.why_generic = why; };
   if (!(L == 32 || L == 64 || L == 128)) no("lineSize not in {32,64,128}");
   for (int q = 0; q < cfg.n_pred && plan.fast; q++) {
@@ -286,20 +302,13 @@ inline void build_vpc_plan(const VpcConfig &cfg, VpcPlan &plan)
       // different sizes: only when every plane-major table stops after a whole number of bit planes (a per-module mask)
       auto whole = [&](const Module &x) { return x.table_size == 8 * L || (x.table_size >= L && x.table_size % L == 0); };
       if (bm0 || !whole(m) || !whole(m0)) { no(tag + "scan tables of different sizes"); break; }
-      P.planes_differ = 1;
+      planes_differ = true;
     }
     P.byte_major = bm0 ? 1 : 0;
-    if (bm0) P.runtime_only = 1;
     // any root for OneBase / DiffBase / WeightBase: the residue array is the natural one with bytes 0..root
-    // rotated by one position (ResidueModule.cpp:24-39).  Roots 1..15 (the rotation stays inside the first row of the
-    // scanned array) and truncated plane-major tables whose row 0 is complete (TableSize >= 16) run on the unrolled
-    // kernels' general-layout twins; roots above 15, the byte-major order and tables of fewer than 16 entries on the
-    // run-time module loop
+    // rotated by one position (ResidueModule.cpp:24-39)
     f.root = m.root;
-    if (m.root != 0 || m.table_size != 8 * L) {
-      if (m.root <= 15 && !bm0 && m.table_size >= 16) P.gen_layout = 1;
-      else P.runtime_only = 1;
-    }
+    if (m.root > max_root) max_root = m.root;
     f.cx = m.consecutive_xor ? 1 : 0;
     f.plane_mask = (bm0 || m.table_size >= 8 * L || m.table_size < L) ? ~0u : ((0xff00u >> (m.table_size / L)) & 0xffu) * 0x01010101u;
     f.tab_off = (int32_t)plan.tab.size();
@@ -362,10 +371,8 @@ inline void build_vpc_plan(const VpcConfig &cfg, VpcPlan &plan)
       }
       // MPC_FK_WEIGHT: class 1 unshifted, class 2 a right shift (or absent); anything else is WEIGHT2
       f.kind = (!wgen && shifts[0] == 0 && shifts[1] <= 0) ? MPC_FK_WEIGHT : MPC_FK_WEIGHT2;
-      if (wgen) {
-        f.wgen = 1;
-        P.wshift_unrolled = 1;
-      }
+      f.wgen = wgen ? 1 : 0;
+      any_wshift = any_wshift || wgen;
       f.ls1 = shifts[0] > 0 ? shifts[0] : 0;
       f.rs1 = shifts[0] < 0 ? -shifts[0] : 0;
       f.ls2 = shifts[1] > 0 ? shifts[1] : 0;
@@ -377,10 +384,7 @@ inline void build_vpc_plan(const VpcConfig &cfg, VpcPlan &plan)
     // c1 split into its low-7-bit and MSB parts (lane-per-line kernel, WeightBase residue)
     for (size_t w = 0; w < c1.size(); w++) plan.tab.push_back(c1[w] & 0x7f7f7f7fu);
     for (size_t w = 0; w < c1.size(); w++) plan.tab.push_back(c1[w] & 0x80808080u);
-    if (gather) {
-      f.gather = 1;
-      P.gather_unrolled = 1;
-    }
+    f.gather = gather ? 1 : 0;
     if (gather || wgen) stride2 = false;
     // periodic tables: words 1.. all use "the same byte of the previous word" with identical masks /
     // constants, so the kernel needs neither the byte gather nor per-word table entries
@@ -396,58 +400,47 @@ inline void build_vpc_plan(const VpcConfig &cfg, VpcPlan &plan)
           // constants that do not repeat every 8 bytes: per-word table entries and a byte gather (two words back is outside the window)
           f.prev_word = 0;
           f.gather = 1;
-          P.gather_unrolled = 1;
           break;
         }
     }
+    any_gather = any_gather || f.gather;
   }
-  if (P.runtime_only) P.gen_layout = 0;
-  if (plan.fast && (P.gather_unrolled || P.wshift_unrolled)) {
-    if (P.byte_major || P.runtime_only || P.planes_differ) {
-      plan.fast = false;
-      plan.why_generic = P.gather_unrolled ? "BaseIndexTable is not windowed (own/previous dword), together with another layout the built-in kernels lack"
-                                           : "WeightTable uses more than two shift distances, together with another layout the built-in kernels lack";
-    } else {
-      P.runtime_only = 1;        // no built-in kernel, and not the run-time loop either (its byte gather is the windowed one)
-    }
+  // ---- kernel form ----
+  // What the layout allows (ts: TableSize, the same in every module unless the planes differ; a root of 1..15 keeps the
+  // rotated bytes inside the first row of the scanned array).  route_vpc (mpc_capi.hip) picks the kernel: a sequence
+  // without a built-in instantiation is compiled at creation, and without a compiler the last column holds.
+  //   scan order   roots   ts            not windowed / shifts > 2   runtime_only  gen_layout  jit_needs       no compiler
+  //   plane-major  0       8 L           -                           0             0           -               built in
+  //   plane-major  0..15   16 ..         -                           0             1           -               built in (twin)
+  //   plane-major  any     < 16          -                           1             0           -               run-time loop
+  //   plane-major  > 15    16 ..         -                           1             1           ANYROOT         run-time loop
+  //   plane-major  0..15   whole planes, differing                   1             1           PLANES          generic
+  //   plane-major  0..15   16 ..         yes                         1             as twin     GATHER/WSHIFT   generic
+  //   byte-major   all 0   16 ..         -                           1             ts != 8 L   BM              run-time loop
+  //   byte-major   other   or ts < 16    -                           1             0           -               run-time loop
+  //   any other combination of differing planes / not windowed / shifts > 2: the generic kernel
+  const int ts0 = cfg.n_pred > 0 ? cfg.modules[(size_t)cfg.start].table_size : 8 * L;
+  const bool twin = !P.byte_major && max_root <= 15 && ts0 >= 16;     // the layouts of the built-in kernels
+  if (plan.fast && (any_gather || any_wshift)) {
+    if (twin && !planes_differ) plan.jit_needs = (any_gather ? JIT_GATHER : 0) | (any_wshift ? JIT_WSHIFT : 0);
+    else no(std::string(jit_need_text(any_gather ? JIT_GATHER : JIT_WSHIFT)) + ", together with another layout the built-in kernels lack");
+  } else if (plan.fast && planes_differ) {
+    if (max_root <= 15) plan.jit_needs = JIT_PLANES;
+    else no(std::string(jit_need_text(JIT_PLANES)) + " together with a RootIndex above 15");
+  } else if (plan.fast && ts0 >= 16 && (P.byte_major ? max_root == 0 : max_root > 15)) {
+    plan.jit_needs = P.byte_major ? JIT_BM : JIT_ANYROOT;
   }
-  if (plan.fast && P.planes_differ) {
-    bool roots_ok = true;
-    for (int q = 0; q < cfg.n_pred; q++) roots_ok = roots_ok && P.fm[q].root <= 15;
-    if (!roots_ok) {
-      plan.fast = false;
-      plan.why_generic = "scan tables of different sizes together with a RootIndex above 15";
-    } else {
-      P.runtime_only = 1;        // no built-in kernel, and not the run-time loop either (one mask for all modules there)
-      P.gen_layout = 1;
-    }
-  }
-  if (plan.fast && !P.byte_major && cfg.n_pred > 0 && cfg.modules[(size_t)cfg.start].table_size >= 16) {
-    bool far_root = false;
-    for (int q = 0; q < cfg.n_pred; q++) far_root = far_root || P.fm[q].root > 15;
-    if (far_root) {           // (the only reason the built-in twins could not take it)
-      P.anyroot_unrolled = 1;
-      P.gen_layout = 1;
-    }
-  }
-  if (plan.fast && P.byte_major && cfg.n_pred > 0) {
-    bool roots0 = true;
-    for (int q = 0; q < cfg.n_pred; q++) roots0 = roots0 && P.fm[q].root == 0;
-    const int ts = cfg.modules[(size_t)cfg.start].table_size;
-    if (roots0 && ts >= 16) {
-      P.bm_unrolled = 1;
-      P.gen_layout = ts != 8 * L ? 1 : 0;      // (the truncation masks of the general layout)
-    }
+  if (plan.fast) {
+    P.runtime_only = (!twin || plan.jit_needs) ? 1 : 0;
+    P.gen_layout = (plan.jit_needs & JIT_BM) ? ts0 != 8 * L
+                   : (plan.jit_needs & (JIT_ANYROOT | JIT_PLANES)) || (twin && (max_root > 0 || ts0 != 8 * L));
   }
   P.plane_mask = ~0u;
-  if (plan.fast && cfg.n_pred > 0 && !P.byte_major && !P.planes_differ) {
-    const int ts = cfg.modules[(size_t)cfg.start].table_size;
-    if (ts >= L && ts % L == 0 && ts < 8 * L) P.plane_mask = ((0xff00u >> (ts / L)) & 0xffu) * 0x01010101u;
-  }
+  if (plan.fast && cfg.n_pred > 0 && !P.byte_major && !planes_differ && ts0 >= L && ts0 % L == 0 && ts0 < 8 * L)
+    P.plane_mask = ((0xff00u >> (ts0 / L)) & 0xffu) * 0x01010101u;
   P.trunc_off = -1;
-  if (plan.fast && !P.planes_differ && cfg.n_pred > 0 && cfg.modules[(size_t)cfg.start].table_size != 8 * L) {
+  if (plan.fast && !planes_differ && cfg.n_pred > 0 && ts0 != 8 * L) {
     // scanned bit i = plane i / L (0 = MSB), byte i % L, for i < TableSize: per residue byte the mask of its scanned bits
-    const int ts = cfg.modules[(size_t)cfg.start].table_size;
     while (plan.tab.size() % 4) plan.tab.push_back(0);
     P.trunc_off = (int32_t)plan.tab.size();
     for (int w = 0; w < W; w++) {
@@ -456,7 +449,7 @@ inline void build_vpc_plan(const VpcConfig &cfg, VpcPlan &plan)
         const int col = 4 * w + k;
         uint32_t bm = 0;
         for (int p = 0; p < 8; p++)
-          if ((P.byte_major ? col * 8 + p : p * L + col) < ts) bm |= 0x80u >> p;
+          if ((P.byte_major ? col * 8 + p : p * L + col) < ts0) bm |= 0x80u >> p;
         word |= bm << (8 * k);
       }
       plan.tab.push_back(word);

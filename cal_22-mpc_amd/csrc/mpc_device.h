@@ -40,10 +40,10 @@ struct MpcFastModule {
   int32_t root;       /* RootIndex (0 on the plain unrolled kernels, 0..15 on their general-layout twins; any position for
                          ONEBASE / DIFF / WEIGHT* on the run-time loop) */
   int32_t gather;     /* DIFF / WEIGHT*: 1 = the BaseIndexTable is not windowed (a base byte outside the own / previous dword): the
-                         base bytes are gathered with the table as compile-time constants (gather_unrolled configurations) */
+                         base bytes are gathered with the table as compile-time constants (mpc::JIT_GATHER configurations) */
   int32_t wgen;       /* WEIGHT*: 1 = the WeightTable has more than two shift distances: the predicted word is assembled from the
-                         table as compile-time constants (wshift_unrolled configurations) */
-  uint32_t plane_mask; /* this module's scanned bit planes, in every byte (planes_differ configurations; else unused) */
+                         table as compile-time constants (mpc::JIT_WSHIFT configurations) */
+  uint32_t plane_mask; /* this module's scanned bit planes, in every byte (mpc::JIT_PLANES configurations; else unused) */
   int32_t prev_word;  /* DIFF/WEIGHT periodic tables.  1: every base byte of words 1.. is the same byte of the
                          previous word (BaseIndexTable[i] = i - 4) and the table entries of words 1.. are
                          identical: no v_perm_b32, two table entries instead of L/4.  2: the same two words
@@ -72,8 +72,8 @@ struct MpcVpcParams {
   int32_t start;        /* module index of the first PredComp module (1 or 2) */
   int32_t has_aws;      /* module 1 is AllWordSame */
   int32_t hist_bins;    /* bins per cluster */
-  int32_t runtime_only; /* fast path, but only through the run-time module loop: a RootIndex above 15, the byte-major order, a
-                           scan table of fewer than 16 entries */
+  int32_t runtime_only; /* 1: no built-in unrolled instantiation applies (a RootIndex above 15, the byte-major order, a scan table
+                           of fewer than 16 entries, a layout only a kernel compiled at creation evaluates) */
   int32_t tab_words;    /* number of dwords in tab */
   int32_t trunc_off;    /* truncated plane-major scan table (TableSize < 8 L, the same for every module): dword offset in
                            tab of L/4 mask words (the bits of the XORed residue bytes that are scanned); -1: full table */
@@ -85,23 +85,10 @@ struct MpcVpcParams {
   const uint32_t *tab;  /* fast path dword tables (device) */
   const uint8_t *gtab;  /* generic path byte tables (device) */
   int32_t gtab_bytes;   /* size of gtab; the generic kernel keeps a copy in LDS when it fits */
-  int32_t gen_layout;   /* 1: some RootIndex is 1..15 and / or the plane-major scan table is truncated (16 <= TableSize < 8 L):
-                           the unrolled kernels' general-layout twins take it */
+  int32_t gen_layout;   /* 1: some RootIndex is not 0 and / or the scan table is truncated (16 <= TableSize < 8 L): the unrolled
+                           kernels' general-layout twins take it (0 where only the run-time module loop can) */
   uint32_t plane_mask;  /* the scanned bit planes of a residue byte, in every byte (0xffffffff: all; TableSize = 6 L: 0xfcfcfcfc);
                            0xffffffff also for a table cut inside a plane, whose per-word masks sit at trunc_off */
-  int32_t bm_unrolled;  /* 1: byte-major order with every RootIndex 0 and a complete first row (TableSize >= 16): no built-in
-                           kernel (runtime_only stays 1), but the unrolled kernels can be compiled for it at handle creation
-                           (mpc_jit.h, -DMPC_JIT_BM); gen_layout then says whether the table is truncated */
-  int32_t anyroot_unrolled; /* 1: plane-major order, complete first row, some RootIndex above 15: no built-in kernel (runtime_only
-                           stays 1), but the general-layout kernels can be compiled for it at handle creation with the roots as
-                           constants (mpc_jit.h, -DMPC_JIT_ANYROOT); gen_layout is 1 */
-  int32_t wshift_unrolled; /* 1: some WEIGHT module has more than two shift distances (like gather_unrolled: -DMPC_JIT_WSHIFT) */
-  int32_t gather_unrolled; /* 1: some DIFF / WEIGHT module has a BaseIndexTable that is not windowed: only a kernel compiled at
-                           creation with the tables as constants (mpc_jit.h, -DMPC_JIT_GATHER) evaluates it on the fast path;
-                           without one the handle falls back to the generic kernel */
-  int32_t planes_differ; /* 1: plane-major tables that stop after a whole number of bit planes, NOT the same number in every
-                           module (MpcFastModule::plane_mask): only a kernel compiled at creation evaluates it (mpc_jit.h,
-                           -DMPC_JIT_PLANES); without one the handle falls back to the generic kernel */
 };
 
 /* Device-side raw statistics (uint64 each):

@@ -11,7 +11,8 @@
 // with hipModuleLoadData and kept in the handle; a copy goes to a cache directory keyed by a hash of the sources, the
 // options and the compiler version, so that the next process skips the compilation (about 3 s).  Nothing here is a
 // fallback path of the product: when hiprtc, the sources or the compilation are not available, the configuration runs
-// the run-time module loop as before and a line on stderr says why.
+// what route_vpc (mpc_capi.hip) picks without them -- the run-time module loop, or the generic kernel for the layouts
+// that loop lacks (mpc::JIT_NO_LOOP) -- and a line on stderr says why.
 //
 //   MPC_JIT=0            never compile at run time
 //   MPC_JITC=PATH        the helper program (default: mpc_jitc next to the library; without one hiprtc is dlopen'ed here)
@@ -43,10 +44,10 @@
 #include <string>
 #include <vector>
 
+#include "mpc_config.h"
 #include "mpc_device.h"
 
 extern "C" size_t mpc_vpc_lane_ring_plan(const MpcVpcParams *P, unsigned *ring_cfg, int *wpb);
-extern "C" int mpc_vpc_lane_unrolled(const MpcVpcParams *P);
 
 namespace mpcjit {
 
@@ -61,7 +62,6 @@ inline int max_modules()
 }
 
 struct Kernels {
-  hipModule_t mod = nullptr;
   hipFunction_t stats = nullptr;    // statistics only
   hipFunction_t lines = nullptr;    // + per-line outputs
   bool from_cache = false;
@@ -77,8 +77,6 @@ struct Loaded {
 };
 inline std::mutex &loaded_mutex() { static std::mutex m; return m; }
 inline std::map<std::string, Loaded *> &loaded_modules() { static std::map<std::string, Loaded *> m; return m; }
-
-inline void unload(Kernels &k) { k = Kernels(); }
 
 // the sequence as the kernels' template arguments (lane-kernel kinds: MPC_FK_* | 8 / 16 for periodic tables)
 inline std::string kinds_of(const MpcVpcParams &P)
@@ -106,23 +104,12 @@ inline std::string gathers_of(const MpcVpcParams &P)
   return s;
 }
 
-inline std::string roots_of(const MpcVpcParams &P)
+inline std::string roots_of(const mpc::VpcPlan &plan)
 {
   std::string s;
-  for (int q = 0; q < P.n_pred; q++) s += (q ? ", " : "") + std::to_string(P.anyroot_unrolled ? P.fm[q].root : 0);
+  for (int q = 0; q < plan.params.n_pred; q++)
+    s += (q ? ", " : "") + std::to_string((plan.jit_needs & mpc::JIT_ANYROOT) ? plan.params.fm[q].root : 0);
   return s;
-}
-
-// a fast-path configuration whose sequence has no built-in instantiation but could have one
-inline bool eligible(const MpcVpcParams &P, bool fast)
-{
-  const char *env = std::getenv("MPC_JIT");
-  if (env && std::strcmp(env, "0") == 0) return false;
-  if (!fast || (P.runtime_only && !P.bm_unrolled && !P.anyroot_unrolled && !P.planes_differ && !P.gather_unrolled && !P.wshift_unrolled) || P.n_pred < 1 || P.n_pred > max_modules()) return false;
-  if (!(P.L == 32 || P.L == 64 || P.L == 128)) return false;
-  if (mpc_vpc_lane_unrolled(&P)) return false;            // built in (never the byte-major order)
-  unsigned ring_cfg = 0;
-  return mpc_vpc_lane_ring_plan(&P, &ring_cfg, nullptr) != 0;       // the rings fit beside the histogram (with some workgroup size)
 }
 
 namespace detail {
@@ -209,15 +196,16 @@ inline Rtc &rtc()
 }  // namespace detail
 
 // the translation unit handed to hiprtc: the lane kernel's device code and two kernels of the sequence
-// gtab: the HOST copy of the generic-path tables (VpcPlan::gtab: every module's BaseIndexTable at gm[q].off_base)
-inline std::string bases_of(const MpcVpcParams &P, const unsigned char *gtab)
+// (every module's BaseIndexTable: the host copy of the generic-path tables, VpcPlan::gtab at gm[q].off_base)
+inline std::string bases_of(const mpc::VpcPlan &plan)
 {
+  const MpcVpcParams &P = plan.params;
   std::string s;
   for (int q = 0; q < P.n_pred; q++) {
     s += q ? ", {" : "{";
     for (int i = 0; i < P.L; i++) {
-      const bool has = P.fm[q].gather && gtab && i != P.fm[q].root;
-      s += (i ? "," : "") + std::to_string(has ? (int)gtab[P.gm[q].off_base + i] : -1);
+      const bool has = P.fm[q].gather && i != P.fm[q].root;
+      s += (i ? "," : "") + std::to_string(has ? (int)plan.gtab[(size_t)(P.gm[q].off_base + i)] : -1);
     }
     s += "}";
   }
@@ -225,15 +213,16 @@ inline std::string bases_of(const MpcVpcParams &P, const unsigned char *gtab)
 }
 
 // every module's shift distance per byte (VpcPlan::gtab at gm[q].off_shift, clamped to +-8); 99: the predicted byte is 0
-inline std::string shifts_of(const MpcVpcParams &P, const unsigned char *gtab)
+inline std::string shifts_of(const mpc::VpcPlan &plan)
 {
+  const MpcVpcParams &P = plan.params;
   std::string s;
   for (int q = 0; q < P.n_pred; q++) {
     s += q ? ", {" : "{";
     for (int i = 0; i < P.L; i++) {
       int v = 99;
-      if (P.fm[q].wgen && gtab && i != P.fm[q].root) {
-        v = (int)(signed char)gtab[P.gm[q].off_shift + i];
+      if (P.fm[q].wgen && i != P.fm[q].root) {
+        v = (int)(signed char)plan.gtab[(size_t)(P.gm[q].off_shift + i)];
         if (v >= 8 || v <= -8) v = 99;
       }
       s += (i ? "," : "") + std::to_string(v);
@@ -243,24 +232,26 @@ inline std::string shifts_of(const MpcVpcParams &P, const unsigned char *gtab)
   return s;
 }
 
-inline std::string source_of(const MpcVpcParams &P, size_t smem_bytes, int testing, const unsigned char *gtab = nullptr)
+inline std::string source_of(const mpc::VpcPlan &plan, size_t smem_bytes, int testing)
 {
+  const MpcVpcParams &P = plan.params;
+  const unsigned need = plan.jit_needs;
   const int W = P.L / 4;
   int wpb = 0;
   (void)mpc_vpc_lane_ring_plan(&P, nullptr, &wpb);
   const std::string targs = std::to_string(W) + ", OUT_, " + (P.gen_layout ? "true" : "false") + ", " + kinds_of(P);
   std::ostringstream s;
   s << "#define MPC_LANE_JIT 1\n"
-    << "#define MPC_JIT_BM " << (P.bm_unrolled ? 1 : 0) << "\n"
-    << "#define MPC_JIT_ANYROOT " << (P.anyroot_unrolled ? 1 : 0) << "\n"
-    << "#define MPC_JIT_PLANES " << (P.planes_differ ? 1 : 0) << "\n"
-    << "#define MPC_JIT_WSHIFT " << (P.wshift_unrolled ? 1 : 0) << "\n"
+    << "#define MPC_JIT_BM " << ((need & mpc::JIT_BM) ? 1 : 0) << "\n"
+    << "#define MPC_JIT_ANYROOT " << ((need & mpc::JIT_ANYROOT) ? 1 : 0) << "\n"
+    << "#define MPC_JIT_PLANES " << ((need & mpc::JIT_PLANES) ? 1 : 0) << "\n"
+    << "#define MPC_JIT_WSHIFT " << ((need & mpc::JIT_WSHIFT) ? 1 : 0) << "\n"
     << "#define MPC_JIT_WGENS " << wgens_of(P) << "\n"
-    << "#define MPC_JIT_SHIFTS " << (P.wshift_unrolled ? shifts_of(P, gtab) : std::string("{0}")) << "\n"
-    << "#define MPC_JIT_GATHER " << (P.gather_unrolled ? 1 : 0) << "\n"
+    << "#define MPC_JIT_SHIFTS " << ((need & mpc::JIT_WSHIFT) ? shifts_of(plan) : std::string("{0}")) << "\n"
+    << "#define MPC_JIT_GATHER " << ((need & mpc::JIT_GATHER) ? 1 : 0) << "\n"
     << "#define MPC_JIT_GATHERS " << gathers_of(P) << "\n"
-    << "#define MPC_JIT_BASES " << (P.gather_unrolled ? bases_of(P, gtab) : std::string("{0}")) << "\n"
-    << "#define MPC_JIT_ROOTS " << roots_of(P) << "\n"
+    << "#define MPC_JIT_BASES " << ((need & mpc::JIT_GATHER) ? bases_of(plan) : std::string("{0}")) << "\n"
+    << "#define MPC_JIT_ROOTS " << roots_of(plan) << "\n"
     << "#define MPC_TESTING " << testing << "\n"
     << "#define " << (P.L <= 32 ? "MPC_LANE_WAVES_32 " : P.L <= 64 ? "MPC_LANE_WAVES " : "MPC_LANE_WAVES_128 ") << wpb << "      /* waves per workgroup of the LDS plan */\n"
     << "#include \"mpc_vpc_lane.hip\"\n"
@@ -386,10 +377,11 @@ inline bool compile(const std::string &source, const std::string &arch, const st
   return true;
 }
 
-// Compile (or take from the cache) and load the two kernels of P's sequence on the current device.
-// Returns false with a reason in `why`; the caller then runs the run-time module loop.
-inline bool build(const MpcVpcParams &P, int testing, Kernels &out, std::string &why, const unsigned char *gtab = nullptr)
+// Compile (or take from the cache) and load the two kernels of the plan's sequence on the current device.
+// Returns false with a reason in `why`; the caller then routes the configuration again (run-time loop or generic kernel).
+inline bool build(const mpc::VpcPlan &plan, int testing, Kernels &out, std::string &why)
 {
+  const MpcVpcParams &P = plan.params;
   unsigned ring_cfg = 0;
   const size_t smem = mpc_vpc_lane_ring_plan(&P, &ring_cfg, nullptr);
   if (smem == 0) { why = "the line rings do not fit the LDS beside the histogram"; return false; }
@@ -405,7 +397,7 @@ inline bool build(const MpcVpcParams &P, int testing, Kernels &out, std::string 
   if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { why = "no device"; return false; }
   const std::string arch = prop.gcnArchName;
   if (arch.compare(0, 6, "gfx950") != 0) { why = "device is " + arch + ", the kernels are written for gfx950"; return false; }
-  const std::string source = source_of(P, smem, testing, gtab);
+  const std::string source = source_of(plan, smem, testing);
 
   // ---- cache: keyed by everything the code object depends on ----
   // (the compiler's version enters through the HIP runtime's: they are installed together)
@@ -420,7 +412,6 @@ inline bool build(const MpcVpcParams &P, int testing, Kernels &out, std::string 
   {
     auto it = loaded_modules().find(mem_key);
     if (it != loaded_modules().end()) {        // this process has it loaded on this device already
-      out.mod = it->second->mod;
       out.stats = it->second->stats;
       out.lines = it->second->lines;
       out.from_cache = true;
@@ -439,7 +430,6 @@ inline bool build(const MpcVpcParams &P, int testing, Kernels &out, std::string 
       return e;
     }
     loaded_modules()[mem_key] = L;
-    out.mod = L->mod;
     out.stats = L->stats;
     out.lines = L->lines;
     return e;

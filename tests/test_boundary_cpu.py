@@ -50,7 +50,7 @@ def test_config_describe_matches_oracle_parse(mpc, configs, oracle):
         assert d["modules"][5]["shifts"][1:4] == [-1, 0, -1]
 
 
-def test_custom_encoding_bits_and_generic_classification(mpc, configs):
+def test_custom_encoding_bits_and_generic_classification(mpc, configs, monkeypatch):
     cfg = configs.probe_config(64, encoding_bits=[2, 1, 3, 4, 4, 5, 5])
     d = mpc.describe_config(cfg)
     assert d["enc_bits"] == [2, 1, 3, 4, 4, 5, 5] and d["hist_bins"] == 512 + 5 + 1
@@ -96,6 +96,27 @@ def test_custom_encoding_bits_and_generic_classification(mpc, configs):
     bm = {"TableSize": 512, "Rows": [i % 8 for i in range(512)], "Cols": [i // 8 for i in range(512)]}
     cfg = configs.make_config(64, [{"name": "AllZero"}, configs.diff_base(64, base, [0] * 64, 0, True, bm)])
     assert mpc.describe_config(cfg)["path"] == "generic"
+    # a weight table with more than two shift distances, different whole-plane table sizes per module: compiled at creation,
+    # else the generic kernel (the run-time loop has neither); together with the byte-major order / a root above 15: generic
+    prev4 = [max(i - 4, 0) for i in range(64)]
+    w4 = [[1.0, 0.5, 0.25, 2.0][i % 4] for i in range(64)]
+    pm = [{"TableSize": ts, "Rows": [i // 64 for i in range(ts)], "Cols": [i % 64 for i in range(ts)]} for ts in (6 * 64, 8 * 64)]
+    wshift = configs.make_config(64, [{"name": "AllZero"}, configs.weight_base(64, prev4, w4, 0, True)])
+    planes = configs.make_config(64, [{"name": "AllZero"}, configs.one_base(64, 0, True, pm[0]), configs.consecutive_base(64, 0, True, pm[1])])
+    for cfg, why in ((wshift, "WeightTable uses more than two shift distances, and run-time compilation is not available for it"),
+                     (planes, "scan tables of different sizes, and run-time compilation is not available for them")):
+        monkeypatch.delenv("MPC_JIT", raising=False)
+        d = mpc.describe_config(cfg)
+        assert d["path"] == "fast" and d["sequence"] == "unrolled" and d["compiled"] == "at creation", d
+        monkeypatch.setenv("MPC_JIT", "0")
+        d = mpc.describe_config(cfg)
+        assert d["path"] == "generic" and d["why_generic"] == why and d["sequence"] == d["compiled"] == "", d
+    monkeypatch.delenv("MPC_JIT", raising=False)
+    planes_root = configs.make_config(64, [{"name": "AllZero"}, configs.one_base(64, 20, True, pm[0]), configs.consecutive_base(64, 0, True, pm[1])])
+    d = mpc.describe_config(planes_root)
+    assert d["path"] == "generic" and d["why_generic"] == "scan tables of different sizes together with a RootIndex above 15", d
+    d = mpc.describe_config(configs.make_config(64, [{"name": "AllZero"}, configs.weight_base(64, prev4, w4, 0, True, bm)]))
+    assert d["path"] == "generic" and "WeightTable uses more than two shift distances, together with" in d["why_generic"], d
 
 
 def test_invalid_configs_are_error_codes(mpc, configs):
@@ -228,7 +249,7 @@ def test_short_scan_tables_pin_the_scan_order(mpc, configs):
     assert mpc.describe_config(configs.probe_config(L))["scan_order"] == "plane-major"
 
 
-def test_run_time_compilation_of_a_module_sequence_builds_for_gfx950(mpc, configs):
+def test_run_time_compilation_of_a_module_sequence_builds_for_gfx950(mpc, configs, monkeypatch):
     """A module sequence without a built-in unrolled instantiation is compiled with hiprtc when a handle is created
     (csrc/mpc_jit.h).  The compilation itself needs no device: the same source the library would hand to hiprtc on a GPU
     box is compiled here for gfx950 (nothing is loaded), at every line size, with and without the general layout."""
@@ -276,3 +297,9 @@ def test_run_time_compilation_of_a_module_sequence_builds_for_gfx950(mpc, config
     assert mpc.describe_config(cfg)["sequence"] == "run-time loop" and mpc.jit_compile_check(cfg) == 0
     cfg = configs.make_config(64, [az] + [configs.one_base(64, 0, bool(i & 1)) for i in range(13)])
     assert mpc.describe_config(cfg)["sequence"] == "run-time loop" and mpc.jit_compile_check(cfg) == 0
+    # MPC_JIT_MAX_MODULES: a sequence of 5 prediction modules is compiled by default, not with a limit of 4
+    cfg = configs.make_config(64, [az] + [configs.one_base(64, 0, bool(i & 1)) for i in range(5)])
+    assert mpc.describe_config(cfg)["compiled"] == "at creation"
+    monkeypatch.setenv("MPC_JIT_MAX_MODULES", "4")
+    d = mpc.describe_config(cfg)
+    assert d["path"] == "fast" and d["sequence"] == "run-time loop" and d["compiled"] == "" and mpc.jit_compile_check(cfg) == 0, d

@@ -74,13 +74,16 @@ int mpc_create_bdi(unsigned line_size, int device, mpc_handle **out);   /* any m
  * `new comp::FPC(lineSize)` (FPC.h:91-97): frequent pattern compression of the line's 32-bit
  * words (FPC.cpp:7-88).  Per-line output: size in bits; `selected` is written as 0.
  * One definition where the reference has undefined behaviour: a zero run ends at the end of
- * the line (FPC.cpp:26 reads past it).  Parity is unpinned (no fixture).     */
+ * the line (FPC.cpp:26 reads past it; with that read stopped at the line end, the reference
+ * gives exactly these numbers: tests/golden/ref_baseline_vectors.npz).                    */
 int mpc_create_fpc(unsigned line_size, int device, mpc_handle **out);
 /* `new comp::BPC(lineSize)` (BPC.h:93-99): bit-plane compression (BPC.cpp:20-185).  Per-line
  * output: size in bits (may exceed 8*L: the reference does not cap it); `selected` is 0.
  * Kept as in the source: the first word always costs 3+4 bits (`if (base = 0)`,
  * BPC.cpp:98).  Defined where the source is undefined: words are zero-extended to 64 bits
- * (BPC.cpp:42-44 copies 4 bytes into an uninitialised int64_t).  Parity is unpinned.       */
+ * (BPC.cpp:42-44 copies 4 bytes into an uninitialised int64_t; the upper half is the same for
+ * every word of a line and cancels in the deltas).  Pinned to the reference's own numbers by
+ * tests/golden/ref_baseline_vectors.npz.                                                    */
 int mpc_create_bpc(unsigned line_size, int device, mpc_handle **out);
 /* `new comp::SC2(lineSize, warmupCnt)` (SC2.h:100-107): a Huffman code over the line's 32-bit little-endian words
  * (SC2.cpp:270-333), with its table built once from a warm-up sample.  Lines 0 .. S-1 of the trace (S =

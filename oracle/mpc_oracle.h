@@ -134,12 +134,13 @@ uint64_t mpc_o_bdi_reduce_sign(uint64_t x);
 unsigned mpc_o_bdi_check(const uint8_t *line, int L, unsigned base_size, unsigned delta_size);
 
 /* FPC::CompressLine (FPC.cpp:7-88), frequent pattern compression of the line's L/4
- * little-endian 32-bit words.  PARITY UNPINNED: the reference ships no fixture for it and
- * FPC.cpp does not compile here without the un-vendored strutil.h, so this follows the
- * source text only.  One deliberate definition: the zero-run loop of the reference
- * (`while(dataConcat[i] == 0)`, FPC.cpp:26) reads past the end of the line when the run
- * reaches it (undefined behaviour, the result depends on heap contents); here a run ends
- * at the end of the line.                                                          */
+ * little-endian 32-bit words.  Pinned to the reference's own FPC.cpp by
+ * tests/golden/ref_baseline_vectors.npz (tests/test_baseline_ref.py).  One deliberate
+ * definition: the zero-run loop of the reference (`while(dataConcat[i] == 0)`, FPC.cpp:26)
+ * reads past the end of the line when the run reaches it (undefined behaviour, the result
+ * depends on heap contents); here a run ends at the end of the line.  The fixture shows
+ * that with the over-read stopped at the line end, the reference gives exactly these
+ * numbers.                                                                          */
 typedef struct {
   uint64_t lines;
   uint64_t original_bits;     /* 32 per word (FPC.h:31-38) */
@@ -152,14 +153,16 @@ unsigned mpc_o_fpc_line(const uint8_t *line, int L, mpc_o_fpc_stats *st);
 
 /* BPC::CompressLine (BPC.cpp:20-185), bit-plane compression: deltas of consecutive 32-bit
  * words, 33 delta bit planes (DBP), each XORed with the plane above (DBX), run-length /
- * pattern coded.  PARITY UNPINNED like FPC (no fixture; BPC.cpp needs the un-vendored
- * strutil.h to compile).  Two properties of the source are kept as they are:
+ * pattern coded.  Pinned to the reference's own BPC.cpp like FPC
+ * (tests/golden/ref_baseline_vectors.npz).  Two properties of the source are kept as they are:
  *   - encodeFirst (BPC.cpp:96-108) tests `if (base = 0)`, an assignment, so it always
  *     returns 3 + 4 = 7 bits;
  *   - pattern ZeroDBP (5) is never counted, a zero DBP is counted as Zero (2).
  * One definition where the source has undefined behaviour: a word is copied into the low
  * 4 bytes of an uninitialised int64_t (BPC.cpp:42-44); here the upper half is zero (the word
- * is zero-extended), which makes every delta a 33-bit two's complement number.          */
+ * is zero-extended), which makes every delta a 33-bit two's complement number.  The upper
+ * half is the same for every word of a line, so it cancels in the deltas: the fixture shows
+ * the reference's numbers equal to these.                                              */
 typedef struct {
   uint64_t lines;
   uint64_t original_bits;

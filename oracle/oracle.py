@@ -257,6 +257,8 @@ class VpcOracle:
 
 
 class BdiOracle:
+    """BDI::CompressLine restatement (reference BDI.cpp:6-218), pinned by tests/golden/ref_baseline_vectors.npz."""
+
     def __init__(self, line_size: int):
         if line_size % 8 or line_size < 8 or line_size > MAX_LINE:
             raise ValueError("BDI needs a line size that is a multiple of 8")
@@ -282,7 +284,7 @@ class BdiOracle:
 
 
 class FpcOracle:
-    """FPC::CompressLine restatement (reference FPC.cpp:7-88) -- PARITY UNPINNED, see mpc_oracle.h."""
+    """FPC::CompressLine restatement (reference FPC.cpp:7-88), pinned by tests/golden/ref_baseline_vectors.npz."""
 
     def __init__(self, line_size: int):
         if line_size % 4 or line_size < 4 or line_size > MAX_LINE:
@@ -307,7 +309,7 @@ class FpcOracle:
 
 
 class BpcOracle:
-    """BPC::CompressLine restatement (reference BPC.cpp:20-185) -- PARITY UNPINNED, see mpc_oracle.h."""
+    """BPC::CompressLine restatement (reference BPC.cpp:20-185), pinned by tests/golden/ref_baseline_vectors.npz."""
 
     def __init__(self, line_size: int):
         if line_size % 4 or line_size < 8 or line_size > 128:

@@ -21,6 +21,16 @@ def cli():
     return os.path.join(BIN, "compressor")
 
 
+# CSV headers of BDIResult / FPCResult / BPCResult::Print (reference BDI.h, FPC.h, BPC.h); their
+# equality with the reference's own output is checked in test_baseline_ref.py
+BDI_HEADER = ("Workload,Original Size,Compressed Size,Compression Ratio,Zeros,Repeated,B8D1,B8D2,B8D4,B4D1,B4D2,B2D1,"
+              "Uncompressed,\n")
+FPC_HEADER = ("Workload,Original Size,Compressed Size,Compression Ratio,Total Words,Prefix0,Prefix1,Prefix2,Prefix3,Prefix4,"
+              "Prefix5,Prefix6,Prefix7,\n")
+BPC_HEADER = ("Workload,Original Size,Compressed Size,Compression Ratio,Total Words,Pattern0,Pattern1,Pattern2,Pattern3,"
+              "Pattern4,Pattern5,Pattern6,\n")
+
+
 def run(cmd, cwd=BIN):
     return subprocess.run(cmd, cwd=cwd, capture_output=True, text=True, timeout=600)
 
@@ -174,8 +184,7 @@ def test_cli_bdi(cli, oracle, traces, tmp_path):
     o = oracle.BdiOracle(128)
     o.compress(data[:-1])
     assert r.stdout.strip().split("\n")[-1] == "comp.ratio: " + fmt_double(o.st.comp_ratio)
-    hdr = ("Workload,Original Size,Compressed Size,Compression Ratio,Zeros,Repeated,B8D1,B8D2,B8D4,B4D1,B4D2,B2D1,"
-           "Uncompressed,\n")
+    hdr = BDI_HEADER
     row = f"bench_ptr,{o.st.original_bits},{o.st.compressed_bits},{fmt_double(o.st.comp_ratio)}," + \
         "".join(f"{o.st.counts[i]}," for i in range(9)) + "\n"
     assert (tmp_path / "BDI_results.csv").read_text() == hdr + row
@@ -234,8 +243,7 @@ def test_cli_fpc(cli, oracle, traces, tmp_path):
     o = oracle.FpcOracle(64)
     o.compress(data[:-1])
     assert r.stdout.strip().split("\n")[-1] == "comp.ratio: " + fmt_double(o.st.comp_ratio)
-    hdr = ("Workload,Original Size,Compressed Size,Compression Ratio,Total Words,Prefix0,Prefix1,Prefix2,Prefix3,Prefix4,"
-           "Prefix5,Prefix6,Prefix7,\n")
+    hdr = FPC_HEADER
     row = f"bench_app,{o.st.original_bits},{o.st.compressed_bits},{fmt_double(o.st.comp_ratio)},{o.st.total_words}," + \
         "".join(f"{o.st.counts[i]}," for i in range(8)) + "\n"
     assert (tmp_path / "FPC_results.csv").read_text() == hdr + row
@@ -253,8 +261,7 @@ def test_cli_bpc(cli, oracle, traces, tmp_path):
     o = oracle.BpcOracle(128)
     o.compress(data[:-1])
     assert r.stdout.strip().split("\n")[-1] == "comp.ratio: " + fmt_double(o.st.comp_ratio)
-    hdr = ("Workload,Original Size,Compressed Size,Compression Ratio,Total Words,Pattern0,Pattern1,Pattern2,Pattern3,"
-           "Pattern4,Pattern5,Pattern6,\n")
+    hdr = BPC_HEADER
     row = f"bench_app,{o.st.original_bits},{o.st.compressed_bits},{fmt_double(o.st.comp_ratio)},{o.st.total_words}," + \
         "".join(f"{o.st.counts[i]}," for i in range(7)) + "\n"
     assert (tmp_path / "BPC_results.csv").read_text() == hdr + row

@@ -652,8 +652,8 @@ def test_baselines_any_line_size(mpc, oracle, traces, L):
 
 @pytest.mark.parametrize("L", [32, 64, 128])
 def test_fpc(mpc, oracle, traces, L):
-    """FPC baseline against the oracle's source-reading restatement (parity unpinned: the
-    reference has no fixture for it): every prefix, zero runs of every length incl. to the end of
+    """FPC baseline against the oracle's restatement (which tests/test_baseline_ref.py pins to the
+    reference's own FPC.cpp): every prefix, zero runs of every length incl. to the end of
     the line, sign-extension boundaries."""
     rng = np.random.default_rng(L)
     n = 6000
@@ -681,7 +681,7 @@ def test_fpc(mpc, oracle, traces, L):
 
 @pytest.mark.parametrize("L", [32, 64, 128])
 def test_bpc(mpc, oracle, traces, L):
-    """BPC baseline against the oracle's source-reading restatement (parity unpinned): ramps and
+    """BPC baseline against the oracle's restatement (pinned like FPC's): ramps and
     constant lines (zero runs, all-ones planes), sparse deltas (single / adjacent ones), wrap-around
     deltas (borrow plane), random and structured data."""
     rng = np.random.default_rng(L + 1)

@@ -392,15 +392,23 @@ def sc2_code_lengths(symbols, freqs) -> np.ndarray:
     return out
 
 
+def _ratio(original, compressed, lines) -> float:
+    if not lines:
+        return 0.0
+    return float(original) / float(compressed) if compressed else float("inf")
+
+
 def vpc_result_from_vector(v: np.ndarray, M: int, bins: int, L: int) -> Dict:
     K = M + 1
+    # VPC.h:49-60: (double)original / (double)compressed after every line -- inf once lines of 0 bits are all there are
+    # (a cluster whose id bits are 0: all-zero lines), 0 before the first line
     out = {"lines": int(v[0]), "original_bits": int(v[1]), "compressed_bits": int(v[2]),
-           "comp_ratio": (float(v[1]) / float(v[2])) if v[2] else 0.0, "clusters": {}}
+           "comp_ratio": _ratio(v[1], v[2], v[0]), "clusters": {}}
     for k in range(K):
         cnt, ob, cb, rl, sr, sr2 = (int(x) for x in v[3 + 6 * k: 3 + 6 * k + 6])
         out["clusters"][k - 1] = {
             "count": cnt, "original_bits": ob, "compressed_bits": cb,
-            "comp_ratio": (float(ob) / float(cb)) if cb else 0.0,
+            "comp_ratio": _ratio(ob, cb, cnt),
             "residue_lines": rl, "sum_r": sr, "sum_r2": sr2,
             # VPC.h:62-76: mean over lines of (sum over bytes / L)
             "mae": (float(sr) / float(L)) / float(rl) if rl else 0.0,

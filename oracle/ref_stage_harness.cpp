@@ -14,11 +14,12 @@
 // Those five include only each other's headers and the C++ standard library.
 // Every other file on the path (VPC.cpp, BDI.cpp, AllZeroModule.cpp,
 // AllWordSameModule.cpp, BitplaneModule.cpp) reaches <strutil.h> /
-// <json/json.h> through ../Compressor.h; those libraries are not in this image
-// and no stand-ins are written for them, so those files are NOT built.  The
-// one stage in the middle of the chain that cannot be built, the bit-plane
-// transpose (BitplaneModule.cpp:7-51), is done here by make_bitplane() into
-// the reference's own `Binary` container.
+// <json/json.h> through ../Compressor.h, so this library leaves them out and
+// does the bit-plane transpose (BitplaneModule.cpp:7-51) itself, in
+// make_bitplane(), into the reference's own `Binary` container.  Those files
+// are built, with stand-ins for the two headers, by the fixture generators
+// tests/golden/make_ref_baseline_vectors.py and make_ref_vpc_vectors.py; the
+// latter pins the whole VPC path end to end (tests/golden/ref_vpc_vectors.npz).
 //
 // The output library lives in oracle/_ref/ (git-ignored) and is only ever
 // loaded by tests/.

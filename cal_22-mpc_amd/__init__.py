@@ -102,6 +102,15 @@ def lib() -> C.CDLL:
             "mpc_npy_shape": ([C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
             "mpc_compress_gpgpusim_log": ([H, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
             "mpc_gpgpusim_log_line_size": ([C.c_char_p, C.POINTER(C.c_uint32)], C.c_int),
+            "mpc_group_create": ([C.POINTER(H), C.c_size_t, C.POINTER(H)], C.c_int),
+            "mpc_group_destroy": ([H], None),
+            "mpc_group_last_error": ([H], C.c_char_p),
+            "mpc_group_form": ([H], C.c_char_p),
+            "mpc_group_compress_batch": ([H, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int),
+            "mpc_group_compress_batch_device": ([H, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
+            "mpc_group_compress_npy": ([H, C.c_char_p, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)], C.c_int),
+            "mpc_group_compress_gpgpusim_log": ([H, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
+            "mpc_group_sync": ([H], C.c_int),
             "mpc_synth_fill": ([C.c_void_p, C.c_uint64, C.c_uint, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p], C.c_int),
             "mpc_read_bandwidth_probe": ([C.c_void_p, C.c_uint64, C.c_void_p], C.c_int),
         }
@@ -120,6 +129,8 @@ EXPORTED_SYMBOLS = [
     "mpc_stats_copy_raw_device", "mpc_stats_from_raw", "mpc_config_describe",
     "mpc_compress_npy", "mpc_npy_shape", "mpc_compress_gpgpusim_log", "mpc_gpgpusim_log_line_size",
     "mpc_synth_fill", "mpc_read_bandwidth_probe",
+    "mpc_group_create", "mpc_group_destroy", "mpc_group_last_error", "mpc_group_form", "mpc_group_compress_batch",
+    "mpc_group_compress_batch_device", "mpc_group_compress_npy", "mpc_group_compress_gpgpusim_log", "mpc_group_sync",
 ]
 # The SC2 entry points of include/mpc_hip.h.  Kept apart from EXPORTED_SYMBOLS, which lists the names of the
 # header's lowercase-letter form (mpc_[a-z_]+) only; every one of both lists is exported by libmpc_hip.so.
@@ -371,6 +382,83 @@ class SC2(_Evaluator):
         n = C.c_size_t()
         self._check(lib().mpc_sc2_table(self._h, sym.ctypes.data, lens.ctypes.data, 1024, C.byref(n)))
         return sym[:n.value].copy(), lens[:n.value].copy()
+
+
+class EvaluatorSet:
+    """A group of evaluators of one line size on one device that are fed together (``mpc_group``): the trace is
+    staged once per chunk and every member sees every line as if it had been called alone.  The members keep their
+    own statistics: read them with each member's ``result()`` / ``stats_vector()`` as usual.  The set borrows its
+    members; close it before them (it keeps them alive until then)."""
+
+    def __init__(self, evaluators):
+        self.members = list(evaluators)
+        self._g = C.c_void_p()
+        if any(not isinstance(e, _Evaluator) or not e._h for e in self.members):
+            raise ValueError("EvaluatorSet takes open VPC / BDI / FPC / BPC / SC2 evaluators")
+        arr = (C.c_void_p * max(1, len(self.members)))(*[e._h.value for e in self.members])
+        rc = lib().mpc_group_create(arr, len(self.members), C.byref(self._g))
+        if rc != 0:
+            raise MpcError(rc, (lib().mpc_group_last_error(None) or b"").decode())
+        self.line_size = self.members[0].line_size
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise MpcError(rc, (lib().mpc_group_last_error(self._g) or b"").decode())
+
+    @property
+    def form(self) -> str:
+        """Which members share a kernel launch and which run their own, e.g.
+        ``"VPC: unrolled; BDI+FPC+BPC: one kernel; SC2: own kernel"``."""
+        return (lib().mpc_group_form(self._g) or b"").decode()
+
+    def close(self) -> None:
+        if self._g:
+            lib().mpc_group_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _pointers(self, values):
+        return (C.c_void_p * len(self.members))(*values)
+
+    def compress_lines(self, lines: np.ndarray, want_sizes: bool = True, want_selected: bool = True):
+        """Host buffer [n, L] uint8 -> one ``(size_bits, selected)`` pair per member, in member order."""
+        lines = np.ascontiguousarray(lines, dtype=np.uint8)
+        if lines.ndim != 2 or lines.shape[1] != self.line_size:
+            raise ValueError(f"expected [n, {self.line_size}] uint8")
+        n = lines.shape[0]
+        sizes = [np.empty(n, dtype=np.uint16) if want_sizes else None for _ in self.members]
+        sel = [np.empty(n, dtype=np.int8) if want_selected else None for _ in self.members]
+        self._check(lib().mpc_group_compress_batch(
+            self._g, lines.ctypes.data, n,
+            self._pointers([a.ctypes.data for a in sizes]) if want_sizes else None,
+            self._pointers([a.ctypes.data for a in sel]) if want_selected else None))
+        return list(zip(sizes, sel))
+
+    def compress_device(self, d_lines: int, n_lines: int, d_sizes=None, d_selected=None, stream: int = 0) -> None:
+        """Device-resident lines; ``d_sizes`` / ``d_selected``: one raw device pointer (or 0 / None) per member."""
+        self._check(lib().mpc_group_compress_batch_device(
+            self._g, d_lines, n_lines,
+            self._pointers([p or None for p in d_sizes]) if d_sizes is not None else None,
+            self._pointers([p or None for p in d_selected]) if d_selected is not None else None, stream or None))
+
+    def compress_npy(self, path: str, first_row: int = 0, n_rows: int = (1 << 62), skip_last_row: bool = True) -> int:
+        done = C.c_uint64()
+        self._check(lib().mpc_group_compress_npy(self._g, path.encode(), first_row, n_rows,
+                                                 1 if skip_last_row else 0, C.byref(done)))
+        return int(done.value)
+
+    def compress_gpgpusim_log(self, path: str):
+        req, done = C.c_uint64(), C.c_uint64()
+        self._check(lib().mpc_group_compress_gpgpusim_log(self._g, path.encode(), C.byref(req), C.byref(done)))
+        return int(req.value), int(done.value)
+
+    def sync(self) -> None:
+        self._check(lib().mpc_group_sync(self._g))
 
 
 def sc2_sampling_lines(num_lines: int) -> int:

@@ -43,7 +43,7 @@ def _sources(d: str):
 def build_lib(force: bool = False, verbose: bool = False, test: bool = False) -> str:
     """libmpc_hip.so (test=True: libmpc_hip_test.so, the same sources with -DMPC_TESTING=1).  The translation units
     are compiled in parallel: the lane kernel file once per line size (-DMPC_LANE_W=8/16/32) plus its dispatcher
-    (-DMPC_LANE_W=0), the other kernels, the C ABI; then linked."""
+    (-DMPC_LANE_W=0), the other kernels (and once more for the group's shared kernel alone), the C ABI; then linked."""
     LIB = TEST_LIB if test else globals()["LIB"]
     deps = _sources(CSRC) + [os.path.join(ROOT, "include", "mpc_hip.h")]
     if not force and _newer(LIB, deps):
@@ -52,7 +52,9 @@ def build_lib(force: bool = False, verbose: bool = False, test: bool = False) ->
     os.makedirs(objdir, exist_ok=True)
     lane = os.path.join(CSRC, "mpc_vpc_lane.hip")
     units = [(lane, f"lane_w{w}.o", [f"-DMPC_LANE_W={w}"]) for w in (16, 32, 8, 0)]
-    units += [(os.path.join(CSRC, "mpc_kernels.hip"), "kernels.o", []), (os.path.join(CSRC, "mpc_sc2.hip"), "sc2.o", []),
+    units += [(os.path.join(CSRC, "mpc_kernels.hip"), "kernels.o", []),
+              (os.path.join(CSRC, "mpc_kernels.hip"), "baselines.o", ["-DMPC_BASELINES_UNIT=1"]),      # the group's shared kernel
+              (os.path.join(CSRC, "mpc_sc2.hip"), "sc2.o", []),
               (os.path.join(CSRC, "mpc_capi.hip"), "capi.o", [])]
     tflag = ["-DMPC_TESTING=1"] if test else []
     procs = []

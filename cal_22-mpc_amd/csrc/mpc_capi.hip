@@ -40,6 +40,7 @@ hipError_t mpc_launch_vpc_generic(const void *, u64, const MpcVpcParams *, uint1
 hipError_t mpc_launch_bdi(const void *, u64, int, uint16_t *, int8_t *, u64 *, int, hipStream_t);
 hipError_t mpc_launch_fpc(const void *, u64, int, uint16_t *, int8_t *, u64 *, int, hipStream_t);
 hipError_t mpc_launch_bpc(const void *, u64, int, uint16_t *, int8_t *, u64 *, int, hipStream_t);
+hipError_t mpc_launch_baselines(const void *, u64, int, const MpcBaselinesArgs *, int, hipStream_t);
 hipError_t mpc_launch_synth(void *, u64, unsigned, int, u64, u64, const uint32_t *, hipStream_t);
 hipError_t mpc_launch_read_probe(const void *, u64, uint32_t *, int, hipStream_t);
 hipError_t mpc_launch_vpc_lane(const void *, u64, const MpcVpcParams *, uint16_t *, int8_t *, u64 *, int, hipStream_t);
@@ -118,7 +119,38 @@ struct mpc_handle {
     std::vector<uint32_t> symbols;   // the table, ascending symbol order
     std::vector<uint16_t> lengths;
   } sc2;
+  std::vector<hipStream_t> group_streams;   // the slot streams of the groups this handle is a member of (sc2_build waits for them)
   std::string error;
+};
+
+namespace {
+
+// a group's staging slot: the chunk is copied once, every member's launch follows on the slot's stream
+struct GroupSlot {
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;
+  uint8_t *h_in = nullptr;       // pinned
+  uint8_t *d_in = nullptr;
+  // per member, allocated when a call first asks for that member's per-line output
+  std::vector<uint16_t *> d_sizes, h_sizes, user_sizes;
+  std::vector<int8_t *> d_sel, h_sel, user_sel;
+  u64 pending_lines = 0;
+  bool busy = false;
+};
+
+}  // namespace
+
+struct mpc_group {
+  std::vector<mpc_handle *> m;   // borrowed, in the caller's order
+  int device = 0;
+  int L = 0;
+  int shared[3] = {-1, -1, -1};  // member index of the BDI, FPC, BPC handle that baselines_kernel evaluates (all -1: no shared launch)
+  int first_shared = -1;         // ... the first of them in member order: where the shared launch is enqueued
+  GroupSlot slots[2];            // the streams and events exist from creation, the buffers from the first staged call
+  bool slots_ready = false;
+  size_t stage_lines = 0;
+  uint8_t *mini = nullptr;       // [kMiniLines * L] lines | per member [kMiniLines] uint16 | per member [kMiniLines] int8
+  std::string form, error;
 };
 
 namespace {
@@ -367,7 +399,7 @@ int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t 
 }
 
 // SC2: the code table from the warm-up counts.  The one blocking point of an SC2 handle: every stream that may still
-// run a warm-up count (the call's, the handle's, both staging slots') is synchronised, the 1024 largest slots are
+// run a warm-up count (the call's, the handle's, both staging slots', the slots of the groups it belongs to) is synchronised, the 1024 largest slots are
 // selected on the device (radix select, 8 bits per pass from the top), only those <= 1024 (symbol, count) pairs come
 // to the host, the heap is replayed there (mpc_sc2.h) and the bucket image goes back to the device.
 int sc2_build(mpc_handle *h, hipStream_t s)
@@ -376,6 +408,8 @@ int sc2_build(mpc_handle *h, hipStream_t s)
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (int i = 0; i < 2; i++)
     if (h->slots[i].stream) HIPCHK(h, hipStreamSynchronize(h->slots[i].stream));
+  // a member of a group: the warm-up chunk may be counting on the group's other slot
+  for (hipStream_t gs : h->group_streams) HIPCHK(h, hipStreamSynchronize(gs));
   const u64 n_slots = h->sc2.hash_mask + 1;
   const int grid = (int)std::min<u64>((n_slots + 255) / 256, (u64)h->num_cus * 8);
   uint32_t *d_work = nullptr;           // [256] histogram | [1] count | pad | [1024] uint64 slots
@@ -687,6 +721,359 @@ int parse_npy_header(FILE *f, u64 *rows, u64 *cols, u64 *data_off, std::string &
   *data_off = off + hlen;
   return MPC_OK;
 }
+
+// ---- streaming a trace file through the staging slots.  The file walkers below are written once, against a
+// "feed": who owns the two slots and what a submitted chunk is launched on -- one handle, or a group of them.
+struct HandleFeed {
+  mpc_handle *h;
+  int L() const { return h->L; }
+  int device() const { return h->device; }
+  int fail(int code, const std::string &msg) const { return set_err(h, code, msg); }
+  int ensure() const { return ensure_slots(h); }
+  u64 stage_lines() const { return (u64)h->stage_lines; }
+  uint8_t *buffer(int which) const { return h->slots[which].h_in; }
+  int retire(int which) const { return ::retire(h, h->slots[which]); }
+  int submit(int which, u64 lines) const { return ::submit(h, h->slots[which], lines, nullptr, nullptr); }
+  int finish() const { return sync_all(h); }
+  void abandon() const { abandon_slots(h); }
+};
+
+template <class Feed>
+int feed_npy(Feed fd_, const char *path, uint64_t first_row, uint64_t n_rows, int skip_last_row, uint64_t *rows_done)
+{
+  if (rows_done) *rows_done = 0;
+  FILE *f = fopen(path, "rb");
+  if (!f) return fd_.fail(MPC_E_NOENT, std::string("cannot open ") + path);
+  u64 rows, cols, off;
+  std::string err;
+  int rc = parse_npy_header(f, &rows, &cols, &off, err);
+  if (rc != MPC_OK) { fclose(f); return fd_.fail(rc, err); }
+  if (cols != (u64)fd_.L()) {
+    fclose(f);
+    return fd_.fail(MPC_E_INVAL, "trace line size " + std::to_string(cols) + " differs from the evaluator's " + std::to_string(fd_.L()));
+  }
+  // the reference driver drops the final row (LoaderNPY.cpp:28-32 + main.cpp:240)
+  u64 usable = (skip_last_row && rows > 0) ? rows - 1 : rows;
+  u64 begin = first_row < usable ? first_row : usable;
+  u64 end = (n_rows > usable - begin) ? usable : begin + n_rows;
+  if (hipSetDevice(fd_.device()) != hipSuccess) { fclose(f); return fd_.fail(MPC_E_HIP, "hipSetDevice failed"); }
+  rc = fd_.ensure();
+  if (rc != MPC_OK) { fclose(f); return rc; }
+  const int fd = fileno(f);
+  u64 done = begin;
+  int which = 0;
+  while (done < end) {
+    rc = fd_.retire(which);
+    if (rc != MPC_OK) break;
+    const u64 take = (end - done) < fd_.stage_lines() ? (end - done) : fd_.stage_lines();
+    if (!parallel_pread(fd, fd_.buffer(which), (size_t)(take * cols), off + done * cols)) { rc = fd_.fail(MPC_E_PARSE, "short read: .npy file is truncated"); break; }
+    rc = fd_.submit(which, take);
+    if (rc != MPC_OK) break;
+    done += take;
+    which ^= 1;
+  }
+  fclose(f);
+  if (rc == MPC_OK) rc = fd_.finish();
+  if (rc != MPC_OK) fd_.abandon();
+  if (rc == MPC_OK && rows_done) *rows_done = end - begin;
+  return rc;
+}
+
+constexpr int kLogKeys = 17, kLogRecordHeader = 62;
+
+template <class Feed>
+int feed_gpgpusim_log(Feed fd_, const char *log_path, uint64_t *requests_read, uint64_t *lines_done)
+{
+  if (requests_read) *requests_read = 0;
+  if (lines_done) *lines_done = 0;
+  // the file is mapped and walked in memory (per-request stdio calls cap the rate at ~35 M requests/s)
+  const int fd = open(log_path, O_RDONLY);
+  if (fd < 0) return fd_.fail(MPC_E_NOENT, std::string("Failed to open a file. Check the path of the file: ") + log_path);
+  struct stat st;
+  if (fstat(fd, &st) != 0) { close(fd); return fd_.fail(MPC_E_NOENT, std::string("cannot stat ") + log_path); }
+  const u64 size = (u64)st.st_size;
+  constexpr u64 kFileHeader = 1 + 7 * kLogKeys;
+  const unsigned char *base = nullptr;
+  if (size > 0) {
+    void *m = mmap(nullptr, (size_t)size, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (m == MAP_FAILED) { close(fd); return fd_.fail(MPC_E_NOMEM, std::string("cannot map ") + log_path); }
+    base = static_cast<const unsigned char *>(m);
+    (void)madvise(m, (size_t)size, MADV_SEQUENTIAL);
+  }
+  close(fd);
+  auto unmap = [&]() { if (base) munmap(const_cast<unsigned char *>(base), (size_t)size); };
+  if (size < kFileHeader || base[0] != kLogKeys) {
+    unmap();
+    return fd_.fail(MPC_E_PARSE, "The header of the GPGPU-sim trace file is not valid.");
+  }
+  if (hipSetDevice(fd_.device()) != hipSuccess) { unmap(); return fd_.fail(MPC_E_HIP, "hipSetDevice failed"); }
+  int rc = fd_.ensure();
+  if (rc != MPC_OK) { unmap(); return rc; }
+  const u64 L = (u64)fd_.L();
+  u64 requests = 0, lines = 0, fill = 0, pos = kFileHeader;
+  bool first = true;
+  int which = 0;
+  rc = fd_.retire(which);
+  while (rc == MPC_OK && pos + kLogRecordHeader <= size) {
+    uint32_t req_type, req_size;
+    std::memcpy(&req_type, base + pos + 38, 4);
+    std::memcpy(&req_size, base + pos + 58, 4);
+    if (first && req_size != L) {
+      rc = fd_.fail(MPC_E_INVAL, "trace line size " + std::to_string(req_size) + " differs from the evaluator's " + std::to_string(L));
+      break;
+    }
+    first = false;
+    const u64 next = pos + kLogRecordHeader + (u64)req_size;
+    if (next > size) break;                                      // incomplete trailing request
+    if (req_type == 0u || req_type == 4u) {                      // GLOBAL_ACC_R, GLOBAL_ACC_W
+      if (req_size != L) {
+        rc = fd_.fail(MPC_E_INVAL, "the GPGPU-sim trace mixes request sizes (" + std::to_string(req_size) + " after " + std::to_string(L) + " bytes)");
+        break;
+      }
+      std::memcpy(fd_.buffer(which) + fill * L, base + pos + kLogRecordHeader, (size_t)L);
+      fill++;
+    }
+    pos = next;
+    requests++;
+    if (fill == fd_.stage_lines()) {
+      rc = fd_.submit(which, fill);
+      if (rc != MPC_OK) break;
+      lines += fill;
+      fill = 0;
+      which ^= 1;
+      rc = fd_.retire(which);
+    }
+  }
+  if (rc == MPC_OK && fill) {
+    rc = fd_.submit(which, fill);
+    if (rc == MPC_OK) lines += fill;
+  }
+  if (rc == MPC_OK) rc = fd_.finish();
+  if (rc != MPC_OK) fd_.abandon();
+  unmap();
+  if (rc == MPC_OK) {
+    if (requests_read) *requests_read = requests;
+    if (lines_done) *lines_done = lines;
+  }
+  return rc;
+}
+
+// ---------------------------------------------------------------------------
+// groups: several handles of one line size on one device, fed together
+// ---------------------------------------------------------------------------
+int group_err(mpc_group *g, int code, const std::string &msg)
+{
+  if (g) g->error = msg; else g_create_error = msg;
+  return code;
+}
+
+#define GHIPCHK(g, call)                                                                        \
+  do {                                                                                          \
+    hipError_t e_ = (call);                                                                     \
+    if (e_ != hipSuccess)                                                                       \
+      return group_err((g), MPC_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));      \
+  } while (0)
+
+const char *algorithm_name(int algorithm)
+{
+  static const char *const name[] = {"VPC", "BDI", "FPC", "BPC", "SC2"};
+  return name[algorithm];
+}
+
+// Which members share baselines_kernel: the first BDI, FPC and BPC handle of the group when the line size has an
+// instantiation and at least two of the three are there; every other member launches its own kernel.
+void group_route(mpc_group *g)
+{
+  int found[3] = {-1, -1, -1}, n = 0;
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const int a = g->m[i]->algorithm;
+    if (a >= 1 && a <= 3 && found[a - 1] < 0) {
+      found[a - 1] = (int)i;
+      n++;
+    }
+  }
+  if (n >= 2 && (g->L == 32 || g->L == 64 || g->L == 128)) {
+    for (int k = 0; k < 3; k++) {
+      g->shared[k] = found[k];
+      if (found[k] >= 0 && (g->first_shared < 0 || found[k] < g->first_shared)) g->first_shared = found[k];
+    }
+  }
+  auto is_shared = [&](int i) { return i == g->shared[0] || i == g->shared[1] || i == g->shared[2]; };
+  std::string form;
+  for (int i = 0; i < (int)g->m.size(); i++) {
+    const mpc_handle *h = g->m[(size_t)i];
+    std::string part;
+    if (is_shared(i)) {
+      if (i != g->first_shared) continue;
+      for (int j = i; j < (int)g->m.size(); j++)
+        if (is_shared(j)) part += (part.empty() ? "" : "+") + std::string(algorithm_name(g->m[(size_t)j]->algorithm));
+      part += ": one kernel";
+    } else {
+      part = std::string(algorithm_name(h->algorithm)) + ": " + (h->algorithm == 0 ? mpc_kernel_form(h) : "own kernel");
+    }
+    form += (form.empty() ? "" : "; ") + part;
+  }
+  g->form = form;
+}
+
+// every member over the same device-resident lines, in member order on one stream; d_sizes / d_sel: arrays of one
+// pointer per member (the array or any entry may be null)
+int group_launch(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, hipStream_t s)
+{
+  if (n == 0) return MPC_OK;
+  for (int i = 0; i < (int)g->m.size(); i++) {
+    mpc_handle *h = g->m[(size_t)i];
+    const bool in_shared = i == g->shared[0] || i == g->shared[1] || i == g->shared[2];
+    if (in_shared) {
+      if (i != g->first_shared) continue;
+      MpcBaselinesArgs A{};
+      MpcBaselineOut *out[3] = {&A.bdi, &A.fpc, &A.bpc};
+      for (int k = 0; k < 3; k++) {
+        const int j = g->shared[k];
+        if (j < 0) continue;
+        out[k]->sizes = d_sizes ? d_sizes[j] : nullptr;
+        out[k]->sel = d_sel ? d_sel[j] : nullptr;
+        out[k]->raw = g->m[(size_t)j]->d_raw;
+      }
+      const hipError_t e = mpc_launch_baselines(d_lines, n, g->L, &A, grid_for(h, n, 256, kWgPerCu), s);
+      if (e != hipSuccess) return group_err(g, MPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+      continue;
+    }
+    const int rc = launch(h, d_lines, n, d_sizes ? d_sizes[i] : nullptr, d_sel ? d_sel[i] : nullptr, s);
+    if (rc != MPC_OK) return group_err(g, rc, "member " + std::to_string(i) + " (" + algorithm_name(h->algorithm) + "): " + h->error);
+  }
+  return MPC_OK;
+}
+
+int group_ensure_slots(mpc_group *g)
+{
+  if (g->slots_ready) return MPC_OK;
+  g->stage_lines = kStageBytes / (size_t)g->L;
+  for (int i = 0; i < 2; i++) {
+    GroupSlot &s = g->slots[i];
+    if (!s.h_in) GHIPCHK(g, hipHostMalloc((void **)&s.h_in, kStageBytes, hipHostMallocDefault));
+    if (!s.d_in) GHIPCHK(g, hipMalloc((void **)&s.d_in, kStageBytes));
+  }
+  g->slots_ready = true;
+  return MPC_OK;
+}
+
+// the per-line output buffers of member i in a slot, when a call asks for them for the first time
+int group_ensure_outputs(mpc_group *g, GroupSlot &s, size_t i, bool sizes, bool sel)
+{
+  if (sizes && !s.d_sizes[i]) {
+    GHIPCHK(g, hipMalloc((void **)&s.d_sizes[i], g->stage_lines * sizeof(uint16_t)));
+    GHIPCHK(g, hipHostMalloc((void **)&s.h_sizes[i], g->stage_lines * sizeof(uint16_t), hipHostMallocDefault));
+  }
+  if (sel && !s.d_sel[i]) {
+    GHIPCHK(g, hipMalloc((void **)&s.d_sel[i], g->stage_lines));
+    GHIPCHK(g, hipHostMalloc((void **)&s.h_sel[i], g->stage_lines, hipHostMallocDefault));
+  }
+  return MPC_OK;
+}
+
+int group_retire(mpc_group *g, GroupSlot &s)
+{
+  if (!s.busy) return MPC_OK;
+  GHIPCHK(g, hipEventSynchronize(s.done));
+  for (size_t i = 0; i < g->m.size(); i++) {
+    if (s.user_sizes[i]) std::memcpy(s.user_sizes[i], s.h_sizes[i], s.pending_lines * sizeof(uint16_t));
+    if (s.user_sel[i]) std::memcpy(s.user_sel[i], s.h_sel[i], s.pending_lines);
+  }
+  s.busy = false;
+  return MPC_OK;
+}
+
+// submit the chunk already sitting in s.h_in: one copy, then every member's launch on the slot's stream.
+// sizes / sel: the callers' arrays of per-member pointers (or null), `first` the chunk's first line in them.
+int group_submit(mpc_group *g, GroupSlot &s, u64 lines, uint16_t *const *sizes, int8_t *const *sel, u64 first)
+{
+  const size_t n = g->m.size();
+  std::vector<uint16_t *> ds(n, nullptr);
+  std::vector<int8_t *> dl(n, nullptr);
+  for (size_t i = 0; i < n; i++) {
+    s.user_sizes[i] = (sizes && sizes[i]) ? sizes[i] + first : nullptr;
+    s.user_sel[i] = (sel && sel[i]) ? sel[i] + first : nullptr;
+    const int rc = group_ensure_outputs(g, s, i, s.user_sizes[i] != nullptr, s.user_sel[i] != nullptr);
+    if (rc != MPC_OK) return rc;
+    if (s.user_sizes[i]) ds[i] = s.d_sizes[i];
+    if (s.user_sel[i]) dl[i] = s.d_sel[i];
+  }
+  GHIPCHK(g, hipMemcpyAsync(s.d_in, s.h_in, lines * (u64)g->L, hipMemcpyHostToDevice, s.stream));
+  const int rc = group_launch(g, s.d_in, lines, ds.data(), dl.data(), s.stream);
+  if (rc != MPC_OK) return rc;
+  for (size_t i = 0; i < n; i++) {
+    if (ds[i]) GHIPCHK(g, hipMemcpyAsync(s.h_sizes[i], ds[i], lines * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
+    if (dl[i]) GHIPCHK(g, hipMemcpyAsync(s.h_sel[i], dl[i], lines, hipMemcpyDeviceToHost, s.stream));
+  }
+  GHIPCHK(g, hipEventRecord(s.done, s.stream));
+  s.pending_lines = lines;
+  s.busy = true;
+  return MPC_OK;
+}
+
+// after an error: nothing of the failed call may be delivered later (abandon_slots)
+void group_abandon(mpc_group *g)
+{
+  for (int i = 0; i < 2; i++) {
+    GroupSlot &s = g->slots[i];
+    if (s.stream) (void)hipStreamSynchronize(s.stream);
+    s.busy = false;
+    s.pending_lines = 0;
+    std::fill(s.user_sizes.begin(), s.user_sizes.end(), nullptr);
+    std::fill(s.user_sel.begin(), s.user_sel.end(), nullptr);
+  }
+}
+
+int group_finish(mpc_group *g)
+{
+  for (int i = 0; i < 2; i++) {
+    const int rc = group_retire(g, g->slots[i]);
+    if (rc != MPC_OK) return rc;
+  }
+  for (int i = 0; i < 2; i++) GHIPCHK(g, hipStreamSynchronize(g->slots[i].stream));
+  return MPC_OK;
+}
+
+// n <= kMiniLines lines, evaluated in place from pinned host memory: one launch per member or per shared launch on the
+// first slot's stream (idle: every group call ends synchronised), one synchronisation
+int group_small(mpc_group *g, const uint8_t *lines, u64 n, uint16_t *const *sizes, int8_t *const *sel)
+{
+  const size_t nm = g->m.size();
+  if (!g->mini) GHIPCHK(g, hipHostMalloc((void **)&g->mini, kMiniLines * ((size_t)g->L + nm * (sizeof(uint16_t) + 1)), hipHostMallocDefault));
+  uint16_t *out_sizes = reinterpret_cast<uint16_t *>(g->mini + kMiniLines * (size_t)g->L);
+  int8_t *out_sel = reinterpret_cast<int8_t *>(out_sizes + nm * kMiniLines);
+  std::vector<uint16_t *> ds(nm, nullptr);
+  std::vector<int8_t *> dl(nm, nullptr);
+  for (size_t i = 0; i < nm; i++) {
+    if (sizes && sizes[i]) ds[i] = out_sizes + i * kMiniLines;
+    if (sel && sel[i]) dl[i] = out_sel + i * kMiniLines;
+  }
+  std::memcpy(g->mini, lines, (size_t)(n * (u64)g->L));
+  hipStream_t s = g->slots[0].stream;
+  const int rc = group_launch(g, g->mini, n, ds.data(), dl.data(), s);
+  if (rc != MPC_OK) { (void)hipStreamSynchronize(s); return rc; }
+  GHIPCHK(g, hipStreamSynchronize(s));
+  for (size_t i = 0; i < nm; i++) {
+    if (ds[i]) std::memcpy(sizes[i], ds[i], (size_t)n * sizeof(uint16_t));
+    if (dl[i]) std::memcpy(sel[i], dl[i], (size_t)n);
+  }
+  return MPC_OK;
+}
+
+struct GroupFeed {
+  mpc_group *g;
+  int L() const { return g->L; }
+  int device() const { return g->device; }
+  int fail(int code, const std::string &msg) const { return group_err(g, code, msg); }
+  int ensure() const { return group_ensure_slots(g); }
+  u64 stage_lines() const { return (u64)g->stage_lines; }
+  uint8_t *buffer(int which) const { return g->slots[which].h_in; }
+  int retire(int which) const { return group_retire(g, g->slots[which]); }
+  int submit(int which, u64 lines) const { return group_submit(g, g->slots[which], lines, nullptr, nullptr, 0); }
+  int finish() const { return group_finish(g); }
+  void abandon() const { group_abandon(g); }
+};
 
 uint32_t *g_sine_dev[16] = {nullptr};   // per device float32 sine period for mpc_synth_fill
 
@@ -1013,48 +1400,10 @@ int mpc_compress_npy(mpc_handle *h, const char *path, uint64_t first_row, uint64
                      uint64_t *rows_done)
 {
   if (!h || !path) return MPC_E_INVAL;
-  if (rows_done) *rows_done = 0;
-  FILE *f = fopen(path, "rb");
-  if (!f) return set_err(h, MPC_E_NOENT, std::string("cannot open ") + path);
-  u64 rows, cols, off;
-  std::string err;
-  int rc = parse_npy_header(f, &rows, &cols, &off, err);
-  if (rc != MPC_OK) { fclose(f); return set_err(h, rc, err); }
-  if (cols != (u64)h->L) {
-    fclose(f);
-    return set_err(h, MPC_E_INVAL, "trace line size " + std::to_string(cols) + " differs from the evaluator's " + std::to_string(h->L));
-  }
-  // the reference driver drops the final row (LoaderNPY.cpp:28-32 + main.cpp:240)
-  u64 usable = (skip_last_row && rows > 0) ? rows - 1 : rows;
-  u64 begin = first_row < usable ? first_row : usable;
-  u64 end = (n_rows > usable - begin) ? usable : begin + n_rows;
-  if (hipSetDevice(h->device) != hipSuccess) { fclose(f); return set_err(h, MPC_E_HIP, "hipSetDevice failed"); }
-  rc = ensure_slots(h);
-  if (rc != MPC_OK) { fclose(f); return rc; }
-  const int fd = fileno(f);
-  u64 done = begin;
-  int which = 0;
-  while (done < end) {
-    Slot &s = h->slots[which];
-    rc = retire(h, s);
-    if (rc != MPC_OK) break;
-    const u64 take = (end - done) < (u64)h->stage_lines ? (end - done) : (u64)h->stage_lines;
-    if (!parallel_pread(fd, s.h_in, (size_t)(take * cols), off + done * cols)) { rc = set_err(h, MPC_E_PARSE, "short read: .npy file is truncated"); break; }
-    rc = submit(h, s, take, nullptr, nullptr);
-    if (rc != MPC_OK) break;
-    done += take;
-    which ^= 1;
-  }
-  fclose(f);
-  if (rc == MPC_OK) rc = sync_all(h);
-  if (rc != MPC_OK) abandon_slots(h);
-  if (rc == MPC_OK && rows_done) *rows_done = end - begin;
-  return rc;
+  return feed_npy(HandleFeed{h}, path, first_row, n_rows, skip_last_row, rows_done);
 }
 
 namespace {
-
-constexpr int kLogKeys = 17, kLogRecordHeader = 62;
 
 // validates the file header of a GPGPU-Sim trace (LoaderGPGPU.cpp:93-119)
 int log_open(const char *path, FILE **out, std::string &err)
@@ -1100,78 +1449,132 @@ int mpc_gpgpusim_log_line_size(const char *log_path, uint32_t *line_size)
 int mpc_compress_gpgpusim_log(mpc_handle *h, const char *log_path, uint64_t *requests_read, uint64_t *lines_done)
 {
   if (!h || !log_path) return MPC_E_INVAL;
-  if (requests_read) *requests_read = 0;
-  if (lines_done) *lines_done = 0;
-  // the file is mapped and walked in memory (per-request stdio calls cap the rate at ~35 M requests/s)
-  const int fd = open(log_path, O_RDONLY);
-  if (fd < 0) return set_err(h, MPC_E_NOENT, std::string("Failed to open a file. Check the path of the file: ") + log_path);
-  struct stat st;
-  if (fstat(fd, &st) != 0) { close(fd); return set_err(h, MPC_E_NOENT, std::string("cannot stat ") + log_path); }
-  const u64 size = (u64)st.st_size;
-  constexpr u64 kFileHeader = 1 + 7 * kLogKeys;
-  const unsigned char *base = nullptr;
-  if (size > 0) {
-    void *m = mmap(nullptr, (size_t)size, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (m == MAP_FAILED) { close(fd); return set_err(h, MPC_E_NOMEM, std::string("cannot map ") + log_path); }
-    base = static_cast<const unsigned char *>(m);
-    (void)madvise(m, (size_t)size, MADV_SEQUENTIAL);
+  return feed_gpgpusim_log(HandleFeed{h}, log_path, requests_read, lines_done);
+}
+
+// ---- groups ---------------------------------------------------------------
+int mpc_group_create(mpc_handle *const *members, size_t n, mpc_group **out)
+{
+  if (!out) return MPC_E_INVAL;
+  *out = nullptr;
+  if (!members || n == 0) return group_err(nullptr, MPC_E_INVAL, "a group needs at least one member");
+  for (size_t i = 0; i < n; i++) {
+    if (!members[i]) return group_err(nullptr, MPC_E_INVAL, "member " + std::to_string(i) + " is NULL");
+    for (size_t j = 0; j < i; j++)
+      if (members[j] == members[i])
+        return group_err(nullptr, MPC_E_INVAL, "member " + std::to_string(i) + " repeats member " + std::to_string(j) + " (a handle is fed once)");
+    if (members[i]->L != members[0]->L)
+      return group_err(nullptr, MPC_E_INVAL, "members of different line sizes: member " + std::to_string(i) + " has " + std::to_string(members[i]->L) +
+                                                 "-byte lines, member 0 " + std::to_string(members[0]->L));
+    if (members[i]->device != members[0]->device)
+      return group_err(nullptr, MPC_E_INVAL, "members on different devices: member " + std::to_string(i) + " is bound to device " +
+                                                 std::to_string(members[i]->device) + ", member 0 to " + std::to_string(members[0]->device));
   }
-  close(fd);
-  auto unmap = [&]() { if (base) munmap(const_cast<unsigned char *>(base), (size_t)size); };
-  if (size < kFileHeader || base[0] != kLogKeys) {
-    unmap();
-    return set_err(h, MPC_E_PARSE, "The header of the GPGPU-sim trace file is not valid.");
+  mpc_group *g = new (std::nothrow) mpc_group();
+  if (!g) return MPC_E_NOMEM;
+  g->m.assign(members, members + n);
+  g->L = members[0]->L;
+  g->device = members[0]->device;
+  group_route(g);
+  bool ok = hipSetDevice(g->device) == hipSuccess;
+  for (int i = 0; i < 2 && ok; i++) {
+    GroupSlot &s = g->slots[i];
+    ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
+         hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
+    s.d_sizes.assign(n, nullptr); s.h_sizes.assign(n, nullptr); s.user_sizes.assign(n, nullptr);
+    s.d_sel.assign(n, nullptr); s.h_sel.assign(n, nullptr); s.user_sel.assign(n, nullptr);
   }
-  if (hipSetDevice(h->device) != hipSuccess) { unmap(); return set_err(h, MPC_E_HIP, "hipSetDevice failed"); }
-  int rc = ensure_slots(h);
-  if (rc != MPC_OK) { unmap(); return rc; }
-  const u64 L = (u64)h->L;
-  u64 requests = 0, lines = 0, fill = 0, pos = kFileHeader;
-  bool first = true;
+  if (!ok) {
+    mpc_group_destroy(g);
+    return group_err(nullptr, MPC_E_HIP, "hipStreamCreate / hipEventCreate failed for the group's slots");
+  }
+  for (mpc_handle *h : g->m)
+    for (int i = 0; i < 2; i++) h->group_streams.push_back(g->slots[i].stream);
+  *out = g;
+  return MPC_OK;
+}
+
+void mpc_group_destroy(mpc_group *g)
+{
+  if (!g) return;
+  (void)hipSetDevice(g->device);
+  for (int i = 0; i < 2; i++) {
+    GroupSlot &s = g->slots[i];
+    if (s.stream) (void)hipStreamSynchronize(s.stream);
+    for (mpc_handle *h : g->m)
+      h->group_streams.erase(std::remove(h->group_streams.begin(), h->group_streams.end(), s.stream), h->group_streams.end());
+    if (s.h_in) (void)hipHostFree(s.h_in);
+    if (s.d_in) (void)hipFree(s.d_in);
+    for (uint16_t *p : s.d_sizes) if (p) (void)hipFree(p);
+    for (uint16_t *p : s.h_sizes) if (p) (void)hipHostFree(p);
+    for (int8_t *p : s.d_sel) if (p) (void)hipFree(p);
+    for (int8_t *p : s.h_sel) if (p) (void)hipHostFree(p);
+    if (s.done) (void)hipEventDestroy(s.done);
+    if (s.stream) (void)hipStreamDestroy(s.stream);
+  }
+  if (g->mini) (void)hipHostFree(g->mini);
+  delete g;
+}
+
+const char *mpc_group_last_error(const mpc_group *g) { return g ? g->error.c_str() : g_create_error.c_str(); }
+
+const char *mpc_group_form(const mpc_group *g) { return g ? g->form.c_str() : ""; }
+
+int mpc_group_compress_batch(mpc_group *g, const uint8_t *lines, uint64_t n, uint16_t *const *sizes, int8_t *const *sel)
+{
+  if (!g || (!lines && n)) return MPC_E_INVAL;
+  if (n == 0) return MPC_OK;
+  GHIPCHK(g, hipSetDevice(g->device));
+  if (n <= kMiniLines) return group_small(g, lines, n, sizes, sel);
+  int rc = group_ensure_slots(g);
+  if (rc != MPC_OK) return rc;
+  u64 done = 0;
   int which = 0;
-  rc = retire(h, h->slots[which]);
-  while (rc == MPC_OK && pos + kLogRecordHeader <= size) {
-    uint32_t req_type, req_size;
-    std::memcpy(&req_type, base + pos + 38, 4);
-    std::memcpy(&req_size, base + pos + 58, 4);
-    if (first && req_size != L) {
-      rc = set_err(h, MPC_E_INVAL, "trace line size " + std::to_string(req_size) + " differs from the evaluator's " + std::to_string(L));
-      break;
-    }
-    first = false;
-    const u64 next = pos + kLogRecordHeader + (u64)req_size;
-    if (next > size) break;                                      // incomplete trailing request
-    if (req_type == 0u || req_type == 4u) {                      // GLOBAL_ACC_R, GLOBAL_ACC_W
-      if (req_size != L) {
-        rc = set_err(h, MPC_E_INVAL, "the GPGPU-sim trace mixes request sizes (" + std::to_string(req_size) + " after " + std::to_string(L) + " bytes)");
-        break;
-      }
-      std::memcpy(h->slots[which].h_in + fill * L, base + pos + kLogRecordHeader, (size_t)L);
-      fill++;
-    }
-    pos = next;
-    requests++;
-    if (fill == (u64)h->stage_lines) {
-      rc = submit(h, h->slots[which], fill, nullptr, nullptr);
-      if (rc != MPC_OK) break;
-      lines += fill;
-      fill = 0;
-      which ^= 1;
-      rc = retire(h, h->slots[which]);
-    }
+  while (done < n) {
+    GroupSlot &s = g->slots[which];
+    rc = group_retire(g, s);   // the slot's previous chunk (overlapped with the other slot's work)
+    if (rc != MPC_OK) break;
+    const u64 take = (n - done) < (u64)g->stage_lines ? (n - done) : (u64)g->stage_lines;
+    parallel_copy(s.h_in, lines + done * (u64)g->L, (size_t)(take * (u64)g->L));
+    rc = group_submit(g, s, take, sizes, sel, done);
+    if (rc != MPC_OK) break;
+    done += take;
+    which ^= 1;
   }
-  if (rc == MPC_OK && fill) {
-    rc = submit(h, h->slots[which], fill, nullptr, nullptr);
-    if (rc == MPC_OK) lines += fill;
-  }
-  if (rc == MPC_OK) rc = sync_all(h);
-  if (rc != MPC_OK) abandon_slots(h);
-  unmap();
-  if (rc == MPC_OK) {
-    if (requests_read) *requests_read = requests;
-    if (lines_done) *lines_done = lines;
-  }
+  if (rc == MPC_OK) rc = group_finish(g);
+  if (rc != MPC_OK) group_abandon(g);
   return rc;
+}
+
+int mpc_group_compress_batch_device(mpc_group *g, const void *d_lines, uint64_t n, uint16_t *const *d_sizes, int8_t *const *d_sel,
+                                    void *hip_stream)
+{
+  if (!g || (!d_lines && n)) return MPC_E_INVAL;
+  if (((uintptr_t)d_lines) & 15u) return group_err(g, MPC_E_INVAL, "device line buffer must be 16-byte aligned");
+  GHIPCHK(g, hipSetDevice(g->device));
+  return group_launch(g, d_lines, n, d_sizes, d_sel, (hipStream_t)hip_stream);
+}
+
+int mpc_group_compress_npy(mpc_group *g, const char *path, uint64_t first_row, uint64_t n_rows, int skip_last_row, uint64_t *rows_done)
+{
+  if (!g || !path) return MPC_E_INVAL;
+  return feed_npy(GroupFeed{g}, path, first_row, n_rows, skip_last_row, rows_done);
+}
+
+int mpc_group_compress_gpgpusim_log(mpc_group *g, const char *log_path, uint64_t *requests_read, uint64_t *lines_done)
+{
+  if (!g || !log_path) return MPC_E_INVAL;
+  return feed_gpgpusim_log(GroupFeed{g}, log_path, requests_read, lines_done);
+}
+
+int mpc_group_sync(mpc_group *g)
+{
+  if (!g) return MPC_E_INVAL;
+  GHIPCHK(g, hipSetDevice(g->device));
+  const int rc = group_finish(g);
+  if (rc != MPC_OK) return rc;
+  GHIPCHK(g, hipDeviceSynchronize());   // batches may have been queued on caller streams
+  return MPC_OK;
 }
 
 int mpc_stats_len(const mpc_handle *h, uint64_t *len)

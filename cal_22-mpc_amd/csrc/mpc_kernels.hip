@@ -688,6 +688,17 @@ __device__ __forceinline__ void fpc_flush(FpcCounts &t, u32 &words, u64 &bits, u
   bits = 0;
 }
 
+// one line: its counts into n (zeroed by the caller), its size in bits returned (fpc_kernel, baselines_kernel)
+template <int NW>
+__device__ __forceinline__ u32 fpc_line(const u32 (&w)[NW], FpcCounts &n)
+{
+  bool prev_zero = false;
+#pragma unroll
+  for (int i = 0; i < NW; i++) fpc_word(w[i], prev_zero, n);
+  // bits per prefix: 6, 7, 11, 19, 19, 19, 11, 35 (PREFIX_SIZE + payload, FPC.h:8 + FPC.cpp); a zero run pays once
+  return 35u * NW + 6u * n.runs - 7u * n.z - 4u * n.c1 - 8u * n.c2 - 16u * (n.c3 + n.e4 + n.e5) - 24u * n.e6;
+}
+
 template <int NW>   // words per line
 __global__ void __launch_bounds__(256)
 fpc_kernel(const uint4 *__restrict__ lines, u64 n_lines, uint16_t *__restrict__ sizes_out,
@@ -725,11 +736,7 @@ fpc_kernel(const uint4 *__restrict__ lines, u64 n_lines, uint16_t *__restrict__ 
     }
 #endif
     FpcCounts n = {0, 0, 0, 0, 0, 0, 0, 0};      // this line's counts
-    bool prev_zero = false;
-#pragma unroll
-    for (int i = 0; i < NW; i++) fpc_word(w[i], prev_zero, n);
-    // bits per prefix: 6, 7, 11, 19, 19, 19, 11, 35 (PREFIX_SIZE + payload, FPC.h:8 + FPC.cpp); a zero run pays once
-    const u32 size = 35u * NW + 6u * n.runs - 7u * n.z - 4u * n.c1 - 8u * n.c2 - 16u * (n.c3 + n.e4 + n.e5) - 24u * n.e6;
+    const u32 size = fpc_line<NW>(w, n);
     tot.z += n.z; tot.c1 += n.c1; tot.c2 += n.c2; tot.c3 += n.c3; tot.e4 += n.e4; tot.e5 += n.e5; tot.e6 += n.e6;
     words += NW;
     bits_acc += size;
@@ -756,6 +763,89 @@ fpc_kernel(const uint4 *__restrict__ lines, u64 n_lines, uint16_t *__restrict__ 
 // low planes at once -- "two adjacent ones" is the OR of X_r & X_(r+1), "DBP[c] == 0" the OR of the
 // d_r, "all ones" their AND.  Plane 32 (the borrows) is a single word and handled on its own.
 // ---------------------------------------------------------------------------
+// One line for baselines_kernel: its pattern counts added into the 16-bit fields of even / odd (patterns 0,2,4,6 /
+// 1,3,5), its size in bits returned.  The same text as the loop body of bpc_kernel below, which keeps its own copy:
+// called from there, the 128-byte instantiation allocates 107 instead of 150 VGPRs, and a solo handle's kernel is
+// not to change with the group's (profiles/group_kernel_resource_usage.txt).
+template <int NW>
+__device__ __forceinline__ u32 bpc_line(const u32 (&w)[NW], u64 &even, u64 &odd)
+{
+  constexpr int ND = NW - 1;                           // deltas = bits of a plane
+  // deltas (low words d_r, sign s_r = 0 / ~0 = bits 32.. of the 33-bit delta) and X_r
+  u32 X[ND];
+  u32 orD = 0, andX = ~0u, top = 0, adj = 0;
+  u32 b0 = 0, b1 = 0, hi = 0, pend = 0;       // ones per plane: bit 0, bit 1, "4 or more"; a waiting carry of weight 2
+#pragma unroll
+  for (int r = 0; r < ND; r++) {
+    const u32 d = w[r + 1] - w[r];
+    const u32 sgn = w[r + 1] < w[r] ? ~0u : 0u;
+    X[r] = d ^ __builtin_amdgcn_alignbit(sgn, d, 1);          // d ^ ((sign : d) >> 1)
+    top = bitop3<((BO_A & BO_B) | BO_C)>(sgn, 1u << r, top);  // plane 32: bit r = the borrow of delta r
+    orD |= d;
+    if (ND == 31) andX &= X[r];
+  }
+#pragma unroll
+  for (int r = 0; r + 1 < ND; r += 2) {
+    // two more planes-words into the count: full adder at weight 1, its carry joins the weight-2 column
+    const u32 s = xor3(b0, X[r], X[r + 1]), c = maj3(b0, X[r], X[r + 1]);
+    b0 = s;
+    if ((r / 2) & 1) {
+      const u32 s2 = xor3(b1, pend, c), c4 = maj3(b1, pend, c);
+      b1 = s2;
+      hi |= c4;
+    } else {
+      pend = c;
+    }
+    adj = bitop3<((BO_A & BO_B) | BO_C)>(X[r], X[r + 1], adj);
+    if (r + 2 < ND) adj = bitop3<((BO_A & BO_B) | BO_C)>(X[r + 1], X[r + 2], adj);
+  }
+  {
+    // ND is odd (7, 15, 31): one X left, and possibly a waiting carry
+    constexpr int last = ND - 1;
+    const u32 c = b0 & X[last];
+    b0 ^= X[last];
+    if ((((ND - 1) / 2) & 1) != 0) {          // a carry is waiting
+      const u32 s2 = xor3(b1, pend, c), c4 = maj3(b1, pend, c);
+      b1 = s2;
+      hi |= c4;
+    } else {
+      hi |= b1 & c;
+      b1 ^= c;
+    }
+  }
+  // classes of the 32 low planes, as bit masks (bit c = plane c)
+  const u32 nz = or3(b0, b1, hi);                                   // DBX[c] != 0
+  const u32 single = bitop3<(BO_A & ~BO_B & ~BO_C) & 0xFFu>(b0, b1, hi);
+  const u32 two = bitop3<(~BO_A & BO_B & ~BO_C) & 0xFFu>(b0, b1, hi) & adj;
+  const u32 zero_dbp = nz & ~orD;                                   // DBP[c] == 0 is tested first (BPC.cpp:127)
+  const u32 allones = ND == 31 ? (nz & orD & andX) : 0u;            // then DBX[c] == 0x7fffffff
+  const u32 rest = nz & ~zero_dbp & ~allones;
+  const u32 one_two = rest & (single | two);
+  const u32 unc = rest & ~(single | two);
+  // plane 32: DBX[32] = DBP[32] = the borrows
+  const u32 t_ones = (u32)__popc(top);
+  const bool t_nz = top != 0u;
+  const bool t_all = ND == 31 && top == 0x7fffffffu;
+  const bool t_one = !t_all && t_ones == 1u;
+  const bool t_two = !t_all && t_ones == 2u && (top & (top >> 1)) != 0u;
+  const bool t_unc = t_nz && !t_all && !t_one && !t_two;
+  // zero-DBX runs in coding order 32 .. 0: bit c of Z = DBX[c] == 0
+  const u64 Z = ((u64)(t_nz ? 0u : 1u) << 32) | (u64)(~nz);
+  const u64 starts = Z & ~(Z >> 1);                 // the plane above is not zero (or there is none)
+  const u64 longer = starts & (Z << 1);             // ... and the plane below is zero too: a run of 2 or more
+  const u32 n_runs = (u32)__popcll(starts);
+  const u32 n_zero = (u32)__popc(zero_dbp), n_all = (u32)__popc(allones) + (t_all ? 1u : 0u);
+  const u32 n_one = (u32)__popc(rest & single) + (t_one ? 1u : 0u);
+  const u32 n_two = (u32)__popc(rest & two & ~single) + (t_two ? 1u : 0u);
+  const u32 n_unc = (u32)__popc(unc) + (t_unc ? 1u : 0u);
+  (void)one_two;
+  const u32 length = 3u + 4u + 3u * n_runs + 4u * (u32)__popcll(longer) + 5u * (n_zero + n_all) + 10u * (n_one + n_two) + 32u * n_unc;
+  // BPCPattern order: Uncomp, ZRLE, Zero, SingleOne, ConsecTwoOnes, ZeroDBP (never), AllOnes
+  even += (u64)n_unc | ((u64)n_zero << 16) | ((u64)n_two << 32) | ((u64)n_all << 48);
+  odd += (u64)n_runs | ((u64)n_one << 16);
+  return length;
+}
+
 template <int NW>   // words per line: 8, 16 or 32
 __global__ void __launch_bounds__(256)
 bpc_kernel(const uint4 *__restrict__ lines, u64 n_lines, uint16_t *__restrict__ sizes_out,
@@ -890,6 +980,17 @@ bpc_kernel(const uint4 *__restrict__ lines, u64 n_lines, uint16_t *__restrict__ 
   if (threadIdx.x < MPC_BPC_RAW_LEN && s_counts[threadIdx.x]) atomicAdd(&gstats[threadIdx.x], s_counts[threadIdx.x]);
 }
 
+// ---------------------------------------------------------------------------
+// This file is compiled twice (build.py).  Without MPC_BASELINES_UNIT: every kernel a handle launches on its own, the
+// measurement helpers and their launchers (the kernel templates above are instantiated by the launchers).  With it:
+// only baselines_kernel, the group's kernel, on the device functions above -- in a unit of its own so that the code
+// and the register allocation of bdi_kernel / fpc_kernel / bpc_kernel cannot depend on it
+// (profiles/group_kernel_resource_usage.txt).
+// ---------------------------------------------------------------------------
+#ifndef MPC_BASELINES_UNIT
+#define MPC_BASELINES_UNIT 0
+#endif
+#if !MPC_BASELINES_UNIT
 // ---------------------------------------------------------------------------
 // BDI / FPC / BPC at line sizes without an unrolled kernel (the reference takes any line a loader
 // hands it: BDI.cpp:8, FPC.cpp:10, BPC.cpp:35).  One lane per line, byte and word loops straight
@@ -1151,3 +1252,223 @@ extern "C" hipError_t mpc_launch_read_probe(const void *d_buf, u64 bytes, u32 *d
                      d_sink);
   return hipGetLastError();
 }
+#else      // MPC_BASELINES_UNIT
+// ---------------------------------------------------------------------------
+// BDI, FPC and BPC in one pass (a group of handles, mpc_capi.hip): the three map a line the same way -- one lane per
+// line, the line in registers -- and each has little arithmetic behind the load, so the line is loaded once and every
+// member of the launch (MASK: bit 0 BDI, bit 1 FPC, bit 2 BPC; at least two) is evaluated on the same registers.
+// How the lines reach the lanes was picked by measurement (ms per 16 GiB with all three members): at
+// 32 and 64 bytes the one-stage ring of bdi_kernel (random 7.13 against 7.61, mixed 7.33 against 7.96), at 128 bytes
+// the transposed coalesced non-temporal loads of fpc_kernel / bpc_kernel (pointers 7.33 against 8.18).  BDI as in
+// bdi_kernel: at 32 and 64 bytes, exact scans that only a few lines of a group need are queued and run later, 64
+// queued lines at a time (without that the sine trace took 11.8 ms, more than the three solo launches together);
+// which scans run for the whole wave is a routing choice, a line's result does not depend on it.
+// Each member's per-line outputs and raw statistics are its
+// own and laid out as its own kernel's: per-workgroup counts in LDS, one atomic per non-zero word at the end.
+// ---------------------------------------------------------------------------
+template <int NW, int MASK>   // words per line: 8, 16 or 32
+__global__ void __launch_bounds__(256)
+baselines_kernel(const uint4 *__restrict__ lines, u64 n_lines, MpcBaselinesArgs A)
+{
+  constexpr bool BDI = (MASK & 1) != 0, FPC = (MASK & 2) != 0, BPC = (MASK & 4) != 0;
+  constexpr bool RING = NW <= 16;            // how the lines reach the lanes: see above
+  constexpr bool DEFER = BDI && NW <= 16;    // BDI scans that few lines of a group need are queued, as in bdi_kernel
+  __shared__ u32 s_queue[DEFER ? 4 : 1][DEFER ? kBdiQueue : 1];
+  __shared__ u64 s_bdi[MPC_BDI_RAW_LEN], s_fpc[MPC_FPC_RAW_LEN], s_bpc[MPC_BPC_RAW_LEN];
+  __shared__ __attribute__((aligned(1024))) uint4 s_stage[4][64 * (NW / 4)];
+  if (threadIdx.x < MPC_BDI_RAW_LEN) {
+    s_bdi[threadIdx.x] = 0;
+    if (threadIdx.x < MPC_FPC_RAW_LEN) s_fpc[threadIdx.x] = s_bpc[threadIdx.x] = 0;
+  }
+  __syncthreads();
+  // BDI: run-length accumulation per lane, (select, size) key and count (bdi_kernel)
+  u32 run_key = 0xffffffffu, run_cnt = 0;
+  auto bdi_run_flush = [&]() {
+    if (run_cnt) {
+      atomicAdd(&s_bdi[run_key >> 16], (u64)run_cnt);
+      atomicAdd(&s_bdi[9], (u64)run_cnt * (u64)(run_key & 0xffffu));
+    }
+  };
+  auto bdi_account = [&](u64 line, u32 best, int select) {
+    const u32 size = best + 4u;
+    if (A.bdi.sizes) A.bdi.sizes[line] = (uint16_t)size;
+    if (A.bdi.sel) A.bdi.sel[line] = (int8_t)select;
+    const u32 key = ((u32)select << 16) | size;
+    if (key != run_key) {
+      bdi_run_flush();
+      run_key = key;
+      run_cnt = 0;
+    }
+    run_cnt++;
+  };
+  const u32 lane = threadIdx.x & 63u;
+  auto fetch = [&](u32 (&w)[NW], u64 line) {      // plain loads: queued lines, the launch's last partial group
+    const uint4 *src = lines + line * (NW / 4);
+#pragma unroll
+    for (int i = 0; i < NW / 4; i++) {
+      const uint4 q = src[i];
+      w[4 * i] = q.x; w[4 * i + 1] = q.y; w[4 * i + 2] = q.z; w[4 * i + 3] = q.w;
+    }
+  };
+  // BDI's queued lines, 64 at a time, every scan they need (the other members have seen them already)
+  u32 *queue = s_queue[DEFER ? uni(threadIdx.x >> 6) : 0u];
+  u32 qn = 0;                                   // queued lines of this wave (wave-uniform)
+  const bool can_defer = n_lines <= 0xffffffffull;      // queue entries are 32-bit line indices
+  auto drain = [&]() __attribute__((always_inline)) {
+    while (qn > 0u) {
+      const u32 take = qn < 64u ? qn : 64u;
+      qn -= take;
+      const bool active = lane < take;
+      const u64 line = active ? (u64)queue[qn + lane] : 0ull;
+      u32 w[NW];
+      fetch(w, line);
+      u32 best;
+      int select;
+      bool deferred;
+      bdi_line<NW, false>(w, active, false, best, select, deferred);
+      if (active) bdi_account(line, best, select);
+    }
+  };
+  // FPC: per-lane totals (fpc_kernel)
+  FpcCounts f_tot = {0, 0, 0, 0, 0, 0, 0, 0};
+  u32 f_words = 0;
+  u64 f_bits = 0;
+  // BPC: pattern counts in 16-bit fields (bpc_kernel)
+  u64 even = 0, odd = 0, p_words = 0, p_bits = 0;
+  u32 since_flush = 0;
+  auto bpc_flush = [&]() {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const u64 e = (even >> (16 * k)) & 0xffffull, o = (odd >> (16 * k)) & 0xffffull;
+      if (e) atomicAdd(&s_bpc[2 * k], e);
+      if (o && k < 3) atomicAdd(&s_bpc[2 * k + 1], o);
+    }
+    if (p_words) atomicAdd(&s_bpc[7], p_words);
+    if (p_bits) atomicAdd(&s_bpc[8], p_bits);
+    even = odd = p_words = p_bits = 0;
+  };
+  // every member on one line held in w (every lane stays in: bdi_line votes across the wave)
+  auto evaluate = [&](const u32 (&w)[NW], u64 line, bool active) __attribute__((always_inline)) {
+    if (FPC && active) {
+      FpcCounts n = {0, 0, 0, 0, 0, 0, 0, 0};
+      const u32 size = fpc_line<NW>(w, n);
+      f_tot.z += n.z; f_tot.c1 += n.c1; f_tot.c2 += n.c2; f_tot.c3 += n.c3; f_tot.e4 += n.e4; f_tot.e5 += n.e5; f_tot.e6 += n.e6;
+      f_words += NW;
+      f_bits += size;
+      if (A.fpc.sizes) A.fpc.sizes[line] = (uint16_t)size;
+      if (A.fpc.sel) A.fpc.sel[line] = 0;
+      if (f_words >= (1u << 30)) fpc_flush(f_tot, f_words, f_bits, s_fpc);
+    }
+    if (BPC && active) {
+      const u32 length = bpc_line<NW>(w, even, odd);
+      p_words += 33u;
+      p_bits += length;
+      if (A.bpc.sizes) A.bpc.sizes[line] = (uint16_t)length;
+      if (A.bpc.sel) A.bpc.sel[line] = 0;
+      if (++since_flush == 1023u) {      // 1023 lines x 34 counts < 2^16 per field
+        bpc_flush();
+        since_flush = 0;
+      }
+    }
+    if (BDI) {
+      u32 best;
+      int select;
+      bool deferred;
+      bdi_line<NW, DEFER>(w, active, can_defer, best, select, deferred);
+      if (DEFER) {
+        const u64 dmask = __ballot(active && deferred);
+        if (dmask) {
+          const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(dmask >> 32), __builtin_amdgcn_mbcnt_lo((u32)dmask, 0u));
+          if (active && deferred) queue[qn + rank] = (u32)line;
+          qn += (u32)__popcll(dmask);
+        }
+      }
+      if (active && !deferred) bdi_account(line, best, select);
+      if (DEFER && qn + 64u > kBdiQueue) drain();        // wave-uniform: room for the next group's deferrals
+    }
+  };
+  if constexpr (RING) {
+  // whole groups of 64 lines through a one-stage ring per wave (bdi_kernel), grid-stride over the waves
+  constexpr int NQ = NW / 4;
+  constexpr u32 SB = 64u * 16u * NQ;            // bytes of a stage
+  const u32 wave = uni(threadIdx.x >> 6);
+  const u32 ring_lds = (u32)(uintptr_t)(__attribute__((address_space(3))) void *)s_stage + wave * SB;
+  u32 lane_off[NQ];
+#pragma unroll
+  for (int j = 0; j < NQ; j++) lane_off[j] = ring_src_off<NQ>(j, lane);
+  const u32 rd0 = (ring_lds + 16u * NQ * lane) | (16u * ring_swz<NQ>(lane));
+  const u64 full_groups = n_lines >> 6, gstride = (u64)gridDim.x * 4u;
+  u64 g = (u64)blockIdx.x * 4u + wave;
+  auto request = [&](u64 gg) { ring_request<NQ>(lane_off, lines + gg * (64u * NQ), ring_lds); };
+  if (g < full_groups) request(g);
+  while (g < full_groups) {
+    qn = uni(qn);
+    ring_wait_vm<0>();
+    u32 a[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; j++) a[j] = rd0 ^ (16u * (u32)j);
+    uint4 v[NQ];
+    ring_read<NQ>(v, a);
+    if (uni(g + gstride < full_groups)) request(g + gstride);       // the stage is free again
+    __builtin_amdgcn_sched_barrier(0);
+    u32 w[NW];
+#pragma unroll
+    for (int i = 0; i < NQ; i++) { w[4 * i] = v[i].x; w[4 * i + 1] = v[i].y; w[4 * i + 2] = v[i].z; w[4 * i + 3] = v[i].w; }
+    evaluate(w, g * 64u + lane, true);
+    g += gstride;
+  }
+  // the launch's last, partial group: plain loads, by one wave
+  if ((n_lines & 63ull) != 0ull && blockIdx.x == 0 && wave == 0u) {
+    const u64 line = full_groups * 64u + lane;
+    const bool active = line < n_lines;
+    u32 w[NW];
+    fetch(w, active ? line : n_lines - 1);
+    evaluate(w, line, active);
+  }
+  } else {
+  uint4 *stage = s_stage[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
+  for (u64 line0 = (u64)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); line0 < n_lines; line0 += (u64)gridDim.x * blockDim.x) {
+    u32 w[NW];
+    {
+      uint4 v[NW / 4];
+      stage_fetch_rows<NW / 4>(v, lines, line0, lane, n_lines);
+      stage_rows_to_lines<NW / 4>(v, stage, lane);
+#pragma unroll
+      for (int i = 0; i < NW / 4; i++) { w[4 * i] = v[i].x; w[4 * i + 1] = v[i].y; w[4 * i + 2] = v[i].z; w[4 * i + 3] = v[i].w; }
+    }
+    evaluate(w, line0 + lane, line0 + lane < n_lines);
+  }
+  }
+  if (DEFER) drain();
+  if (BDI) bdi_run_flush();
+  if (FPC) fpc_flush(f_tot, f_words, f_bits, s_fpc);
+  if (BPC) bpc_flush();
+  __syncthreads();
+  if (BDI && threadIdx.x < MPC_BDI_RAW_LEN && s_bdi[threadIdx.x]) atomicAdd(&A.bdi.raw[threadIdx.x], s_bdi[threadIdx.x]);
+  if (FPC && threadIdx.x < MPC_FPC_RAW_LEN && s_fpc[threadIdx.x]) atomicAdd(&A.fpc.raw[threadIdx.x], s_fpc[threadIdx.x]);
+  if (BPC && threadIdx.x < MPC_BPC_RAW_LEN && s_bpc[threadIdx.x]) atomicAdd(&A.bpc.raw[threadIdx.x], s_bpc[threadIdx.x]);
+}
+
+// The group's launch for BDI / FPC / BPC members (raw != NULL) of 32-, 64- or 128-byte lines, at least two of them.
+template <int NW>
+static void launch_baselines(int mask, int grid, hipStream_t stream, const uint4 *l, u64 n_lines, const MpcBaselinesArgs &A)
+{
+  switch (mask) {
+  case 3: hipLaunchKernelGGL((baselines_kernel<NW, 3>), dim3(grid), dim3(256), 0, stream, l, n_lines, A); break;
+  case 5: hipLaunchKernelGGL((baselines_kernel<NW, 5>), dim3(grid), dim3(256), 0, stream, l, n_lines, A); break;
+  case 6: hipLaunchKernelGGL((baselines_kernel<NW, 6>), dim3(grid), dim3(256), 0, stream, l, n_lines, A); break;
+  default: hipLaunchKernelGGL((baselines_kernel<NW, 7>), dim3(grid), dim3(256), 0, stream, l, n_lines, A); break;
+  }
+}
+
+extern "C" hipError_t mpc_launch_baselines(const void *d_lines, u64 n_lines, int L, const MpcBaselinesArgs *A, int grid, hipStream_t stream)
+{
+  const int mask = (A->bdi.raw ? 1 : 0) | (A->fpc.raw ? 2 : 0) | (A->bpc.raw ? 4 : 0);
+  if ((mask & (mask - 1)) == 0 || (L != 32 && L != 64 && L != 128)) return hipErrorInvalidValue;   // fewer than two members
+  const uint4 *l = static_cast<const uint4 *>(d_lines);
+  if (L == 32) launch_baselines<8>(mask, grid, stream, l, n_lines, *A);
+  else if (L == 64) launch_baselines<16>(mask, grid, stream, l, n_lines, *A);
+  else launch_baselines<32>(mask, grid, stream, l, n_lines, *A);
+  return hipGetLastError();
+}
+#endif     // MPC_BASELINES_UNIT

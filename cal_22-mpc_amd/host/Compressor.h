@@ -51,6 +51,11 @@ public:
   // ADDITIVE: bytes per line.  Default: the result object's LineSize (CompResult.h).
   virtual unsigned GetLineSize() { return m_Stat->LineSize; }
 
+  // ADDITIVE: the libmpc_hip handle behind a GPU evaluator (VPC, BDI, FPC, BPC, SC2), nullptr for every other
+  // compressor; lines waiting in the line buffer are evaluated first.  comp::CompressorSet (CompressorSet.h) feeds
+  // its members through it.
+  virtual mpc_handle *DeviceHandle() { return nullptr; }
+
   // ADDITIVE: buffered per-line mode, for drivers that keep the reference's loop (GetCacheline ->
   // CompressLine per line, main.cpp:225-243 -- which never looks at CompressLine()'s return value).
   // After SetLineBuffering(n), n > 0, CompressLine() copies the line into a host buffer of n lines and

@@ -1,0 +1,61 @@
+#include "CompressorSet.h"
+
+#include <cstdio>
+#include <cstdlib>
+
+#include "mpc_hip.h"
+
+namespace comp
+{
+
+static void fail(const char *what, int rc, mpc_group *g)
+{
+  const char *msg = mpc_group_last_error(g);
+  printf("%s (%d): %s\n", what, rc, msg ? msg : "");
+  exit(1);
+}
+
+CompressorSet::CompressorSet(const std::vector<Compressor *> &members) : m_Members(members), m_Group(nullptr)
+{
+  std::vector<mpc_handle *> handles;
+  for (size_t i = 0; i < m_Members.size(); i++) {
+    mpc_handle *h = m_Members[i] ? m_Members[i]->DeviceHandle() : nullptr;
+    if (!h) {
+      printf("CompressorSet: member %zu%s%s is not a GPU evaluator (VPC, BDI, FPC, BPC, SC2): it cannot be fed in a set.\n", i,
+             m_Members[i] ? " " : "", m_Members[i] ? m_Members[i]->GetCompressorName().c_str() : "");
+      exit(1);
+    }
+    handles.push_back(h);
+  }
+  int rc = mpc_group_create(handles.data(), handles.size(), &m_Group);
+  if (rc != MPC_OK) fail("CompressorSet: cannot create the group", rc, nullptr);
+}
+
+CompressorSet::~CompressorSet() { mpc_group_destroy(m_Group); }
+
+std::string CompressorSet::GetForm() const { return mpc_group_form(m_Group); }
+
+void CompressorSet::Prepare()
+{
+  for (Compressor *c : m_Members) (void)c->DeviceHandle();
+}
+
+void CompressorSet::CompressBatch(const uint8_t *lines, unsigned long long n)
+{
+  Prepare();
+  int rc = mpc_group_compress_batch(m_Group, lines, n, nullptr, nullptr);
+  if (rc != MPC_OK) fail("CompressorSet::CompressBatch", rc, m_Group);
+}
+
+unsigned long long CompressorSet::CompressFile(const std::string &tracePath)
+{
+  Prepare();
+  uint64_t done = 0;
+  const bool isLog = tracePath.size() > 4 && tracePath.compare(tracePath.size() - 4, 4, ".log") == 0;
+  int rc = isLog ? mpc_group_compress_gpgpusim_log(m_Group, tracePath.c_str(), nullptr, &done)
+                 : mpc_group_compress_npy(m_Group, tracePath.c_str(), 0, ~0ull, 1, &done);
+  if (rc != MPC_OK) fail("CompressorSet::CompressFile", rc, m_Group);
+  return done;
+}
+
+}  // namespace comp

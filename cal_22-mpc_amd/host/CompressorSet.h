@@ -1,0 +1,49 @@
+// CompressorSet.h -- ADDITIVE, no counterpart in the reference: several GPU evaluators over one trace at the cost of
+// one pass.  The reference compares compressors by running its driver once per algorithm (main.cpp:208-248 each
+// time); a CompressorSet feeds every member the same lines while the trace is read and staged once (mpc_group,
+// include/mpc_hip.h).  Each member keeps its own statistics: GetResult(i) is the member's GetResult(), and its
+// Print() / PrintDetail() write what a run with that member alone writes.
+#ifndef MPC_HOST_COMPRESSORSET_H
+#define MPC_HOST_COMPRESSORSET_H
+
+#include <string>
+#include <vector>
+
+#include "Compressor.h"
+
+struct mpc_group;
+
+namespace comp
+{
+
+class CompressorSet
+{
+public:
+  // Members are borrowed and must outlive the set; every one must be a GPU evaluator (VPC, BDI, FPC, BPC, SC2) of the
+  // same line size.  Anything else is refused with a message (exit(1), as the evaluators' constructors do).
+  explicit CompressorSet(const std::vector<Compressor *> &members);
+  ~CompressorSet();
+  CompressorSet(const CompressorSet &) = delete;
+  CompressorSet &operator=(const CompressorSet &) = delete;
+
+  size_t Size() const { return m_Members.size(); }
+  unsigned GetLineSize() { return m_Members[0]->GetLineSize(); }
+  // which members share a kernel launch, e.g. "VPC: unrolled; BDI+FPC+BPC: one kernel"
+  std::string GetForm() const;
+
+  // n consecutive lines of GetLineSize() bytes to every member
+  void CompressBatch(const uint8_t *lines, unsigned long long n);
+  // a .npy file (all rows but the last, as the reference driver does) or a GPGPU-Sim .log file to every member;
+  // returns the number of lines evaluated
+  unsigned long long CompressFile(const std::string &tracePath);
+  CompResult *GetResult(size_t i) { return m_Members[i]->GetResult(); }
+
+private:
+  void Prepare();      // members' buffered lines first
+  std::vector<Compressor *> m_Members;
+  mpc_group *m_Group;
+};
+
+}  // namespace comp
+
+#endif

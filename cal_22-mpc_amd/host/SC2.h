@@ -25,6 +25,7 @@ public:
   virtual void CompressBatch(const uint8_t *lines, unsigned long long n);
   virtual unsigned long long CompressFile(const std::string &tracePath);
   virtual unsigned GetLineSize() { return m_LineSize; }
+  virtual mpc_handle *DeviceHandle() { FlushLines(); m_Started = true; return m_Handle; }
   // Before the first line only: the evaluator is created again with the new warm-up count.
   void SetSamplingCnt(unsigned cnt);
 

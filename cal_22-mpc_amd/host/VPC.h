@@ -65,6 +65,7 @@ public:
   virtual void CompressBatch(const uint8_t *lines, unsigned long long n);
   virtual unsigned long long CompressFile(const std::string &tracePath);
   virtual unsigned GetLineSize() { return (unsigned)m_LineSize; }
+  virtual mpc_handle *DeviceHandle() { FlushLines(); return m_Handle; }
 
 private:
   mpc_handle *m_Handle;

@@ -6,6 +6,8 @@
 // (GLOBAL_ACC_R / GLOBAL_ACC_W requests, reference main.cpp:222-224) or APSim .txt files
 // (32-byte data beats of handshaking channels).  The other algorithm names are recognised
 // and reported as not part of this build.
+// ADDITIVE: -a takes a comma-separated list (-a VPC,BDI,FPC,BPC): every algorithm of the list is evaluated in ONE pass
+// over the trace (comp::CompressorSet) and writes exactly the files a run with its name alone writes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +17,7 @@
 
 #include "BDI.h"
 #include "BPC.h"
+#include "CompressorSet.h"
 #include "FPC.h"
 #include "LoaderAPSim.h"
 #include "LoaderGPGPU.h"
@@ -25,6 +28,8 @@
 #define REQ_SIZE 32   // line size asked of the APSim loader (reference main.cpp:23)
 
 static comp::CompResult *compressLines(comp::Compressor *compressor, trace::Loader *loader, bool perLine);
+static int runList(const std::vector<std::string> &names, const std::string &tracePath, const std::string &configPath,
+                   const std::string &outputDirPath);
 
 static const char *kHelp =
     "Usage:\n"
@@ -32,6 +37,7 @@ static const char *kHelp =
     "\n"
     "  -a, --algorithm arg  Compression algorithm\n"
     "                       [VPC/FPC/BDI/BPC/CPACK/SC2/PATTERN/VIEWER]. Default=VPC\n"
+    "                       A list (VPC,BDI,FPC,BPC) is evaluated in one pass.\n"
     "  -i, --input arg      Input GPGPU-Sim trace file path. Supported extensions:\n"
     "                       .log, .npy\n"
     "  -c, --config arg     Config file path (.json).\n"
@@ -97,12 +103,37 @@ int main(int argc, char **argv)
   std::string algorithm = a.has_algorithm ? a.algorithm : "VPC";
   bool help = a.help;
   if (!a.has_input) help = true;
+  // a list of algorithms: checked before anything is opened or written
+  std::vector<std::string> list;
+  if (algorithm.find(',') != std::string::npos) list = mpctext::split(algorithm, ",");      // ("BDI," has an empty element)
+  for (size_t i = 0; i < list.size() && !help; i++) {
+    const std::string &n = list[i];
+    if (n == "CPACK" || n == "SC2" || n == "PATTERN" || n == "VIEWER") {
+      std::cout << "Algorithm " << n << " is not part of this build: VPC, BDI, FPC and BPC are (see DESIGN.md, \"Out of scope\")." << std::endl;
+      return 1;
+    }
+    if (!(n == "VPC" || n == "BDI" || n == "FPC" || n == "BPC")) {
+      std::cout << "Invalid name of algorithm in the list \"" << algorithm << "\": \"" << n << "\"." << std::endl;
+      return 1;
+    }
+    for (size_t j = 0; j < i; j++)
+      if (list[j] == n) {
+        std::cout << "Algorithm " << n << " is named twice in the list \"" << algorithm << "\"." << std::endl;
+        return 1;
+      }
+    if (a.per_line) {
+      std::cout << "--per-line / --line-buffer evaluate one algorithm: a list of algorithms is fed in batches." << std::endl;
+      return 1;
+    }
+    if (n == "VPC" && !a.has_config) help = true;
+  }
   if (algorithm == "VPC" && !a.has_config) help = true;
   if (help) {
     std::cout << kHelp << std::endl;
     return 0;
   }
   const std::string tracePath = a.input, configPath = a.config, outputDirPath = a.has_output ? a.output : "";
+  if (!list.empty()) return runList(list, tracePath, configPath, outputDirPath);
 
   // loader by extension (reference main.cpp:74-83)
   trace::Loader *loader = nullptr;
@@ -213,4 +244,71 @@ static comp::CompResult *compressLines(comp::Compressor *compressor, trace::Load
     delete memReq;      // (the reference leaks its request object)
   }
   return compressor->GetResult();
+}
+
+// -a with a list: one pass over the trace for all of them, then each algorithm's own result files and one
+// "<name> comp.ratio: <ratio>" line each, in list order.
+static int runList(const std::vector<std::string> &names, const std::string &tracePath, const std::string &configPath,
+                   const std::string &outputDirPath)
+{
+  std::vector<std::string> parts = mpctext::split(tracePath, "/");
+  if (parts.size() < 2) {
+    std::cout << "The trace path needs at least one '/' (workload name = <directory>_<file>)." << std::endl;
+    return 1;
+  }
+  std::string appName = parts[parts.size() - 1];
+  mpctext::replace_all(appName, ".log", "");
+  mpctext::replace_all(appName, ".npy", "");
+  mpctext::replace_all(appName, ".txt", "");
+  const std::string workloadName = parts[parts.size() - 2] + "_" + appName;
+
+  trace::Loader *loader = nullptr;
+  if (mpctext::ends_with(tracePath, ".npy")) {
+    loader = new trace::LoaderNPY(tracePath);
+  } else if (mpctext::ends_with(tracePath, ".log")) {
+    loader = new trace::gpgpusim::LoaderGPGPU(tracePath);
+  } else if (mpctext::ends_with(tracePath, ".txt")) {
+    loader = new trace::apsim::LoaderGPGPU(tracePath, REQ_SIZE);
+  } else {
+    std::cerr << "Unsupported extension." << std::endl;
+    abort();
+  }
+  const unsigned lineSize = loader->GetCachelineSize();
+  std::vector<comp::Compressor *> members;
+  for (const std::string &n : names) {
+    comp::Compressor *c = n == "VPC" ? static_cast<comp::Compressor *>(new comp::VPC(configPath))
+                          : n == "BDI" ? static_cast<comp::Compressor *>(new comp::BDI(lineSize))
+                          : n == "FPC" ? static_cast<comp::Compressor *>(new comp::FPC(lineSize))
+                                       : static_cast<comp::Compressor *>(new comp::BPC(lineSize));
+    if (c->GetLineSize() != lineSize) {
+      printf("The trace has %u-byte lines but the evaluator is configured for %u-byte lines.\n", lineSize, c->GetLineSize());
+      exit(1);
+    }
+    members.push_back(c);
+  }
+  {
+    comp::CompressorSet set(members);
+    const std::string path = loader->GetStreamablePath();
+    if (!path.empty()) {
+      set.CompressFile(path);
+    } else {
+      const unsigned long long cap = (64ull << 20) / lineSize;
+      std::vector<uint8_t> buf((size_t)(cap * lineSize));
+      for (;;) {
+        unsigned long long n = loader->GetBatch(buf.data(), cap);
+        if (n == 0) break;
+        set.CompressBatch(buf.data(), n);
+      }
+    }
+    for (size_t i = 0; i < names.size(); i++) {
+      comp::CompResult *compStat = set.GetResult(i);
+      const std::string saveFileName = (names[i] == "VPC") ? parseConfig(configPath) : names[i];
+      std::cout << names[i] << " comp.ratio: " << mpctext::num(compStat->CompRatio) << std::endl;
+      compStat->Print(workloadName, outputDirPath + "/" + saveFileName + "_results.csv");
+      compStat->PrintDetail(workloadName, outputDirPath + "/" + saveFileName + "_results_detail.csv");
+    }
+  }
+  delete loader;
+  for (comp::Compressor *c : members) delete c;
+  return 0;
 }

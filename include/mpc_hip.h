@@ -224,6 +224,42 @@ int mpc_compress_gpgpusim_log(mpc_handle *h, const char *log_path, uint64_t *req
 /* Header probe: req_size of the first request (0 for a trace without requests). */
 int mpc_gpgpusim_log_line_size(const char *log_path, uint32_t *line_size);
 
+/* ---- groups: several evaluators over one trace (replaces main.cpp:208-248 run once per algorithm) ----
+ * The reference compares compressors by running its driver once per algorithm: the trace is loaded and walked again
+ * for each.  A group is an ordered set of existing handles of ONE line size on ONE device that are fed together: a
+ * chunk of the trace is staged once (the group owns its two pinned + device slots) and every member's launch follows
+ * on the slot's stream, in member order.  Each member sees every line exactly as if it had been called alone and keeps
+ * its own statistics: mpc_stats_get and everything else that takes the member's handle work as before.  BDI, FPC and
+ * BPC members of 32-, 64- or 128-byte lines, when at least two of them are in the group, share one kernel that loads a
+ * line once and evaluates all of them on it; every other member launches its own kernel (mpc_group_form).
+ * The group BORROWS the handles: destroy the group before its members.  A member stays usable on its own between group
+ * calls.  One group is used from one thread at a time.                                                             */
+typedef struct mpc_group mpc_group;
+/* MPC_E_INVAL with a message (mpc_group_last_error(NULL)) for: no member, a NULL or repeated handle, members of
+ * different line sizes, members on different devices.                                                              */
+int mpc_group_create(mpc_handle *const *members, size_t n, mpc_group **out);
+void mpc_group_destroy(mpc_group *g);
+/* Last error text of this group (or of the last failed mpc_group_create if g==NULL). */
+const char *mpc_group_last_error(const mpc_group *g);
+/* One line of text, for logs and tests: which members share a kernel launch and which run their own, in member order,
+ * e.g. "VPC: unrolled; BDI+FPC+BPC: one kernel; SC2: own kernel" (a VPC member: its mpc_kernel_form).               */
+const char *mpc_group_form(const mpc_group *g);
+/* mpc_compress_batch for every member.  size_bits_out / selected_out: arrays of one pointer per member, in member
+ * order; the array itself or any entry may be NULL (per-line output buffers exist only for members that were asked
+ * for theirs).  Calls of up to 512 lines are evaluated in place from one small pinned buffer: one launch per member
+ * or per shared launch, one synchronisation.                                                                      */
+int mpc_group_compress_batch(mpc_group *g, const uint8_t *lines, uint64_t n_lines,
+                             uint16_t *const *size_bits_out, int8_t *const *selected_out);
+/* mpc_compress_batch_device for every member: asynchronous on `hip_stream`, optional DEVICE output arrays per member. */
+int mpc_group_compress_batch_device(mpc_group *g, const void *d_lines, uint64_t n_lines,
+                                    uint16_t *const *d_size_bits_out, int8_t *const *d_selected_out, void *hip_stream);
+/* mpc_compress_npy / mpc_compress_gpgpusim_log for every member: the file is read and staged once. */
+int mpc_group_compress_npy(mpc_group *g, const char *npy_path, uint64_t first_row, uint64_t n_rows,
+                           int skip_last_row, uint64_t *rows_done);
+int mpc_group_compress_gpgpusim_log(mpc_group *g, const char *log_path, uint64_t *requests_read, uint64_t *lines_done);
+/* Waits for the group's slots and for the whole device (mpc_sync). */
+int mpc_group_sync(mpc_group *g);
+
 /* ---- measurement helpers (bench.py; not part of the evaluator) -----------
  * Synthetic device-resident traces of SURVEY.md 8d, generated on the GPU:
  * kind 0 zeros, 1 random u32, 2 fp32 sine, 3 mixed int/fp, 4 pointer qwords.

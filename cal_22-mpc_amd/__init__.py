@@ -23,7 +23,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPC_HIP_LIB") or os.path.join(HERE, "libmpc_hip.so")   # override: development builds only
 
-MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2 = 1, 2, 3, 4, 5, 6
+MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2, MPC_PATH_PATTERN = 1, 2, 3, 4, 5, 6, 7
 SYNTH_KINDS = {"zeros": 0, "random_u32": 1, "sine_f32": 2, "mixed": 3, "pointers_u64": 4}
 
 
@@ -80,6 +80,8 @@ def lib() -> C.CDLL:
             "mpc_sc2_sampling_lines": ([C.c_uint64], C.c_uint64),
             "mpc_sc2_code_lengths": ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
             "mpc_sc2_table": ([H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
+            "mpc_create_pattern": ([C.c_uint, C.c_int, C.POINTER(H)], C.c_int),
+            "mpc_pattern_distinct_lines": ([H, C.POINTER(C.c_uint64)], C.c_int),
             "mpc_destroy": ([H], None),
             "mpc_get_info": ([H, C.POINTER(Info)], C.c_int),
             "mpc_last_error": ([H], C.c_char_p),
@@ -131,6 +133,7 @@ EXPORTED_SYMBOLS = [
     "mpc_synth_fill", "mpc_read_bandwidth_probe",
     "mpc_group_create", "mpc_group_destroy", "mpc_group_last_error", "mpc_group_form", "mpc_group_compress_batch",
     "mpc_group_compress_batch_device", "mpc_group_compress_npy", "mpc_group_compress_gpgpusim_log", "mpc_group_sync",
+    "mpc_create_pattern", "mpc_pattern_distinct_lines",
 ]
 # The SC2 entry points of include/mpc_hip.h.  Kept apart from EXPORTED_SYMBOLS, which lists the names of the
 # header's lowercase-letter form (mpc_[a-z_]+) only; every one of both lists is exported by libmpc_hip.so.
@@ -384,6 +387,56 @@ class SC2(_Evaluator):
         return sym[:n.value].copy(), lens[:n.value].copy()
 
 
+def pattern_entropy(counts) -> float:
+    """``PatternResult::ComputeEntropy`` (reference ``Pattern.h:124-154``): the map holds the symbols that occurred,
+    ``entropy += -p * log2(p)`` in ascending symbol order."""
+    import math
+    counts = [int(c) for c in counts]
+    total = sum(counts)
+    entropy = 0.0
+    for c in counts:
+        if c:
+            p = float(c) / float(total)
+            entropy += -p * math.log2(p)
+    return entropy
+
+
+def pattern_result_from_vector(v: np.ndarray) -> Dict:
+    """``PatternResult`` (reference ``Pattern.h:30-226``) from the statistics vector."""
+    sym = [int(x) for x in v[22:278]]
+    exc = [int(x) for x in v[278:534]]
+    return {"name": "Pattern Checker", "lines": int(v[0]), "original_bits": 0, "compressed_bits": 0, "comp_ratio": 0.0,
+            "size_bits": int(v[3]), "Z": int(v[4]), "R": int(v[5]), "T": int(v[6]), "U": int(v[7]), "Total": int(v[8]),
+            "implicit_counts": [int(x) for x in v[9:15]], "explicit_counts": [int(x) for x in v[15:21]],
+            "joined_lines": int(v[21]), "symbol_counts": sym, "symbol_counts_except": exc,
+            "entropy": pattern_entropy(sym), "entropy_except": pattern_entropy(exc)}
+
+
+class Pattern(_Evaluator):
+    """``comp::Pattern(lineSize)`` (reference ``Pattern.h:228-252``): zero / repeated / already-seen / base-delta bytes and
+    the byte entropy of a trace.  Per-line ``selected`` is the ``PatternState`` (0..5, 9 = NotDefined).  The set of
+    lines seen lives on the device and holds up to 2**24 - 1 distinct lines (the reference evicts beyond that; this
+    raises ``MpcError`` instead).  One object per trace and per GPU."""
+
+    def __init__(self, line_size: int, device: int = 0):
+        super().__init__()
+        rc = lib().mpc_create_pattern(line_size, device, C.byref(self._h))
+        if rc != 0:
+            raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
+        self._finish()
+        self.kernel_path = self.info.kernel_path
+
+    def result(self) -> Dict:
+        """The counts of ``PatternResult`` and both entropies (the reference computes them in ``Print``)."""
+        return pattern_result_from_vector(self.stats_vector())
+
+    def distinct_lines(self) -> int:
+        """Lines in the set since creation (``reset()`` keeps the set)."""
+        n = C.c_uint64()
+        self._check(lib().mpc_pattern_distinct_lines(self._h, C.byref(n)))
+        return int(n.value)
+
+
 class EvaluatorSet:
     """A group of evaluators of one line size on one device that are fed together (``mpc_group``): the trace is
     staged once per chunk and every member sees every line as if it had been called alone.  The members keep their
@@ -394,7 +447,7 @@ class EvaluatorSet:
         self.members = list(evaluators)
         self._g = C.c_void_p()
         if any(not isinstance(e, _Evaluator) or not e._h for e in self.members):
-            raise ValueError("EvaluatorSet takes open VPC / BDI / FPC / BPC / SC2 evaluators")
+            raise ValueError("EvaluatorSet takes open VPC / BDI / FPC / BPC / SC2 / Pattern evaluators")
         arr = (C.c_void_p * max(1, len(self.members)))(*[e._h.value for e in self.members])
         rc = lib().mpc_group_create(arr, len(self.members), C.byref(self._g))
         if rc != 0:

@@ -55,6 +55,7 @@ def build_lib(force: bool = False, verbose: bool = False, test: bool = False) ->
     units += [(os.path.join(CSRC, "mpc_kernels.hip"), "kernels.o", []),
               (os.path.join(CSRC, "mpc_kernels.hip"), "baselines.o", ["-DMPC_BASELINES_UNIT=1"]),      # the group's shared kernel
               (os.path.join(CSRC, "mpc_sc2.hip"), "sc2.o", []),
+              (os.path.join(CSRC, "mpc_pattern.hip"), "pattern.o", []),
               (os.path.join(CSRC, "mpc_capi.hip"), "capi.o", [])]
     tflag = ["-DMPC_TESTING=1"] if test else []
     procs = []

@@ -23,6 +23,7 @@
 #include "mpc_config.h"
 #include "mpc_device.h"
 #include "mpc_sc2.h"
+#include "mpc_pattern.h"
 
 // libmpc_hip_test.so (build.py, -DMPC_TESTING=1): route counters behind the raw statistics and a cap on the launch grid,
 // see mpc_kernel_common.h.  Must agree with the kernels' translation units.
@@ -53,6 +54,8 @@ hipError_t mpc_launch_sc2_count(const void *, u64, int, u64 *, u64, uint16_t *, 
 hipError_t mpc_launch_sc2_hist(const u64 *, u64, u64, int, uint32_t *, int, hipStream_t);
 hipError_t mpc_launch_sc2_collect(const u64 *, u64, u64, u64 *, uint32_t *, int, hipStream_t);
 hipError_t mpc_launch_sc2_size(const void *, u64, int, const MpcSc2Table *, uint16_t *, int8_t *, u64 *, int, hipStream_t);
+hipError_t mpc_launch_pattern(const void *, u64, int, uint16_t *, int8_t *, u64 *, int, hipStream_t);
+hipError_t mpc_launch_pattern_set(const void *, uint32_t, int, const MpcPatternSet *, u64 *, int, hipStream_t);
 }
 
 namespace {
@@ -83,7 +86,7 @@ struct VpcRoute { VpcKernel kernel = VpcKernel::Generic; std::string why_generic
 }  // namespace
 
 struct mpc_handle {
-  int algorithm = 0;   // 0 VPC, 1 BDI, 2 FPC, 3 BPC, 4 SC2
+  int algorithm = 0;   // 0 VPC, 1 BDI, 2 FPC, 3 BPC, 4 SC2, 5 Pattern
   int device = 0;
   int L = 0;
   int num_cus = 256;
@@ -119,6 +122,14 @@ struct mpc_handle {
     std::vector<uint32_t> symbols;   // the table, ascending symbol order
     std::vector<uint16_t> lengths;
   } sc2;
+  // Pattern: the set of distinct lines (mpc_pattern.h).  Its passes must not overlap on one set: every call waits, on its
+  // own stream, for the event the call before it recorded behind its passes -- whichever stream that was.
+  struct {
+    MpcPatternSet set{};
+    hipEvent_t done = nullptr;
+    bool recorded = false;
+    bool over = false;           // a line beyond the capacity arrived: the handle takes no more lines
+  } pat;
   std::vector<hipStream_t> group_streams;   // the slot streams of the groups this handle is a member of (sc2_build waits for them)
   std::string error;
 };
@@ -374,11 +385,13 @@ int grid_for(const mpc_handle *h, u64 work_items, int block, int per_cu)
 }
 
 int launch_sc2(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
+int launch_pattern(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
 
 int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s)
 {
   if (n == 0) return MPC_OK;
   if (h->algorithm == 4) return launch_sc2(h, d_lines, n, d_sizes, d_sel, s);
+  if (h->algorithm == 5) return launch_pattern(h, d_lines, n, d_sizes, d_sel, s);
   hipError_t e;
   if (h->algorithm == 3) {
     e = mpc_launch_bpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
@@ -501,6 +514,45 @@ int launch_sc2(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int
   return MPC_OK;
 }
 
+// Pattern: the line analysis, then the set passes behind those of every earlier call
+const char *const kPatternLimit = "Pattern: more than 16777215 (2^24 - 1) distinct lines: the reference starts evicting there, which is not modelled";
+
+int launch_pattern(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s)
+{
+  if (h->pat.over) return set_err(h, MPC_E_INVAL, kPatternLimit);
+  const uint8_t *base = static_cast<const uint8_t *>(d_lines);
+  auto failed = [&](hipError_t e) { return set_err(h, MPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)); };
+  // (a launch stays below 2^31 bytes: the workgroups count bytes in 32 bits)
+  for (u64 at = 0; at < n; at += MPC_PATTERN_CHUNK) {
+    const u64 take = std::min<u64>(n - at, MPC_PATTERN_CHUNK);
+    const hipError_t e = mpc_launch_pattern(base + at * (u64)h->L, take, h->L, d_sizes ? d_sizes + at : nullptr, d_sel ? d_sel + at : nullptr,
+                                            h->d_raw, grid_for(h, take, 256, kWgPerCu), s);
+    if (e != hipSuccess) return failed(e);
+  }
+  if (h->pat.recorded) HIPCHK(h, hipStreamWaitEvent(s, h->pat.done, 0));
+  for (u64 at = 0; at < n; at += MPC_PATTERN_CHUNK) {
+    const u64 take = std::min<u64>(n - at, MPC_PATTERN_CHUNK);
+    HIPCHK(h, hipMemsetAsync(h->pat.set.ctl + MPC_PSET_PENDING_A, 0, 2 * sizeof(u64), s));
+    const hipError_t e = mpc_launch_pattern_set(base + at * (u64)h->L, (uint32_t)take, h->L, &h->pat.set, h->d_raw, grid_for(h, take, 256, 8), s);
+    if (e != hipSuccess) return failed(e);
+  }
+  HIPCHK(h, hipEventRecord(h->pat.done, s));
+  h->pat.recorded = true;
+  return MPC_OK;
+}
+
+// Pattern, at a point where the handle's work is complete: has a line beyond the capacity arrived?
+int pattern_status(mpc_handle *h)
+{
+  if (h->algorithm != 5) return MPC_OK;
+  if (!h->pat.over) {
+    u64 ctl[2] = {0, 0};
+    HIPCHK(h, hipMemcpy(ctl, h->pat.set.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+    h->pat.over = ctl[MPC_PSET_OVERFLOW] != 0;
+  }
+  return h->pat.over ? set_err(h, MPC_E_INVAL, kPatternLimit) : MPC_OK;
+}
+
 int ensure_slots(mpc_handle *h)
 {
   if (h->slots_ready) return MPC_OK;
@@ -542,7 +594,7 @@ int compress_small(mpc_handle *h, const uint8_t *lines, uint64_t n, uint16_t *si
   HIPCHK(h, hipStreamSynchronize(h->stream));   // (polling hipStreamQuery instead was slower: 46 k vs 58 k lines/s)
   if (sizes) std::memcpy(sizes, out_sizes, (size_t)n * sizeof(uint16_t));
   if (sel) std::memcpy(sel, out_sel, (size_t)n);
-  return MPC_OK;
+  return pattern_status(h);
 }
 
 // wait for a slot's in-flight chunk and hand its per-line results to the caller
@@ -593,12 +645,34 @@ int sync_all(mpc_handle *h)
     if (rc != MPC_OK) return rc;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  return MPC_OK;
+  return pattern_status(h);
 }
 
 // raw device statistics -> ABI vector (added into `vec`)
 void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<u64> &vec)
 {
+  if (h->algorithm == 5) {
+    const u64 L = (u64)h->L;
+    vec[0] += raw[MPC_PAT_LINES];
+    vec[3] += raw[MPC_PAT_SIZES];
+    vec[4] += L * raw[MPC_PAT_ZERO];
+    vec[5] += L * raw[MPC_PAT_SAME];
+    vec[6] += L * raw[MPC_PAT_EXISTED];
+    vec[7] += L * raw[MPC_PAT_UNDEF];
+    vec[8] += L * raw[MPC_PAT_LINES];
+    for (int k = 0; k < 6; k++) {
+      vec[9 + k] += raw[MPC_PAT_IMPLICIT + k];
+      vec[15 + k] += raw[MPC_PAT_EXPLICIT + k];
+    }
+    vec[21] += raw[MPC_PAT_JOINED];
+    // SymbolCounts = the ordinary lines' bytes + L/4 of each byte of a word-same line's word + L zero bytes per zero line
+    for (int b = 0; b < 256; b++) {
+      vec[22 + b] += raw[MPC_PAT_HIST + b] + (L / 4) * raw[MPC_PAT_SAME_HIST + b];
+      vec[278 + b] += raw[MPC_PAT_HIST + b];
+    }
+    vec[22] += L * raw[MPC_PAT_ZERO];
+    return;
+  }
   if (h->algorithm == 4) {
     // lines and warm-up lines are counted by the host (it splits every call at line S); bits and hits on the device
     vec[0] += h->sc2.lines;
@@ -876,7 +950,7 @@ int group_err(mpc_group *g, int code, const std::string &msg)
 
 const char *algorithm_name(int algorithm)
 {
-  static const char *const name[] = {"VPC", "BDI", "FPC", "BPC", "SC2"};
+  static const char *const name[] = {"VPC", "BDI", "FPC", "BPC", "SC2", "PATTERN"};
   return name[algorithm];
 }
 
@@ -909,7 +983,7 @@ void group_route(mpc_group *g)
         if (is_shared(j)) part += (part.empty() ? "" : "+") + std::string(algorithm_name(g->m[(size_t)j]->algorithm));
       part += ": one kernel";
     } else {
-      part = std::string(algorithm_name(h->algorithm)) + ": " + (h->algorithm == 0 ? mpc_kernel_form(h) : "own kernel");
+      part = std::string(algorithm_name(h->algorithm)) + ": " + (h->algorithm == 0 ? mpc_kernel_form(h) : h->algorithm == 5 ? "own kernels" : "own kernel");
     }
     form += (form.empty() ? "" : "; ") + part;
   }
@@ -1025,6 +1099,8 @@ void group_abandon(mpc_group *g)
   }
 }
 
+int group_members_status(mpc_group *g);
+
 int group_finish(mpc_group *g)
 {
   for (int i = 0; i < 2; i++) {
@@ -1032,6 +1108,16 @@ int group_finish(mpc_group *g)
     if (rc != MPC_OK) return rc;
   }
   for (int i = 0; i < 2; i++) GHIPCHK(g, hipStreamSynchronize(g->slots[i].stream));
+  return group_members_status(g);
+}
+
+// a Pattern member that ran into its capacity fails the group call (checked wherever the group has synchronised)
+int group_members_status(mpc_group *g)
+{
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const int rc = pattern_status(g->m[i]);
+    if (rc != MPC_OK) return group_err(g, rc, "member " + std::to_string(i) + " (" + algorithm_name(g->m[i]->algorithm) + "): " + g->m[i]->error);
+  }
   return MPC_OK;
 }
 
@@ -1058,7 +1144,7 @@ int group_small(mpc_group *g, const uint8_t *lines, u64 n, uint16_t *const *size
     if (ds[i]) std::memcpy(sizes[i], ds[i], (size_t)n * sizeof(uint16_t));
     if (dl[i]) std::memcpy(sel[i], dl[i], (size_t)n);
   }
-  return MPC_OK;
+  return group_members_status(g);
 }
 
 struct GroupFeed {
@@ -1175,6 +1261,70 @@ int mpc_create_fpc(unsigned line_size, int device, mpc_handle **out)
   return MPC_OK;
 }
 
+int mpc_create_pattern(unsigned line_size, int device, mpc_handle **out)
+{
+  if (!out) return MPC_E_INVAL;
+  *out = nullptr;
+  // 8-, 4- and 2-byte values (Pattern.cpp:26-58): a multiple of 8, or checkPattern reads past the line
+  if (line_size < 8 || line_size > MPC_MAX_LINE || (line_size % 8)) {
+    g_create_error = "Pattern line size must be a multiple of 8 in 8.." + std::to_string(MPC_MAX_LINE) + " bytes";
+    return MPC_E_INVAL;
+  }
+  mpc_handle *h = new (std::nothrow) mpc_handle();
+  if (!h) return MPC_E_NOMEM;
+  h->algorithm = 5;
+  h->L = (int)line_size;
+  h->raw_len = MPC_PATTERN_RAW_LEN;
+  h->stats_len = 534;
+  int rc = pick_device(device, &h->device, &h->num_cus);
+  if (rc == MPC_OK) rc = finish_create(h);
+  if (rc == MPC_OK) {
+    MpcPatternSet &S = h->pat.set;
+    const size_t slots = (size_t)1 << MPC_PATTERN_SLOT_BITS;
+    S.tag_mask = ~0ull;
+#if MPC_TESTING
+    // test library only: a hash of a few bits, so that unequal lines meet on the tag and in the chains
+    if (const char *e = getenv("MPC_TEST_PATTERN_TAG_BITS")) {
+      const long bits = atol(e);
+      if (bits >= 1 && bits < 64) S.tag_mask = (1ull << bits) - 1ull;
+    }
+#endif
+    if (hipMalloc((void **)&S.tags, slots * sizeof(u64)) != hipSuccess || hipMalloc((void **)&S.store, slots * (size_t)line_size) != hipSuccess ||
+        hipMalloc((void **)&S.ctl, MPC_PSET_WORDS * sizeof(u64)) != hipSuccess ||
+        hipMalloc((void **)&S.pend_a, (size_t)MPC_PATTERN_CHUNK * sizeof(uint2)) != hipSuccess ||
+        hipMalloc((void **)&S.pend_b, (size_t)MPC_PATTERN_CHUNK * sizeof(uint2)) != hipSuccess) {
+      g_create_error = "hipMalloc of the Pattern line set (" + std::to_string(slots * (sizeof(u64) + line_size)) + " bytes) failed";
+      rc = MPC_E_NOMEM;
+    } else if (hipMemset(S.tags, 0, slots * sizeof(u64)) != hipSuccess || hipMemset(S.ctl, 0, MPC_PSET_WORDS * sizeof(u64)) != hipSuccess ||
+               hipDeviceSynchronize() != hipSuccess ||          // (the kernels run on non-blocking streams)
+               hipEventCreateWithFlags(&h->pat.done, hipEventDisableTiming) != hipSuccess) {
+      g_create_error = "initialising the Pattern line set failed";
+      rc = MPC_E_NODEVICE;
+    }
+  }
+  if (rc != MPC_OK) {
+    mpc_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return MPC_OK;
+}
+
+int mpc_pattern_distinct_lines(mpc_handle *h, uint64_t *n)
+{
+  if (!h || !n || h->algorithm != 5) return MPC_E_INVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = sync_all(h);
+  if (rc != MPC_OK) return rc;
+  HIPCHK(h, hipDeviceSynchronize());   // callers may have used their own streams
+  rc = pattern_status(h);
+  if (rc != MPC_OK) return rc;
+  u64 v = 0;
+  HIPCHK(h, hipMemcpy(&v, h->pat.set.ctl + MPC_PSET_DISTINCT, sizeof(v), hipMemcpyDeviceToHost));
+  *n = v;
+  return MPC_OK;
+}
+
 uint64_t mpc_sc2_sampling_lines(uint64_t num_lines)
 {
   // main.cpp:110-113: max(10000, min(numLines / 100, WARM_UP_CNT))
@@ -1272,6 +1422,12 @@ void mpc_destroy(mpc_handle *h)
   if (h->d_raw) (void)hipFree(h->d_raw);
   if (h->sc2.d_hash) (void)hipFree(h->sc2.d_hash);
   if (h->sc2.d_buckets) (void)hipFree(h->sc2.d_buckets);
+  if (h->pat.set.tags) (void)hipFree(h->pat.set.tags);
+  if (h->pat.set.store) (void)hipFree(h->pat.set.store);
+  if (h->pat.set.ctl) (void)hipFree(h->pat.set.ctl);
+  if (h->pat.set.pend_a) (void)hipFree(h->pat.set.pend_a);
+  if (h->pat.set.pend_b) (void)hipFree(h->pat.set.pend_b);
+  if (h->pat.done) (void)hipEventDestroy(h->pat.done);
   delete h;
 }
 
@@ -1282,9 +1438,9 @@ int mpc_get_info(const mpc_handle *h, mpc_info *info)
   info->algorithm = h->algorithm;
   info->line_size = h->L;
   info->num_modules = h->algorithm == 0 ? h->cfg.M : 0;
-  info->num_clusters = h->algorithm == 0 ? h->cfg.M + 1 : (h->algorithm == 1 ? 9 : (h->algorithm == 2 ? 8 : h->algorithm == 3 ? 7 : 2));
+  info->num_clusters = h->algorithm == 0 ? h->cfg.M + 1 : (h->algorithm == 1 ? 9 : (h->algorithm == 2 ? 8 : h->algorithm == 3 ? 7 : h->algorithm == 5 ? 10 : 2));
   info->hist_bins = h->algorithm == 0 ? h->cfg.hist_bins : 0;
-  info->kernel_path = h->algorithm == 4 ? MPC_PATH_SC2 : h->algorithm == 3 ? MPC_PATH_BPC : h->algorithm == 2 ? MPC_PATH_FPC
+  info->kernel_path = h->algorithm == 5 ? MPC_PATH_PATTERN : h->algorithm == 4 ? MPC_PATH_SC2 : h->algorithm == 3 ? MPC_PATH_BPC : h->algorithm == 2 ? MPC_PATH_FPC
                       : h->algorithm == 1 ? MPC_PATH_BDI : (h->route.kernel != VpcKernel::Generic ? MPC_PATH_VPC_FAST : MPC_PATH_VPC_GENERIC);
   info->device = h->device;
   info->stats_len = h->stats_len;
@@ -1322,6 +1478,7 @@ const char *mpc_kernel_form(const mpc_handle *h)
 {
   if (!h) return "";
   if (h->algorithm == 4) return h->sc2.built ? "table sizing" : "warm-up counting";
+  if (h->algorithm == 5) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled, then the set passes" : "run-time loop, then the set passes";
   if (h->algorithm != 0) return "unrolled";
   if (h->route.kernel == VpcKernel::AtCreation && h->jit.from_cache) return "unrolled, compiled at creation (from the cache)";
   static const char *const form[] = {"unrolled", "unrolled, general layout", "unrolled, compiled at creation", "run-time loop", "generic"};
@@ -1349,7 +1506,7 @@ int mpc_sync(mpc_handle *h)
   int rc = sync_all(h);
   if (rc != MPC_OK) return rc;
   HIPCHK(h, hipDeviceSynchronize());   // batches may have been queued on caller streams
-  return MPC_OK;
+  return pattern_status(h);
 }
 
 int mpc_compress_batch(mpc_handle *h, const uint8_t *lines, uint64_t n, uint16_t *sizes, int8_t *sel)
@@ -1574,7 +1731,7 @@ int mpc_group_sync(mpc_group *g)
   const int rc = group_finish(g);
   if (rc != MPC_OK) return rc;
   GHIPCHK(g, hipDeviceSynchronize());   // batches may have been queued on caller streams
-  return MPC_OK;
+  return group_members_status(g);
 }
 
 int mpc_stats_len(const mpc_handle *h, uint64_t *len)
@@ -1591,6 +1748,8 @@ int mpc_stats_get(mpc_handle *h, uint64_t *vec, size_t n)
   int rc = sync_all(h);
   if (rc != MPC_OK) return rc;
   HIPCHK(h, hipDeviceSynchronize());   // callers may have used their own streams
+  rc = pattern_status(h);
+  if (rc != MPC_OK) return rc;
   std::vector<u64> raw(h->raw_len);
   HIPCHK(h, hipMemcpy(raw.data(), h->d_raw, h->raw_len * sizeof(u64), hipMemcpyDeviceToHost));
   std::vector<u64> out(h->extra);

@@ -51,7 +51,7 @@ public:
   // ADDITIVE: bytes per line.  Default: the result object's LineSize (CompResult.h).
   virtual unsigned GetLineSize() { return m_Stat->LineSize; }
 
-  // ADDITIVE: the libmpc_hip handle behind a GPU evaluator (VPC, BDI, FPC, BPC, SC2), nullptr for every other
+  // ADDITIVE: the libmpc_hip handle behind a GPU evaluator (VPC, BDI, FPC, BPC, SC2, Pattern), nullptr for every other
   // compressor; lines waiting in the line buffer are evaluated first.  comp::CompressorSet (CompressorSet.h) feeds
   // its members through it.
   virtual mpc_handle *DeviceHandle() { return nullptr; }

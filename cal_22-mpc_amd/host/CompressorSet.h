@@ -19,7 +19,7 @@ namespace comp
 class CompressorSet
 {
 public:
-  // Members are borrowed and must outlive the set; every one must be a GPU evaluator (VPC, BDI, FPC, BPC, SC2) of the
+  // Members are borrowed and must outlive the set; every one must be a GPU evaluator (VPC, BDI, FPC, BPC, SC2, Pattern) of the
   // same line size.  Anything else is refused with a message (exit(1), as the evaluators' constructors do).
   explicit CompressorSet(const std::vector<Compressor *> &members);
   ~CompressorSet();

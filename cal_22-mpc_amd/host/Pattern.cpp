@@ -1,0 +1,134 @@
+#include "Pattern.h"
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+
+#include "mpc_hip.h"
+
+namespace comp
+{
+
+double PatternResult::ComputeEntropy(std::map<uint8_t, uint64_t> &symbolCounts)
+{
+  uint64_t sum = 0;
+  for (auto &kv : symbolCounts) sum += kv.second;
+  double entropy = 0;
+  for (auto &kv : symbolCounts) {
+    const double probability = (double)kv.second / (double)sum;
+    entropy += -probability * log2(probability);
+  }
+  return entropy;
+}
+
+void PatternResult::Print(std::string workloadName, std::string filePath)
+{
+  std::ofstream file;
+  if (filePath != "")
+    openForAppend(file, filePath,
+                  "Workload,Entropy [b/B],Entropy except AllZeros AllWordSame [b/B],Zeros [B],Repeated Line [B],"
+                  "Temporal Locality [B],B8D1-Implicit [B],B8D1-Explicit [B],B8D2-Implicit [B],B8D2-Explicit [B],"
+                  "B8D4-Implicit [B],B8D4-Explicit [B],B4D1-Implicit [B],B4D1-Explicit [B],B4D2-Implicit [B],"
+                  "B4D2-Explicit [B],B2D1-Implicit [B],B2D1-Explicit [B],Undefined [B],Total Size [B],\n");
+  std::ostream &stream = (filePath == "") ? std::cout : file;
+  stream << workloadName << "," << mpctext::num(ComputeEntropy(SymbolCounts)) << ","
+         << mpctext::num(ComputeEntropy(SymbolCountsExceptAllZerosAllWordSame)) << ",";
+  stream << Z << "," << R << "," << T << ",";
+  for (int i = 0; i < 6; i++) stream << ImplicitCounts[(size_t)i] << "," << ExplicitCounts[(size_t)i] << ",";
+  stream << U << "," << Total << "," << std::endl;
+}
+
+void PatternResult::LoadVector(const uint64_t *v)
+{
+  // CompResult::Update is never called by the reference's Pattern: the three CompResult numbers stay 0
+  OriginalSize = 0;
+  CompressedSize = 0;
+  CompRatio = 0;
+  Z = v[4];
+  R = v[5];
+  T = v[6];
+  U = v[7];
+  Total = v[8];
+  for (int i = 0; i < 6; i++) {
+    ImplicitCounts[(size_t)i] = v[9 + i];
+    ExplicitCounts[(size_t)i] = v[15 + i];
+  }
+  SymbolCounts.clear();
+  SymbolCountsExceptAllZerosAllWordSame.clear();
+  for (int b = 0; b < 256; b++) {
+    if (v[22 + b]) SymbolCounts[(uint8_t)b] = v[22 + b];
+    if (v[278 + b]) SymbolCountsExceptAllZerosAllWordSame[(uint8_t)b] = v[278 + b];
+  }
+}
+
+static void fail(const char *what, int rc, mpc_handle *h)
+{
+  const char *msg = mpc_last_error(h);
+  printf("%s (%d): %s\n", what, rc, msg ? msg : "");
+  exit(1);
+}
+
+Pattern::Pattern(unsigned lineSize) : m_Handle(nullptr), m_LineSize(lineSize)
+{
+  int rc = mpc_create_pattern(lineSize, -1, &m_Handle);
+  if (rc != MPC_OK) fail("Pattern: cannot create the evaluator", rc, nullptr);
+  m_Stat = new PatternResult(lineSize);
+  m_Stat->CompressorName = "Pattern Checker";
+}
+
+Pattern::~Pattern() { mpc_destroy(m_Handle); }
+
+unsigned Pattern::CompressLine(std::vector<uint8_t> &dataLine)
+{
+  if (dataLine.size() != m_LineSize) {
+    printf("Pattern: line of %zu bytes, expected %u.\n", dataLine.size(), m_LineSize);
+    exit(1);
+  }
+  if (LineBuffering()) {
+    BufferLine(dataLine);
+    return 0;
+  }
+  uint16_t bits = 0;
+  int rc = mpc_compress_batch(m_Handle, dataLine.data(), 1, &bits, nullptr);
+  if (rc != MPC_OK) fail("Pattern::CompressLine", rc, m_Handle);
+  return bits;
+}
+
+void Pattern::CompressBatch(const uint8_t *lines, unsigned long long n)
+{
+  FlushLines();
+  int rc = mpc_compress_batch(m_Handle, lines, n, nullptr, nullptr);
+  if (rc != MPC_OK) fail("Pattern::CompressBatch", rc, m_Handle);
+}
+
+unsigned long long Pattern::CompressFile(const std::string &tracePath)
+{
+  FlushLines();
+  uint64_t done = 0;
+  const bool isLog = tracePath.size() > 4 && tracePath.compare(tracePath.size() - 4, 4, ".log") == 0;
+  int rc = isLog ? mpc_compress_gpgpusim_log(m_Handle, tracePath.c_str(), nullptr, &done)
+                 : mpc_compress_npy(m_Handle, tracePath.c_str(), 0, ~0ull, 1, &done);
+  if (rc != MPC_OK) fail("Pattern::CompressFile", rc, m_Handle);
+  return done;
+}
+
+CompResult *Pattern::GetResult()
+{
+  FlushLines();
+  std::vector<uint64_t> v(534);
+  int rc = mpc_stats_get(m_Handle, v.data(), v.size());
+  if (rc != MPC_OK) fail("Pattern::GetResult", rc, m_Handle);
+  static_cast<PatternResult *>(m_Stat)->LoadVector(v.data());
+  return m_Stat;
+}
+
+unsigned long long Pattern::DistinctLines()
+{
+  FlushLines();
+  uint64_t n = 0;
+  int rc = mpc_pattern_distinct_lines(m_Handle, &n);
+  if (rc != MPC_OK) fail("Pattern::DistinctLines", rc, m_Handle);
+  return n;
+}
+
+}  // namespace comp

@@ -1,0 +1,60 @@
+// Pattern.h -- the dataset analyser behind the reference's class names (reference src/compressor/Pattern.h):
+// zero / repeated / already-seen / base-delta bytes and the byte entropy of a trace; evaluation on the MI355X via
+// libmpc_hip.so (mpc_create_pattern).  The counts come from the device, the two entropies are computed here from the
+// count maps, as the reference's Print does.  The reference's public m_DataCache member (its LRU of lines) has no
+// counterpart: the set of lines lives in device memory (DistinctLines() is its size).
+#ifndef MPC_HOST_PATTERN_H
+#define MPC_HOST_PATTERN_H
+
+#include <map>
+
+#include "CompResult.h"
+#include "Compressor.h"
+
+namespace comp
+{
+
+enum class PatternState {
+  Base8Delta1 = 0, Base8Delta2 = 1, Base8Delta4 = 2, Base4Delta1 = 3, Base4Delta2 = 4, Base2Delta1 = 5,
+  Zeros = 6, Repeat = 7, TemporalLocality = 8, NotDefined = 9,
+};
+
+struct PatternResult : public CompResult {
+  PatternResult(unsigned lineSize) : CompResult(lineSize), ImplicitCounts(6, 0), ExplicitCounts(6, 0), Z(0), R(0), T(0), U(0), Total(0) {}
+  // entropy = sum(-p * log2(p)) over the symbols of the map, ascending (Pattern.h:124-154)
+  double ComputeEntropy(std::map<uint8_t, uint64_t> &symbolCounts);
+  // the 22-column row (Pattern.h:156-217)
+  virtual void Print(std::string workloadName = "", std::string filePath = "");
+  // the statistics vector of a Pattern handle (mpc_hip.h); a symbol that never occurred has no map entry
+  void LoadVector(const uint64_t *vec);
+
+  std::vector<uint64_t> ImplicitCounts;
+  std::vector<uint64_t> ExplicitCounts;
+  std::map<uint8_t, uint64_t> SymbolCounts;
+  std::map<uint8_t, uint64_t> SymbolCountsExceptAllZerosAllWordSame;
+  uint64_t Z, R, T, U;   // Zeros, Repeated, TemporalLocality, NotDefined
+  uint64_t Total;
+};
+
+class Pattern : public Compressor
+{
+public:
+  Pattern(unsigned lineSize);
+  virtual ~Pattern();
+  virtual unsigned CompressLine(std::vector<uint8_t> &dataLine);
+  virtual CompResult *GetResult();
+  virtual void CompressBatch(const uint8_t *lines, unsigned long long n);
+  virtual unsigned long long CompressFile(const std::string &tracePath);
+  virtual unsigned GetLineSize() { return m_LineSize; }
+  virtual mpc_handle *DeviceHandle() { FlushLines(); return m_Handle; }
+  // lines in the set (at most 2^24 - 1: the reference evicts beyond that, this evaluator stops with an error)
+  unsigned long long DistinctLines();
+
+private:
+  mpc_handle *m_Handle;
+  unsigned m_LineSize;
+};
+
+}  // namespace comp
+
+#endif

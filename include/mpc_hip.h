@@ -47,13 +47,14 @@ typedef struct mpc_handle mpc_handle;
 #define MPC_PATH_FPC          4
 #define MPC_PATH_BPC          5
 #define MPC_PATH_SC2          6
+#define MPC_PATH_PATTERN      7
 
 typedef struct {
   int32_t abi_version;
-  int32_t algorithm;        /* 0 = VPC, 1 = BDI, 2 = FPC, 3 = BPC, 4 = SC2 */
+  int32_t algorithm;        /* 0 = VPC, 1 = BDI, 2 = FPC, 3 = BPC, 4 = SC2, 5 = Pattern */
   int32_t line_size;        /* bytes per line (L) */
   int32_t num_modules;      /* VPC: M; BDI: 0 */
-  int32_t num_clusters;     /* VPC: M+1 (cluster -1 .. M-1); BDI: 9 states; FPC: 8 prefixes; BPC: 7 patterns; SC2: 2 (warm-up, table) */
+  int32_t num_clusters;     /* VPC: M+1 (cluster -1 .. M-1); BDI: 9 states; FPC: 8 prefixes; BPC: 7 patterns; SC2: 2 (warm-up, table); Pattern: 10 states */
   int32_t hist_bins;        /* VPC: bins per cluster in the stats vector */
   int32_t kernel_path;      /* MPC_PATH_* */
   int32_t device;           /* HIP device ordinal the handle is bound to */
@@ -110,6 +111,24 @@ int mpc_sc2_code_lengths(const uint32_t *symbols, const uint64_t *freqs, size_t 
 /* The handle's code table in ascending symbol order: *n symbols (0 before line S has been seen); symbols and lengths
  * need room for *n entries (at most 1024).                                                                          */
 int mpc_sc2_table(mpc_handle *h, uint32_t *symbols, uint16_t *lengths, size_t cap, size_t *n);
+/* `new comp::Pattern(lineSize)` (Pattern.h:228-252): the reference's dataset analyser.  Per line of L bytes
+ * (Pattern.cpp:6-75): all bytes zero adds L to Z; all 4-byte words equal adds L to R (a zero line counts in both); an
+ * equal line seen before on this handle, in this or any earlier call, adds L to T, and otherwise the line joins the
+ * handle's set; the six base-delta scans B8D1 B8D2 B8D4 B4D1 B4D2 B2D1 run in that order and the first of the smallest
+ * sizes below 8 L is selected; the selected scan's immediates add their B bytes each to ImplicitCounts and its other
+ * values to ExplicitCounts, a line without a selection adds L to U; every byte is counted in SymbolCounts and, unless
+ * the line is all-zero or all-word-same, in SymbolCountsExceptAllZerosAllWordSame.  Per-line output: the smallest size
+ * + 4 bits (CompressLine's return value); `selected` is the PatternState, 0..5 or 9 (NotDefined).
+ * line_size: a multiple of 8 from 8 to 256 (the reference reads past the line otherwise); checked before any device is
+ * touched.  The set lives in device memory, sized at creation: (8 + line_size) x 2^25 bytes (2.25 GiB for 64-byte
+ * lines) plus 64 MiB of work lists.
+ * LIMIT the reference does not have: its LRU starts evicting when the 2^24-th distinct line arrives, and eviction is
+ * not modelled.  A handle takes 2^24 - 1 distinct lines.  The call that brings one more fails with MPC_E_INVAL (a call
+ * that does not wait for its lines, mpc_compress_batch_device, reports it at the next mpc_sync / mpc_stats_get); from
+ * then on the handle refuses lines and mpc_stats_get returns the same error.  A new trace needs a new handle.        */
+int mpc_create_pattern(unsigned line_size, int device, mpc_handle **out);
+/* Lines in the handle's set since creation (waits like mpc_sync; not cleared by mpc_stats_reset). */
+int mpc_pattern_distinct_lines(mpc_handle *h, uint64_t *n);
 void mpc_destroy(mpc_handle *h);
 
 int mpc_get_info(const mpc_handle *h, mpc_info *info);
@@ -171,6 +190,11 @@ int mpc_sync(mpc_handle *h);
  * SC2 layout: [0] lines [1] original_bits [2] compressed_bits [3] warm-up lines [4] table symbols
  *             [5] words found in the table.  mpc_stats_reset clears the statistics only: the table and the
  *             handle's line counter (which line is line S) stay.
+ * Pattern layout: [0] lines [1] 0 [2] 0 (CompResult::Update is never called: OriginalSize and CompressedSize stay 0)
+ *             [3] sum of the returned sizes [4] Z [5] R [6] T [7] U [8] Total, all in bytes [9..14] ImplicitCounts
+ *             [15..20] ExplicitCounts [21] lines that joined the set [22..277] SymbolCounts [278..533]
+ *             SymbolCountsExceptAllZerosAllWordSame.  T = L x ([0] - [21]).  mpc_stats_reset clears the statistics,
+ *             [21] included, and keeps the set: lines seen before the reset still count as seen.
  */
 int mpc_stats_len(const mpc_handle *h, uint64_t *len);
 int mpc_stats_get(mpc_handle *h, uint64_t *vec, size_t n);      /* syncs */
@@ -180,12 +204,13 @@ int mpc_stats_set(mpc_handle *h, const uint64_t *vec, size_t n);   /* = (after a
 /* Device-side exchange (multi-GPU without a host round trip).  The handle's device
  * accumulators ("raw" statistics: VPC [sum_r(K)] [sum_r2(K)] [histogram(K x B)], BDI
  * [Counts(9)] [compressed_bits], FPC [Counts(8)] [compressed_bits], BPC [Counts(7)] [TotalWords] [compressed_bits], SC2
- * [compressed_bits] [words_in_table]) are plain uint64 sums, so ranks may all-reduce them
+ * [compressed_bits] [words_in_table], Pattern: the 531 sums of csrc/mpc_pattern.h) are plain uint64 sums, so ranks may all-reduce them
  * directly: mpc_stats_copy_raw_device enqueues an asynchronous device-to-device copy of
  * the raw_len words into d_dst on hip_stream (after everything already enqueued there),
  * and mpc_stats_from_raw turns such an array -- on the host, e.g. after the all-reduce --
  * into the statistics vector described above (merged-in host statistics not included; SC2 takes [0], [1], [3] and
- * [4], which the host counts, from this handle). */
+ * [4], which the host counts, from this handle).  A Pattern handle covers ONE GPU: its set is per device, so T and [21] of
+ * two handles that each saw a part of a trace do not add up to those of the whole trace; every other entry does. */
 int mpc_stats_raw_len(const mpc_handle *h, uint64_t *raw_len);
 int mpc_stats_copy_raw_device(mpc_handle *h, void *d_dst, void *hip_stream);
 int mpc_stats_from_raw(const mpc_handle *h, const uint64_t *raw, size_t raw_len, uint64_t *vec, size_t n);
@@ -231,7 +256,8 @@ int mpc_gpgpusim_log_line_size(const char *log_path, uint32_t *line_size);
  * on the slot's stream, in member order.  Each member sees every line exactly as if it had been called alone and keeps
  * its own statistics: mpc_stats_get and everything else that takes the member's handle work as before.  BDI, FPC and
  * BPC members of 32-, 64- or 128-byte lines, when at least two of them are in the group, share one kernel that loads a
- * line once and evaluates all of them on it; every other member launches its own kernel (mpc_group_form).
+ * line once and evaluates all of them on it; every other member launches its own kernel (a Pattern member its own kernels: the
+ * analysis and the set passes) (mpc_group_form).
  * The group BORROWS the handles: destroy the group before its members.  A member stays usable on its own between group
  * calls.  One group is used from one thread at a time.                                                             */
 typedef struct mpc_group mpc_group;

@@ -64,6 +64,9 @@
 #ifndef MPC_JIT_WSHIFT
 #define MPC_JIT_WSHIFT 0
 #endif
+#ifndef MPC_DRAIN_WAIT
+#define MPC_DRAIN_WAIT 1   // development-only: 0 leaves the wait for the drain copy's loads to the compiler (see the drain loop)
+#endif
 #ifndef MPC_ABLATE
 #define MPC_ABLATE 0   // development-only timing ablations (tools/ablate.sh); results are WRONG when non-zero
 #endif
@@ -261,8 +264,20 @@ __device__ __forceinline__ u32 window_residue(const Lane<W> &c, int e, ctab_t t,
     // and the MSB of the predicted byte come from the pre-split masks t[3W..], t[4W..]
     const u32 p7 = ((b >> fm.rs2) & t[2 * W + k]) | (b & t[3 * W + k]);
     const u32 sub = (c.x[e] | H80) - p7;
-    const u32 w = c.x[e] ^ (b & t[4 * W + k]);          // bit 7: line ^ predicted
-    return FULL ? (sub ^ (~w & H80)) : (sub ^ ~w);
+    // bit 7: line ^ predicted.  Written as the two v_bitop3_b32 they are: left to the compiler, words 0 and 1 (whose
+    // table entries differ from the periodic ones) came out as separate and / xor chains, 10 instructions instead of 7
+    const u32 w = bitop3<(BO_A ^ (BO_B & BO_C))>(c.x[e], b, t[4 * W + k]);
+    return FULL ? bitop3<(BO_A ^ (BO_B & ~BO_C)) & 0xFFu>(sub, H80, w) : bitop3<(BO_A ^ ~BO_B) & 0xFFu>(sub, w, w);
+  } else if constexpr (lk_base(KIND) == MPC_FK_DIFF && !FULL) {
+    // MSB of line - (base + diff) without the predicted byte: with p7 = (b & 0x7f..) + c1 (bit 7 = the carry) the predicted
+    // byte is (p7 & 0x7f) | (p7 ^ b ^ c2) & 0x80, so bit 7 of msb_of_bsub(line, predicted) is that of
+    // ((line | 0x80..) - (p7 & 0x7f..)) ^ line ^ p7 ^ b ^ ~c2 -- six instructions instead of ten
+#if MPC_JIT_WSHIFT
+    if (fm.wgen) return msb_of_bsub(c.x[e], lane_weight_general<W>(b, fm.wgen - 1, e));
+#endif
+    const u32 p7 = (b & L7F) + t[W + k];
+    const u32 sub = (c.x[e] | H80) - (p7 & L7F);
+    return bitop3<(BO_A ^ BO_B ^ ~BO_C) & 0xFFu>(xor3(sub, c.x[e], p7), b, t[2 * W + k]);
   } else {
 #if MPC_JIT_WSHIFT
     const u32 pred = fm.wgen ? lane_weight_general<W>(b, fm.wgen - 1, e) : window_predict<lk_base(KIND)>(b, t[W + k], t[2 * W + k], fm);
@@ -375,6 +390,12 @@ __device__ __forceinline__ u32 lane_leading_zero_rows(const u32 (&r)[W], ctab_t 
   return (plane_mask == ~0u ? G : gf) ? NG * p + j_star : 2u * W;
 }
 
+// this lane's bit of a wave mask, as a condition: the mask IS the condition's register pair, no instruction is issued
+__device__ __forceinline__ bool lane_bit(u64 mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
+
+// NOTE: after lane_last (the last module alone) only r, pm and -- for ConsecutiveBase -- root_r are set; q, cx, encb and
+// the other kinds' root_r (0) are that module's constants, which lane_step takes from there (`last_only`).  Read them
+// through lane_step's selects, never from `best` directly.
 template <int W>
 struct LaneBest {
   u32 r[W];
@@ -537,6 +558,15 @@ __device__ __forceinline__ void lane_seq(const Lane<W> &c, const MpcVpcParams &P
   if constexpr (!last) lane_seq<W, NPT, Q + 1, REST...>(c, P, keep_bits, best, any_full);
 }
 
+// whether the last module of the sequence sets a residue at the root position (ConsecutiveBase)
+template <int... KINDS>
+__device__ __host__ constexpr bool lane_last_has_root_r()
+{
+  constexpr int n = sizeof...(KINDS);
+  constexpr int kinds[n > 0 ? n : 1] = {KINDS...};
+  return n > 0 && lk_base(kinds[n > 0 ? n - 1 : 0]) == MPC_FK_CONSEC;
+}
+
 // the last module alone (pass 1 ruled out every other module for the whole wave)
 template <int W, int NPT, int Q>
 __device__ __forceinline__ void lane_last(const Lane<W> &, const MpcVpcParams &, LaneBest<W> &) {}
@@ -545,12 +575,12 @@ template <int W, int NPT, int Q, int KIND, int... REST>
 __device__ __forceinline__ void lane_last(const Lane<W> &c, const MpcVpcParams &P, LaneBest<W> &best)
 {
   if constexpr (Q + 1 == NPT) {
-    lane_residue<W, KIND>(c, LANE_FM(Q), lane_tab(P), best.r, best.root_r);
+    // (only ConsecutiveBase has a residue of its own at the root position; the others' is 0, which lane_step knows)
+    u32 zero_root_r;
+    lane_residue<W, KIND>(c, LANE_FM(Q), lane_tab(P), best.r, lk_base(KIND) == MPC_FK_CONSEC ? best.root_r : zero_root_r);
     if (c.gen && LANE_FM(Q).root != 0) lane_root_to_front<W, W>(c, LANE_FM(Q).root, best.r);
-    best.q = Q;
-    best.cx = (u32)LANE_FM(Q).cx;
     best.pm = MPC_JIT_PLANES ? LANE_FM(Q).plane_mask : ~0u;
-    best.encb = (u32)P.enc_bits[P.start + Q + 1];
+    // (best.q, best.cx, best.encb: wave-uniform constants of this module, lane_step takes them from there)
   } else {
     lane_last<W, NPT, Q + 1, REST...>(c, P, best);
   }
@@ -988,7 +1018,6 @@ __device__ __forceinline__ void lane_step(const uint4 (&v)[W / 4], u32 line0, u3
   const u32 line = DRAIN ? dline : line0 + loff;
   const bool valid = DRAIN ? dvalid : (FULL ? true : (line < E.n_lines));
   const u64 valid_mask = (FULL && !DRAIN) ? ~0ull : __ballot(valid);
-  bool deferred = false;
   Lane<W> c;
   c.gen = GEN;
 #pragma unroll
@@ -997,20 +1026,32 @@ __device__ __forceinline__ void lane_step(const uint4 (&v)[W / 4], u32 line0, u3
   }
 
   // ---- AllZero / AllWordSame (VPC.cpp:332-364) ----
-  bool is_rep = false, is_zero = false;
+  // The per-line predicates of a group (zero, same, needs the modules, deferred, open, keeps its encoding) are kept as
+  // WAVE MASKS in scalar registers: the wave-uniform decisions are scalar compares of them, and a lane reads its own bit
+  // back (lane_bit: no instruction, the mask is used as the condition) only in the general tail.  The exit that random
+  // data takes -- every line of the group stays uncompressed -- needs no per-line flag, selector or size at all.
+  u64 zero_mask = 0, rep_mask = 0;
   if (__ballot(valid && c.x[1] == c.x[0])) {   // wave-uniform: otherwise no line of the wave can be either
     u32 diff = 0;
 #pragma unroll
     for (int e = 1; e < W; e++) diff |= c.x[e] ^ c.x[0];
-    is_rep = diff == 0;                       // every word equals word 0
-    is_zero = (diff | c.x[0]) == 0;
+    rep_mask = __ballot(valid && diff == 0);                       // every word equals word 0
+    zero_mask = __ballot(valid && (diff | c.x[0]) == 0);
   }
-  bool need = valid && !(is_zero || (P.has_aws && is_rep));
-  u64 need_mask = __ballot(need);
+  u64 need_mask = valid_mask & ~(zero_mask | (P.has_aws ? rep_mask : 0ull));
+  u64 defer_mask = 0;
 
-  int chosen = is_zero ? 0 : 1;
-  u32 size = is_zero ? E.enc_zero : E.enc_same;
   u32 sum_r = 0, sum_r2 = 0;        // residue statistics of this line (VPC.cpp:417-443)
+  // Selector and size of a line that needed the modules.  They have no initial value on purpose (it would be a vector move
+  // on every path that merges below, the all-uncompressed exit included) and are assigned only where some line needs the
+  // modules and the group does not take that exit.  Their ONLY reads are the two `need ? n_chosen : ...` / `need ? n_size :
+  // ...` selects of the tail: the conditional operator evaluates them for no lane whose `need` is false, and `need` is a
+  // bit of need_mask, so a group that skipped the assignment (need_mask == 0) reads them on no lane.  Keep it that way: any
+  // other read needs an initial value.
+  int n_chosen;
+  u32 n_size;
+  bool all_unc = false;             // wave-uniform: the group took the all-uncompressed exit
+  u32 key = 0;
 
   // truncated scan table (run-time loop only): per residue word the bits that are scanned
   ctab_t scan_mask = ((NPT == 0 || (GEN && P.plane_mask == ~0u)) && P.trunc_off >= 0) ? lane_tab(P) + P.trunc_off : nullptr;     // (byte-major: plane_mask is all ones)
@@ -1019,24 +1060,32 @@ __device__ __forceinline__ void lane_step(const uint4 (&v)[W / 4], u32 line0, u3
     c.b0 = c.x[0] & 0xffu;
     c.rootb = perm(c.x[0], c.x[0], 0u);
     LaneBest<W> best;
+    u32 keep_bits = 0;
     if constexpr (NPT > 0) {
-      u64 defer_mask = 0;
       const bool allow_defer = !DRAIN && E.defer_cap != 0u && qn + (u32)((NPT - 1) * MPC_DEFER_MAX) <= E.defer_cap;
-      u32 keep_bits = 0;
       if ((__ballot(lane_row0_min<W, NPT, 0, KINDS...>(c, P) != 0u) & need_mask) != need_mask)
-        keep_bits = lane_prefilters<W, NPT, 0, KINDS...>(c, P, need_mask, defer_mask, allow_defer, alt);
+        keep_bits = lane_prefilters<W, NPT, 0, KINDS...>(c, P, need_mask, defer_mask, allow_defer, alt);     // (takes the deferred lines out of need_mask)
       if (!DRAIN && defer_mask) {          // wave-uniform and rare: some lines leave for the queue
-        deferred = (defer_mask >> E.lane) & 1ull;
         const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(defer_mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)defer_mask, 0u));
-        if (deferred) E.defer_q[qn + rank] = line;
+        if (lane_bit(defer_mask)) E.defer_q[qn + rank] = line;
         qn += (u32)__popcll(defer_mask);
-        need = need && !deferred;
       }
       if (keep_bits == 0) lane_last<W, NPT, 0, KINDS...>(c, P, best);
       else lane_seq<W, NPT, 0, KINDS...>(c, P, keep_bits, best, false);
     } else {
       lane_seq_runtime<W>(c, P, best, scan_mask, need_mask);
     }
+    // only the last module was evaluated (wave-uniform): the winner's index, XOR flavour and id bits are that module's
+    // constants and stay in scalar registers; lane_last does not set them in `best`.  (The empty statement hides from the
+    // compiler that this is the condition of the branch above: it would otherwise turn the selects below back into
+    // vector moves at the end of lane_last, on the path of every incompressible group.  Results do not depend on it; should
+    // a compiler see through it, the cost is 3 vector moves per group -- profiles/hotpath_pmc_per_group.txt is the record
+    // to compare a new compiler's counters with.)
+    u32 kb = keep_bits;
+    asm volatile("" : "+s"(kb));
+    const bool last_only = NPT > 0 && kb == 0;
+    u32 last_cx = 0;
+    if constexpr (NPT > 0) last_cx = (u32)LANE_FM(NPT - 1).cx;
     // without any prediction module the empty scanned array encodes to 0 bits and the line is
     // reported uncompressed at that size (VPC.cpp:397-407 with an empty maxScanned)
     const bool no_pred = NPT == 0 && P.n_pred == 0;
@@ -1045,13 +1094,15 @@ __device__ __forceinline__ void lane_step(const uint4 (&v)[W / 4], u32 line0, u3
     // XOR stage of the winner, on bytes: b ^ (b >> 1), or b ^ 0x7f where the MSB is set;
     // column 0 untouched.  The flavour is usually the same for the whole wave.
     u32 t[W];
-    const u64 cx_mask = __ballot(best.cx != 0);
+    const u32 best_root_r = (last_only && !lane_last_has_root_r<KINDS...>()) ? 0u : best.root_r;
+    const u64 cx_mask = last_only ? (last_cx ? ~0ull : 0ull) : __ballot(best.cx != 0);
     if ((cx_mask & need_mask) == need_mask) {
 #pragma unroll
       for (int e = 0; e < W; e++) t[e] = best.r[e] ^ ((best.r[e] >> 1) & (e == 0 ? 0x7f7f7f00u : L7F));
     } else {
       // both flavours, selected per lane with bit masks (no divergence)
-      const u32 cx7 = best.cx ? L7F : 0u, ncx = best.cx ? 0u : ~0u;
+      const u32 bcx = last_only ? last_cx : best.cx;
+      const u32 cx7 = bcx ? L7F : 0u, ncx = bcx ? 0u : ~0u;
 #pragma unroll
       for (int e = 0; e < W; e++) {
         const u32 a = best.r[e] & H80;
@@ -1074,21 +1125,21 @@ __device__ __forceinline__ void lane_step(const uint4 (&v)[W / 4], u32 line0, u3
     // The certificate pays where it closes every line of the group (incompressible data); where the
     // previous group of this wave still had compressible lines it is skipped and the encoder runs
     // straight away (rs.enc_hot, wave-uniform).
-    bool open = need;
+    u64 open_mask = need_mask;
     const bool byte_major = (NPT == 0 && P.byte_major) || (MPC_JIT_BM && NPT > 0);    // (run-time loop: no certificate for that order)
-    if (!rs.enc_hot && !byte_major) open = need && !lane_certified<W>(t);
-    if (MPC_JIT_BM && NPT > 0 && !rs.enc_hot) open = need && !lane_certified_bm<W>(t);
+    if (!rs.enc_hot && !byte_major) open_mask &= ~__ballot(lane_certified<W>(t));
+    if (MPC_JIT_BM && NPT > 0 && !rs.enc_hot) open_mask &= ~__ballot(lane_certified_bm<W>(t));
     if constexpr (MPC_ABLATE & 16) {                  // timing ablation: the certificate stays, the compressible path is cut off
-      if (__ballot(open)) E.st.hist[0] = 1u;          // (keeps the certificate alive; results are wrong)
-      open = false;
+      if (open_mask) E.st.hist[0] = 1u;               // (keeps the certificate alive; results are wrong)
+      open_mask = 0;
     }
     u32 enc = uncomp;
-    if (__ballot(open)) {
+    u64 keep_mask = 0;
+    if (open_mask) {
       if (byte_major) enc = lane_encode_bm<W>(t);
       else enc = lane_encode<W>(t);
+      if (!no_pred) keep_mask = __ballot(enc < uncomp) & open_mask;             // VPC.cpp:397-407
     }
-    const bool keep = open && enc < uncomp && !no_pred;             // VPC.cpp:397-407
-    const u64 keep_mask = __ballot(keep);
     rs.enc_hot = keep_mask != 0;
 
     // residue statistics over all positions: the winner's residues (the root position
@@ -1099,7 +1150,8 @@ __device__ __forceinline__ void lane_step(const uint4 (&v)[W / 4], u32 line0, u3
       // one wave-uniform key, sums of the raw bytes
       if constexpr (MPC_ABLATE & 4) { sum_r = c.x[3]; sum_r2 = c.x[5]; }
       else byte_sums<W>(c.x, sum_r, sum_r2);
-      if (valid) lane_run_add(rs, unc_size, sum_r, sum_r2, E);       // cluster -1: key = size
+      all_unc = true;
+      key = unc_size;                                         // cluster -1: key = size
       if constexpr (OUT) {
         if (valid) {
           const u64 at = E.first_line + line;
@@ -1107,56 +1159,80 @@ __device__ __forceinline__ void lane_step(const uint4 (&v)[W / 4], u32 line0, u3
           if (E.sel_out) E.sel_out[at] = (int8_t)-1;
         }
       }
-      return;
-    }
-    if (keep_mask == need_mask) {
-      // every line that needed the modules keeps its encoding (wave-uniform; the usual case on compressible data): the
-      // winner's residues as they are, nothing to select
-      const u32 w0 = mask_sel(0xffu, best.root_r, best.r[0]);
-      u32 a0 = sum_bytes(w0, 0u), q0 = sum_sq_bytes(w0, 0u), a1 = 0, q1 = 0;
-#pragma unroll
-      for (int e = 1; e < W; e += 2) {
-        a1 = sum_bytes(best.r[e], a1);
-        q1 = sum_sq_bytes(best.r[e], q1);
-        if (e + 1 < W) {
-          a0 = sum_bytes(best.r[e + 1], a0);
-          q0 = sum_sq_bytes(best.r[e + 1], q0);
-        }
-      }
-      sum_r = a0 + a1;
-      sum_r2 = q0 + q1;
     } else {
-      u32 w[W];
-      const u32 km = keep ? ~0u : 0u;
+      const bool keep = lane_bit(keep_mask);
+      if (keep_mask == need_mask) {
+        // every line that needed the modules keeps its encoding (wave-uniform; the usual case on compressible data): the
+        // winner's residues as they are, nothing to select
+        const u32 w0 = mask_sel(0xffu, best_root_r, best.r[0]);
+        u32 a0 = sum_bytes(w0, 0u), q0 = sum_sq_bytes(w0, 0u), a1 = 0, q1 = 0;
 #pragma unroll
-      for (int e = 0; e < W; e++) w[e] = mask_sel(km, best.r[e], c.x[e]);
-      w[0] = mask_sel(km & 0xffu, best.root_r, w[0]);
-      byte_sums<W>(w, sum_r, sum_r2);
+        for (int e = 1; e < W; e += 2) {
+          a1 = sum_bytes(best.r[e], a1);
+          q1 = sum_sq_bytes(best.r[e], q1);
+          if (e + 1 < W) {
+            a0 = sum_bytes(best.r[e + 1], a0);
+            q0 = sum_sq_bytes(best.r[e + 1], q0);
+          }
+        }
+        sum_r = a0 + a1;
+        sum_r2 = q0 + q1;
+      } else {
+        u32 w[W];
+        const u32 km = keep ? ~0u : 0u;
+#pragma unroll
+        for (int e = 0; e < W; e++) w[e] = mask_sel(km, best.r[e], c.x[e]);
+        w[0] = mask_sel(km & 0xffu, best_root_r, w[0]);
+        byte_sums<W>(w, sum_r, sum_r2);
+      }
+      const bool need = lane_bit(need_mask);
+      sum_r = need ? sum_r : 0u;
+      sum_r2 = need ? sum_r2 : 0u;
+      if (keep_mask) {     // (wave-uniform)
+        u32 last_encb = 0;
+        if constexpr (NPT > 0) last_encb = (u32)P.enc_bits[P.start + NPT];
+        n_chosen = keep ? P.start + (last_only ? NPT - 1 : best.q) : -1;
+        n_size = keep ? enc + (last_only ? last_encb : best.encb) : unc_size;
+      } else {
+        n_chosen = -1;
+        n_size = unc_size;
+      }
     }
-    sum_r = need ? sum_r : 0u;
-    sum_r2 = need ? sum_r2 : 0u;
-    if (need) {
-      chosen = keep ? P.start + best.q : -1;
-      size = keep ? enc + best.encb : unc_size;
+  }
+
+  if (!all_unc) {
+    // a deferred line is counted when it is drained; here it goes to a spare histogram slot behind
+    // the last cluster (index K * bins, never flushed), which keeps EXEC whole
+    const bool is_zero = lane_bit(zero_mask), need = lane_bit(need_mask), deferred = !DRAIN && lane_bit(defer_mask);
+    const int chosen = need ? n_chosen : (is_zero ? 0 : 1);
+    const u32 size = need ? n_size : (is_zero ? E.enc_zero : E.enc_same);
+    key = ((u32)(chosen + 1) << 16) | size;
+    if (!DRAIN) key = deferred ? ((u32)E.K << 16) : key;
+
+    // ---- per-line outputs (parity mode) ----
+    if constexpr (OUT) {
+      if (valid && !deferred) {
+        const u64 at = E.first_line + line;
+        if (E.sizes_out) E.sizes_out[at] = (uint16_t)size;
+        if (E.sel_out) E.sel_out[at] = (int8_t)chosen;
+      }
     }
   }
 
   // ---- statistics: run-length per lane ----
-  // a deferred line is counted when it is drained; here it goes to a spare histogram slot behind
-  // the last cluster (index K * bins, never flushed), which keeps EXEC whole
-  u32 key = ((u32)(chosen + 1) << 16) | size;
-  if (!DRAIN) key = deferred ? ((u32)E.K << 16) : key;
-  if (valid) lane_run_add(rs, key, sum_r, sum_r2, E);
-
-  // ---- per-line outputs (parity mode) ----
-  if constexpr (OUT) {
-    if (valid && !deferred) {
-      const u64 at = E.first_line + line;
-      if (E.sizes_out) E.sizes_out[at] = (uint16_t)size;
-      if (E.sel_out) E.sel_out[at] = (int8_t)chosen;
-    }
+  if (FULL && !DRAIN && __ballot(key != rs.key) == 0) {
+    // no lane's run ends here (one ballot; always so on incompressible data, whose key is wave-uniform): three additions
+    rs.cnt++;
+    rs.acc_r += sum_r;
+    rs.acc_r2 += sum_r2;
+  } else if (valid) {
+    lane_run_add(rs, key, sum_r, sum_r2, E);
   }
 }
+
+// s_waitcnt immediate on gfx9 / gfx950: vmcnt = bits 3:0 and 15:14, expcnt = bits 6:4, lgkmcnt = bits 11:8.
+// vmcnt(0) with the other two counters at their maxima (7, 15), i.e. not waited for: 0x0F70.
+constexpr int kWaitVm0 = (7 << 4) | (15 << 8);
 
 template <int NQ>
 __device__ __forceinline__ void lane_fetch(uint4 (&v)[NQ], const uint4 *__restrict__ lines, u32 line, u32 n_lines)
@@ -1322,7 +1398,9 @@ __device__ __forceinline__ void vpc_lane_body(unsigned char *smem, const uint4 *
       request(cb, 0u);
       request(cb, 1u);
     }
-    bool paired = false;            // wave-uniform: this block is evaluated as even lines / odd lines
+    // wave-uniform: this block is evaluated as even lines / odd lines.  (A u32, not a bool: uni() of a boolean first makes it
+    // a vector register again -- v_cndmask + v_readfirstlane on every group.)
+    u32 paired = 0;
     u32 pair_left = 0;
     bool tail_done = false;
     for (;;) {
@@ -1330,7 +1408,7 @@ __device__ __forceinline__ void vpc_lane_body(unsigned char *smem, const uint4 *
         cb = uni(cb);
         qn = uni(qn);
         iter = uni(iter);
-        const bool pair_now = uni(paired);
+        const u32 pair_now = uni(paired);
         const u32 nb = claim();                          // the wave's next block (the counter's latency hides behind the waits)
         for (u32 h = 0; h < 2u; h = uni(h + 1u)) {
           // ---- the group's lines: wait for its request, read it out one line per lane, refill what is free ----
@@ -1345,7 +1423,7 @@ __device__ __forceinline__ void vpc_lane_body(unsigned char *smem, const uint4 *
           } else {
             // requests complete in issue order (stage 0, then stage 1): the wanted one has landed when at most the NQ
             // instructions of the one request issued after it are outstanding
-            if (uni(h == 0u || nb != kNone)) ring_wait_vm<NQ>();
+            if (h == 0u || nb != kNone) ring_wait_vm<NQ>();       // (h and nb are scalars)
             else ring_wait_vm<0>();
             a0 = rd0 + h * SB;
           }
@@ -1381,11 +1459,11 @@ __device__ __forceinline__ void vpc_lane_body(unsigned char *smem, const uint4 *
         if (MPC_TESTING && E.lane == 0) route_add(routes, pair_now ? MPC_RT_VPC_PAIRED_BLOCKS : MPC_RT_VPC_PLAIN_BLOCKS, 1u);
         if (paired) {
           if (--pair_left == 0u) {                     // probe with plain groups
-            paired = false;
+            paired = 0u;
             if (MPC_TESTING && E.lane == 0) route_add(routes, MPC_RT_VPC_TO_PLAIN, 1u);
           }
         } else if (alt) {
-          paired = true;
+          paired = 1u;
           pair_left = kPairProbe;
           if (MPC_TESTING && E.lane == 0) route_add(routes, MPC_RT_VPC_TO_PAIRED, 1u);
         }
@@ -1418,6 +1496,12 @@ __device__ __forceinline__ void vpc_lane_body(unsigned char *smem, const uint4 *
           break;
         }
         lane_fetch<NQ>(va, lines, dline, n_lines);
+        // The loads are waited for HERE, all of them (vmcnt(0), the other counters untouched).  Left to the compiler, the wait
+        // sits at the first use of each register -- and a group that ends early (no valid line needs the modules) uses only
+        // the first two words: the compiler then carries "a load into va may be pending" back into the streaming loop and
+        // puts an s_waitcnt vmcnt(0) of its own in front of the ring's read-out there, on every group, which makes the
+        // counted waits (ring_wait_vm<NQ>) dead: a group would wait for the refill requested one group earlier.
+        if constexpr (MPC_DRAIN_WAIT) __builtin_amdgcn_s_waitcnt(kWaitVm0);
         lane_step<W, OUT, GEN, false, true, KINDS...>(va, 0u, 0u, dline, dvalid, P, E, rs, qn, alt);
       }
       if (tail_mine) tail_done = true;

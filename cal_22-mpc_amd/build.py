@@ -40,6 +40,19 @@ def _sources(d: str):
     return out
 
 
+def lib_units(csrc: str = CSRC):
+    """The translation units of the library as (source, object name, extra flags); tools/ab.py links its variants from
+    the same list (csrc: the sources of another tree, a saved baseline)."""
+    lane = os.path.join(csrc, "mpc_vpc_lane.hip")
+    units = [(lane, f"lane_w{w}.o", [f"-DMPC_LANE_W={w}"]) for w in (16, 32, 8, 0)]
+    units += [(os.path.join(csrc, "mpc_kernels.hip"), "kernels.o", []),
+              (os.path.join(csrc, "mpc_kernels.hip"), "baselines.o", ["-DMPC_BASELINES_UNIT=1"]),      # the group's shared kernel
+              (os.path.join(csrc, "mpc_sc2.hip"), "sc2.o", []),
+              (os.path.join(csrc, "mpc_pattern.hip"), "pattern.o", []),
+              (os.path.join(csrc, "mpc_capi.hip"), "capi.o", [])]
+    return units
+
+
 def build_lib(force: bool = False, verbose: bool = False, test: bool = False) -> str:
     """libmpc_hip.so (test=True: libmpc_hip_test.so, the same sources with -DMPC_TESTING=1).  The translation units
     are compiled in parallel: the lane kernel file once per line size (-DMPC_LANE_W=8/16/32) plus its dispatcher
@@ -50,13 +63,7 @@ def build_lib(force: bool = False, verbose: bool = False, test: bool = False) ->
         return LIB
     objdir = os.path.join(HERE, "obj_test" if test else "obj")
     os.makedirs(objdir, exist_ok=True)
-    lane = os.path.join(CSRC, "mpc_vpc_lane.hip")
-    units = [(lane, f"lane_w{w}.o", [f"-DMPC_LANE_W={w}"]) for w in (16, 32, 8, 0)]
-    units += [(os.path.join(CSRC, "mpc_kernels.hip"), "kernels.o", []),
-              (os.path.join(CSRC, "mpc_kernels.hip"), "baselines.o", ["-DMPC_BASELINES_UNIT=1"]),      # the group's shared kernel
-              (os.path.join(CSRC, "mpc_sc2.hip"), "sc2.o", []),
-              (os.path.join(CSRC, "mpc_pattern.hip"), "pattern.o", []),
-              (os.path.join(CSRC, "mpc_capi.hip"), "capi.o", [])]
+    units = lib_units()
     tflag = ["-DMPC_TESTING=1"] if test else []
     procs = []
     for src, obj, extra in units:

@@ -1,5 +1,5 @@
-// mpc_capi.hip -- the C ABI of include/mpc_hip.h: handles, the pinned
-// double-buffered host->device stager, .npy streaming, statistics.
+// mpc_capi.hip -- the C ABI of include/mpc_hip.h: handles and groups, which kernel a handle launches, statistics.
+// The staging pipeline behind the host-buffer and file calls is mpc_stage.h, the trace files mpc_trace_files.h.
 //
 // There is no CPU evaluation path in this library: every size it reports was
 // computed by a gfx950 kernel in mpc_kernels.hip.
@@ -10,20 +10,15 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <system_error>
-#include <thread>
 #include <vector>
 
 #include "../../include/mpc_hip.h"
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include "mpc_config.h"
 #include "mpc_device.h"
 #include "mpc_sc2.h"
 #include "mpc_pattern.h"
+#include "mpc_launch.h"
 
 // libmpc_hip_test.so (build.py, -DMPC_TESTING=1): route counters behind the raw statistics and a cap on the launch grid,
 // see mpc_kernel_common.h.  Must agree with the kernels' translation units.
@@ -35,49 +30,39 @@ constexpr size_t kRouteWords = MPC_TESTING ? 16 : 0;
 typedef unsigned long long u64;
 
 #include "mpc_jit.h"
+#include "mpc_stage.h"
 
-extern "C" {
-hipError_t mpc_launch_vpc_generic(const void *, u64, const MpcVpcParams *, uint16_t *, int8_t *, u64 *, int, hipStream_t);
-hipError_t mpc_launch_bdi(const void *, u64, int, uint16_t *, int8_t *, u64 *, int, hipStream_t);
-hipError_t mpc_launch_fpc(const void *, u64, int, uint16_t *, int8_t *, u64 *, int, hipStream_t);
-hipError_t mpc_launch_bpc(const void *, u64, int, uint16_t *, int8_t *, u64 *, int, hipStream_t);
-hipError_t mpc_launch_baselines(const void *, u64, int, const MpcBaselinesArgs *, int, hipStream_t);
-hipError_t mpc_launch_synth(void *, u64, unsigned, int, u64, u64, const uint32_t *, hipStream_t);
-hipError_t mpc_launch_read_probe(const void *, u64, uint32_t *, int, hipStream_t);
-hipError_t mpc_launch_vpc_lane(const void *, u64, const MpcVpcParams *, uint16_t *, int8_t *, u64 *, int, hipStream_t);
-hipError_t mpc_launch_vpc_lane_jit(hipFunction_t, hipFunction_t, const void *, u64, const MpcVpcParams *, uint16_t *, int8_t *, u64 *, int,
-                                   hipStream_t);
-size_t mpc_vpc_lane_smem(const MpcVpcParams *);
-int mpc_vpc_lane_unrolled(const MpcVpcParams *);
-size_t mpc_vpc_generic_smem(const MpcVpcParams *);
-hipError_t mpc_launch_sc2_count(const void *, u64, int, u64 *, u64, uint16_t *, int8_t *, u64 *, hipStream_t);
-hipError_t mpc_launch_sc2_hist(const u64 *, u64, u64, int, uint32_t *, int, hipStream_t);
-hipError_t mpc_launch_sc2_collect(const u64 *, u64, u64, u64 *, uint32_t *, int, hipStream_t);
-hipError_t mpc_launch_sc2_size(const void *, u64, int, const MpcSc2Table *, uint16_t *, int8_t *, u64 *, int, hipStream_t);
-hipError_t mpc_launch_pattern(const void *, u64, int, uint16_t *, int8_t *, u64 *, int, hipStream_t);
-hipError_t mpc_launch_pattern_set(const void *, uint32_t, int, const MpcPatternSet *, u64 *, int, hipStream_t);
-}
+using mpcstage::Sink;
+using mpcstage::Stager;
 
 namespace {
 
 thread_local std::string g_create_error;
 
-// staging: two slots, each a pinned host buffer + device buffer + stream
-constexpr size_t kStageBytes = 64ull << 20;   // per slot
-constexpr size_t kMiniLines = 512;            // batches up to this many lines take the small path
+// The ABI's algorithm numbers (mpc_info.algorithm) and, per algorithm, the facts that do not depend on a handle.
+enum class Algo { VPC, BDI, FPC, BPC, SC2, Pattern };
 
-struct Slot {
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;
-  uint8_t *h_in = nullptr;       // pinned
-  uint8_t *d_in = nullptr;
-  uint16_t *d_sizes = nullptr, *h_sizes = nullptr;
-  int8_t *d_sel = nullptr, *h_sel = nullptr;
-  uint16_t *user_sizes = nullptr;  // where the pending results go
-  int8_t *user_sel = nullptr;
-  u64 pending_lines = 0;
-  bool busy = false;
+struct AlgoFacts {
+  const char *name;                        // in a group's form and error texts
+  const char *label;                       // in the refusal of a line size
+  u64 raw_len, stats_len;                  // device raw statistics, ABI statistics vector (VPC computes its own from the configuration)
+  int clusters;                            // mpc_info.num_clusters (VPC: modules + 1)
+  int path;                                // mpc_info.kernel_path (VPC: MPC_PATH_VPC_GENERIC when routed there)
+  unsigned min_line, multiple, max_line;   // line sizes a handle is created for (VPC: the configuration's checks)
 };
+constexpr AlgoFacts kAlgo[] = {
+  {"VPC", "VPC", 0, 0, 0, MPC_PATH_VPC_FAST, 0, 0, 0},
+  // BDI.cpp:8 takes any dataLine.size(); values are 8, 4 and 2 bytes wide, so a multiple of 8
+  {"BDI", "BDI", MPC_BDI_RAW_LEN, 12, 9, MPC_PATH_BDI, 8, 8, MPC_MAX_LINE},
+  {"FPC", "FPC", MPC_FPC_RAW_LEN, 11, 8, MPC_PATH_FPC, 4, 4, MPC_MAX_LINE},
+  // 32-bit words; a plane has one bit per delta and is held in an int32_t (BPC.cpp:53-63): 2..32 words
+  {"BPC", "BPC", MPC_BPC_RAW_LEN, 11, 7, MPC_PATH_BPC, 8, 4, 128},
+  {"SC2", "SC2", MPC_SC2_RAW_LEN, 6, 2, MPC_PATH_SC2, 4, 4, MPC_MAX_LINE},
+  // 8-, 4- and 2-byte values (Pattern.cpp:26-58): a multiple of 8, or checkPattern reads past the line
+  {"PATTERN", "Pattern", MPC_PATTERN_RAW_LEN, 534, 10, MPC_PATH_PATTERN, 8, 8, MPC_MAX_LINE},
+};
+constexpr const AlgoFacts &facts(Algo a) { return kAlgo[(int)a]; }
+const char *algorithm_name(Algo a) { return facts(a).name; }
 
 // the kernel a VPC configuration runs (route_vpc), and why it is the generic one
 enum class VpcKernel { BuiltIn, BuiltInGeneral, AtCreation, RuntimeLoop, Generic };
@@ -86,7 +71,7 @@ struct VpcRoute { VpcKernel kernel = VpcKernel::Generic; std::string why_generic
 }  // namespace
 
 struct mpc_handle {
-  int algorithm = 0;   // 0 VPC, 1 BDI, 2 FPC, 3 BPC, 4 SC2, 5 Pattern
+  Algo algorithm = Algo::VPC;
   int device = 0;
   int L = 0;
   int num_cus = 256;
@@ -101,13 +86,7 @@ struct mpc_handle {
   u64 raw_len = 0;
   std::vector<u64> extra;        // merged-in statistics (ABI layout)
   u64 stats_len = 0;
-  Slot slots[2];
-  bool slots_ready = false;
-  size_t stage_lines = 0;
-  // small batches (the per-line CompressLine of the reference's interface above all): one pinned,
-  // device-visible buffer the kernel reads the lines from and writes the results to directly --
-  // no staging copies, no 64 MiB slots; a call is one launch and one stream synchronisation
-  uint8_t *mini = nullptr;       // [kMiniLines * L] lines | [kMiniLines] uint16 sizes | [kMiniLines] int8 clusters
+  Stager stage;                  // one member: this handle (mpc_stage.h); nothing of it exists before the first host-buffer call
   mpcjit::Kernels jit;           // VPC: the unrolled kernels compiled at creation (mpc_jit.h; route AtCreation)
   // SC2: lines 0 .. S-1 of the trace (counted across calls) are warm-up lines, the table is built when line S arrives
   struct {
@@ -130,37 +109,15 @@ struct mpc_handle {
     bool recorded = false;
     bool over = false;           // a line beyond the capacity arrived: the handle takes no more lines
   } pat;
-  std::vector<hipStream_t> group_streams;   // the slot streams of the groups this handle is a member of (sc2_build waits for them)
+  std::vector<Stager *> fed_by;  // every stager that feeds this handle: its own, then those of the groups it is a member of (sc2_build)
   std::string error;
 };
 
-namespace {
-
-// a group's staging slot: the chunk is copied once, every member's launch follows on the slot's stream
-struct GroupSlot {
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;
-  uint8_t *h_in = nullptr;       // pinned
-  uint8_t *d_in = nullptr;
-  // per member, allocated when a call first asks for that member's per-line output
-  std::vector<uint16_t *> d_sizes, h_sizes, user_sizes;
-  std::vector<int8_t *> d_sel, h_sel, user_sel;
-  u64 pending_lines = 0;
-  bool busy = false;
-};
-
-}  // namespace
-
 struct mpc_group {
   std::vector<mpc_handle *> m;   // borrowed, in the caller's order
-  int device = 0;
-  int L = 0;
   int shared[3] = {-1, -1, -1};  // member index of the BDI, FPC, BPC handle that baselines_kernel evaluates (all -1: no shared launch)
   int first_shared = -1;         // ... the first of them in member order: where the shared launch is enqueued
-  GroupSlot slots[2];            // the streams and events exist from creation, the buffers from the first staged call
-  bool slots_ready = false;
-  size_t stage_lines = 0;
-  uint8_t *mini = nullptr;       // [kMiniLines * L] lines | per member [kMiniLines] uint16 | per member [kMiniLines] int8
+  Stager stage;                  // m.size() members; its streams and events exist from creation (the members' fed_by), the rest as for a handle
   std::string form, error;
 };
 
@@ -172,12 +129,41 @@ int set_err(mpc_handle *h, int code, const std::string &msg)
   return code;
 }
 
-#define HIPCHK(h, call)                                                                         \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess)                                                                       \
-      return set_err((h), MPC_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));        \
-  } while (0)
+int group_err(mpc_group *g, int code, const std::string &msg)
+{
+  if (g) g->error = msg; else g_create_error = msg;
+  return code;
+}
+
+// The two sinks of the stager (mpc_stage.h), which HIPCHK reports through as well: set_err and group_err are the two
+// places a message lands.
+int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
+int pattern_status(mpc_handle *h);
+int group_launch(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, hipStream_t s);
+int group_members_status(mpc_group *g);
+
+Sink sink_of(mpc_handle *h)
+{
+  return {h,
+          [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, hipStream_t s) {
+            return launch(static_cast<mpc_handle *>(c), d, n, ds ? ds[0] : nullptr, dl ? dl[0] : nullptr, s);
+          },
+          [](void *c, int code, const std::string &msg) { return set_err(static_cast<mpc_handle *>(c), code, msg); },
+          [](void *c) { return pattern_status(static_cast<mpc_handle *>(c)); }};
+}
+
+Sink sink_of(mpc_group *g)
+{
+  return {g,
+          [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, hipStream_t s) {
+            return group_launch(static_cast<mpc_group *>(c), d, n, ds, dl, s);
+          },
+          [](void *c, int code, const std::string &msg) { return group_err(static_cast<mpc_group *>(c), code, msg); },
+          [](void *c) { return group_members_status(static_cast<mpc_group *>(c)); }};
+}
+
+// a handle's slots retired, its own stream idle, Pattern's capacity checked
+int sync_all(mpc_handle *h) { return mpcstage::finish(h->stage, sink_of(h), h->stream); }
 
 int pick_device(int device, int *out, int *cus)
 {
@@ -214,6 +200,8 @@ int finish_create(mpc_handle *h)
       hipStreamSynchronize(h->stream) != hipSuccess)
     return set_err(nullptr, MPC_E_NODEVICE, "hipMemset(stats) failed");
   h->extra.assign(h->stats_len, 0);
+  mpcstage::init(h->stage, h->device, h->L, 1);
+  h->fed_by.assign(1, &h->stage);
   return MPC_OK;
 }
 
@@ -253,7 +241,7 @@ int create_vpc_from_text(const std::string &text, int device, mpc_handle **out)
     return rc;
   }
   mpc::build_vpc_plan(h->cfg, h->plan);
-  h->algorithm = 0;
+  h->algorithm = Algo::VPC;
   h->L = h->cfg.L;
   const int K = h->cfg.M + 1;
   h->raw_len = mpc_vpc_raw_len(K, h->cfg.hist_bins);
@@ -301,67 +289,6 @@ int create_vpc_from_text(const std::string &text, int device, mpc_handle **out)
   return MPC_OK;
 }
 
-// Staging copies (caller's buffer -> pinned slot) are memory-bandwidth work on the host: one
-// thread moves ~12-24 GB/s, less than the PCIe link takes, so large copies are split over a
-// few threads.
-constexpr size_t kCopySlice = 8u << 20;
-constexpr unsigned kCopyThreads = 4;
-
-void parallel_copy(void *dst, const void *src, size_t bytes)
-{
-  const size_t want = (bytes + kCopySlice - 1) / kCopySlice;
-  unsigned hw = std::thread::hardware_concurrency();
-  if (hw == 0) hw = 1;
-  const unsigned nt = (unsigned)std::min<size_t>(std::min<size_t>(want, kCopyThreads), hw);
-  if (nt <= 1) { std::memcpy(dst, src, bytes); return; }
-  const size_t per = ((bytes + nt - 1) / nt + 63) & ~(size_t)63;
-  std::vector<std::thread> th;
-  for (unsigned i = 0; i < nt; i++) {
-    const size_t off = (size_t)i * per;
-    if (off >= bytes) break;
-    const size_t n = std::min(per, bytes - off);
-    // (no exception may leave the library: a thread that cannot be started -- the host's thread limit -- copies here instead)
-    try {
-      th.emplace_back([=]() { std::memcpy((char *)dst + off, (const char *)src + off, n); });
-    } catch (const std::system_error &) {
-      std::memcpy((char *)dst + off, (const char *)src + off, n);
-    }
-  }
-  for (auto &t : th) t.join();
-}
-
-// the same for page cache -> pinned slot; false on a short read / error
-bool parallel_pread(int fd, void *dst, size_t bytes, u64 file_off)
-{
-  const size_t want = (bytes + kCopySlice - 1) / kCopySlice;
-  unsigned hw = std::thread::hardware_concurrency();
-  if (hw == 0) hw = 1;
-  const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(want, kCopyThreads), hw));
-  const size_t per = ((bytes + nt - 1) / nt + 4095) & ~(size_t)4095;
-  std::vector<int> ok(nt, 1);
-  auto work = [&](unsigned i) {
-    size_t off = (size_t)i * per;
-    const size_t end = std::min(bytes, off + per);
-    while (off < end) {
-      const ssize_t got = pread(fd, (char *)dst + off, end - off, (off_t)(file_off + off));
-      if (got <= 0) { ok[i] = 0; return; }
-      off += (size_t)got;
-    }
-  };
-  std::vector<std::thread> th;
-  for (unsigned i = 1; i < nt; i++) {
-    try {
-      th.emplace_back(work, i);
-    } catch (const std::system_error &) {
-      work(i);          // (the host's thread limit: read this part here)
-    }
-  }
-  work(0);
-  for (auto &t : th) t.join();
-  for (int v : ok) if (!v) return false;
-  return true;
-}
-
 // Workgroups per CU of the grid-stride VPC and BDI kernels.  2-8 are resident; a grid of 32 per
 // CU lets CUs that finish early pick up more work (same-box A/B against 8 per CU: VPC random
 // -3.5 %, mixed -5 %, 128-byte lines -9 %, all-zero traces +3 %; BDI random -8 %, pointers -10 %).
@@ -390,39 +317,40 @@ int launch_pattern(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes,
 int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s)
 {
   if (n == 0) return MPC_OK;
-  if (h->algorithm == 4) return launch_sc2(h, d_lines, n, d_sizes, d_sel, s);
-  if (h->algorithm == 5) return launch_pattern(h, d_lines, n, d_sizes, d_sel, s);
   hipError_t e;
-  if (h->algorithm == 3) {
-    e = mpc_launch_bpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
-  } else if (h->algorithm == 2) {
-    e = mpc_launch_fpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
-  } else if (h->algorithm == 1) {
-    e = mpc_launch_bdi(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
-  } else if (h->route.kernel == VpcKernel::AtCreation) {
-    e = mpc_launch_vpc_lane_jit(h->jit.stats, h->jit.lines, d_lines, n, &h->params, d_sizes, d_sel, h->d_raw,
-                                grid_for(h, n, 256, kWgPerCu), s);
-  } else if (h->route.kernel == VpcKernel::Generic) {
-    e = mpc_launch_vpc_generic(d_lines, n, &h->params, d_sizes, d_sel, h->d_raw, grid_for(h, n, 128, 8), s);
-  } else {     // built in or the run-time module loop: the lane launcher finds which
-    e = mpc_launch_vpc_lane(d_lines, n, &h->params, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
+  switch (h->algorithm) {
+  case Algo::SC2: return launch_sc2(h, d_lines, n, d_sizes, d_sel, s);
+  case Algo::Pattern: return launch_pattern(h, d_lines, n, d_sizes, d_sel, s);
+  case Algo::BPC: e = mpc_launch_bpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
+  case Algo::FPC: e = mpc_launch_fpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
+  case Algo::BDI: e = mpc_launch_bdi(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
+  default:
+    if (h->route.kernel == VpcKernel::AtCreation) {
+      e = mpc_launch_vpc_lane_jit(h->jit.stats, h->jit.lines, d_lines, n, &h->params, d_sizes, d_sel, h->d_raw,
+                                  grid_for(h, n, 256, kWgPerCu), s);
+    } else if (h->route.kernel == VpcKernel::Generic) {
+      e = mpc_launch_vpc_generic(d_lines, n, &h->params, d_sizes, d_sel, h->d_raw, grid_for(h, n, 128, 8), s);
+    } else {     // built in or the run-time module loop: the lane launcher finds which
+      e = mpc_launch_vpc_lane(d_lines, n, &h->params, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s);
+    }
   }
   if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   return MPC_OK;
 }
 
 // SC2: the code table from the warm-up counts.  The one blocking point of an SC2 handle: every stream that may still
-// run a warm-up count (the call's, the handle's, both staging slots', the slots of the groups it belongs to) is synchronised, the 1024 largest slots are
+// run a warm-up count (the call's, the handle's, the slot streams of every stager that feeds the handle: its own and
+// those of the groups it belongs to, whose other slot may still be counting) is synchronised, the 1024 largest slots are
 // selected on the device (radix select, 8 bits per pass from the top), only those <= 1024 (symbol, count) pairs come
 // to the host, the heap is replayed there (mpc_sc2.h) and the bucket image goes back to the device.
 int sc2_build(mpc_handle *h, hipStream_t s)
 {
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (int i = 0; i < 2; i++)
-    if (h->slots[i].stream) HIPCHK(h, hipStreamSynchronize(h->slots[i].stream));
-  // a member of a group: the warm-up chunk may be counting on the group's other slot
-  for (hipStream_t gs : h->group_streams) HIPCHK(h, hipStreamSynchronize(gs));
+  for (Stager *st : h->fed_by) {
+    const int rc = mpcstage::sync_slots(*st, sink_of(h));
+    if (rc != MPC_OK) return rc;
+  }
   const u64 n_slots = h->sc2.hash_mask + 1;
   const int grid = (int)std::min<u64>((n_slots + 255) / 256, (u64)h->num_cus * 8);
   uint32_t *d_work = nullptr;           // [256] histogram | [1] count | pad | [1024] uint64 slots
@@ -544,7 +472,7 @@ int launch_pattern(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes,
 // Pattern, at a point where the handle's work is complete: has a line beyond the capacity arrived?
 int pattern_status(mpc_handle *h)
 {
-  if (h->algorithm != 5) return MPC_OK;
+  if (h->algorithm != Algo::Pattern) return MPC_OK;
   if (!h->pat.over) {
     u64 ctl[2] = {0, 0};
     HIPCHK(h, hipMemcpy(ctl, h->pat.set.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
@@ -553,105 +481,11 @@ int pattern_status(mpc_handle *h)
   return h->pat.over ? set_err(h, MPC_E_INVAL, kPatternLimit) : MPC_OK;
 }
 
-int ensure_slots(mpc_handle *h)
-{
-  if (h->slots_ready) return MPC_OK;
-  h->stage_lines = kStageBytes / (size_t)h->L;
-  for (int i = 0; i < 2; i++) {
-    Slot &s = h->slots[i];
-    HIPCHK(h, hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    HIPCHK(h, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    HIPCHK(h, hipHostMalloc((void **)&s.h_in, kStageBytes, hipHostMallocDefault));
-    HIPCHK(h, hipMalloc((void **)&s.d_in, kStageBytes));
-    HIPCHK(h, hipMalloc((void **)&s.d_sizes, h->stage_lines * sizeof(uint16_t)));
-    HIPCHK(h, hipMalloc((void **)&s.d_sel, h->stage_lines));
-    HIPCHK(h, hipHostMalloc((void **)&s.h_sizes, h->stage_lines * sizeof(uint16_t), hipHostMallocDefault));
-    HIPCHK(h, hipHostMalloc((void **)&s.h_sel, h->stage_lines, hipHostMallocDefault));
-  }
-  h->slots_ready = true;
-  return MPC_OK;
-}
-
-int ensure_mini(mpc_handle *h)
-{
-  if (h->mini) return MPC_OK;
-  const size_t bytes = kMiniLines * ((size_t)h->L + sizeof(uint16_t) + 1);
-  HIPCHK(h, hipHostMalloc((void **)&h->mini, bytes, hipHostMallocDefault));
-  return MPC_OK;
-}
-
-// n <= kMiniLines lines, evaluated in place from pinned host memory on the handle's own stream
-int compress_small(mpc_handle *h, const uint8_t *lines, uint64_t n, uint16_t *sizes, int8_t *sel)
-{
-  int rc = ensure_mini(h);
-  if (rc != MPC_OK) return rc;
-  uint8_t *in = h->mini;
-  uint16_t *out_sizes = reinterpret_cast<uint16_t *>(h->mini + kMiniLines * (size_t)h->L);
-  int8_t *out_sel = reinterpret_cast<int8_t *>(out_sizes + kMiniLines);
-  std::memcpy(in, lines, (size_t)(n * (uint64_t)h->L));
-  rc = launch(h, in, n, sizes ? out_sizes : nullptr, sel ? out_sel : nullptr, h->stream);
-  if (rc != MPC_OK) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));   // (polling hipStreamQuery instead was slower: 46 k vs 58 k lines/s)
-  if (sizes) std::memcpy(sizes, out_sizes, (size_t)n * sizeof(uint16_t));
-  if (sel) std::memcpy(sel, out_sel, (size_t)n);
-  return pattern_status(h);
-}
-
-// wait for a slot's in-flight chunk and hand its per-line results to the caller
-int retire(mpc_handle *h, Slot &s)
-{
-  if (!s.busy) return MPC_OK;
-  HIPCHK(h, hipEventSynchronize(s.done));
-  if (s.user_sizes) std::memcpy(s.user_sizes, s.h_sizes, s.pending_lines * sizeof(uint16_t));
-  if (s.user_sel) std::memcpy(s.user_sel, s.h_sel, s.pending_lines);
-  s.busy = false;
-  return MPC_OK;
-}
-
-// submit the chunk already sitting in s.h_in
-int submit(mpc_handle *h, Slot &s, u64 lines, uint16_t *user_sizes, int8_t *user_sel)
-{
-  HIPCHK(h, hipMemcpyAsync(s.d_in, s.h_in, lines * (u64)h->L, hipMemcpyHostToDevice, s.stream));
-  int rc = launch(h, s.d_in, lines, user_sizes ? s.d_sizes : nullptr, user_sel ? s.d_sel : nullptr, s.stream);
-  if (rc != MPC_OK) return rc;
-  if (user_sizes) HIPCHK(h, hipMemcpyAsync(s.h_sizes, s.d_sizes, lines * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
-  if (user_sel) HIPCHK(h, hipMemcpyAsync(s.h_sel, s.d_sel, lines, hipMemcpyDeviceToHost, s.stream));
-  HIPCHK(h, hipEventRecord(s.done, s.stream));
-  s.user_sizes = user_sizes;
-  s.user_sel = user_sel;
-  s.pending_lines = lines;
-  s.busy = true;
-  return MPC_OK;
-}
-
-// After an error: nothing of the failed call may be delivered later.  Wait for both slots' streams
-// and forget their pending results (the caller's output pointers may be gone by the next call).
-void abandon_slots(mpc_handle *h)
-{
-  for (int i = 0; i < 2; i++) {
-    Slot &s = h->slots[i];
-    if (s.stream) (void)hipStreamSynchronize(s.stream);
-    s.busy = false;
-    s.user_sizes = nullptr;
-    s.user_sel = nullptr;
-    s.pending_lines = 0;
-  }
-}
-
-int sync_all(mpc_handle *h)
-{
-  for (int i = 0; i < 2; i++) {
-    int rc = retire(h, h->slots[i]);
-    if (rc != MPC_OK) return rc;
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return pattern_status(h);
-}
-
 // raw device statistics -> ABI vector (added into `vec`)
 void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<u64> &vec)
 {
-  if (h->algorithm == 5) {
+  switch (h->algorithm) {
+  case Algo::Pattern: {
     const u64 L = (u64)h->L;
     vec[0] += raw[MPC_PAT_LINES];
     vec[3] += raw[MPC_PAT_SIZES];
@@ -673,7 +507,7 @@ void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<
     vec[22] += L * raw[MPC_PAT_ZERO];
     return;
   }
-  if (h->algorithm == 4) {
+  case Algo::SC2: {
     // lines and warm-up lines are counted by the host (it splits every call at line S); bits and hits on the device
     vec[0] += h->sc2.lines;
     vec[1] += h->sc2.lines * 8ull * (u64)h->L;
@@ -683,7 +517,7 @@ void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<
     vec[5] += raw[1];
     return;
   }
-  if (h->algorithm == 3) {
+  case Algo::BPC: {
     // lines are not recoverable from the pattern counts: the kernel counts compressed bits per line,
     // and every line contributes exactly 33 planes = TotalWords / 33
     const u64 lines = raw[7] / 33ull;
@@ -694,7 +528,7 @@ void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<
     for (int i = 0; i < 7; i++) vec[4 + i] += raw[i];
     return;
   }
-  if (h->algorithm == 2) {
+  case Algo::FPC: {
     u64 words = 0;
     for (int i = 0; i < 8; i++) {
       vec[3 + i] += raw[i];
@@ -705,7 +539,7 @@ void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<
     vec[2] += raw[8];
     return;
   }
-  if (h->algorithm == 1) {
+  case Algo::BDI: {
     u64 lines = 0;
     for (int i = 0; i < 9; i++) {
       vec[3 + i] += raw[i];
@@ -715,6 +549,8 @@ void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<
     vec[1] += lines * 8ull * (u64)h->L;
     vec[2] += raw[9];
     return;
+  }
+  case Algo::VPC: break;
   }
   const int K = h->cfg.M + 1, B = h->cfg.hist_bins;
   const u64 uncomp = 8ull * (u64)h->L;
@@ -742,231 +578,22 @@ void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<
   }
 }
 
-// ---- .npy header (format spec: magic, version, header length, python dict) ----
-int parse_npy_header(FILE *f, u64 *rows, u64 *cols, u64 *data_off, std::string &err)
-{
-  unsigned char pre[12];
-  if (fread(pre, 1, 10, f) != 10 || std::memcmp(pre, "\x93NUMPY", 6) != 0) { err = "not a .npy file"; return MPC_E_PARSE; }
-  size_t hlen, off;
-  if (pre[6] == 1) {
-    hlen = (size_t)pre[8] | ((size_t)pre[9] << 8);
-    off = 10;
-  } else {
-    if (fread(pre + 10, 1, 2, f) != 2) { err = "truncated .npy header"; return MPC_E_PARSE; }
-    hlen = (size_t)pre[8] | ((size_t)pre[9] << 8) | ((size_t)pre[10] << 16) | ((size_t)pre[11] << 24);
-    off = 12;
-  }
-  if (hlen > (1u << 20)) { err = "unreasonable .npy header length"; return MPC_E_PARSE; }
-  std::string hdr(hlen, '\0');
-  if (fread(&hdr[0], 1, hlen, f) != hlen) { err = "truncated .npy header"; return MPC_E_PARSE; }
-  auto find_val = [&](const char *key) -> size_t {
-    size_t p = hdr.find(key);
-    if (p == std::string::npos) return p;
-    p = hdr.find(':', p);
-    return p == std::string::npos ? p : p + 1;
-  };
-  size_t p = find_val("'descr'");
-  if (p == std::string::npos) { err = ".npy header has no descr"; return MPC_E_PARSE; }
-  size_t q1 = hdr.find('\'', p), q2 = q1 == std::string::npos ? q1 : hdr.find('\'', q1 + 1);
-  if (q2 == std::string::npos) { err = ".npy descr malformed"; return MPC_E_PARSE; }
-  std::string descr = hdr.substr(q1 + 1, q2 - q1 - 1);
-  if (!(descr == "|u1" || descr == "<u1" || descr == "u1" || descr == "=u1")) { err = ".npy dtype is " + descr + ", expected uint8"; return MPC_E_INVAL; }
-  p = find_val("'fortran_order'");
-  {
-    const size_t v = p == std::string::npos ? p : hdr.find_first_not_of(' ', p);
-    if (v == std::string::npos) { err = ".npy header has no fortran_order value"; return MPC_E_PARSE; }
-    if (hdr.compare(v, 5, "False") != 0) { err = ".npy array must be C-order"; return MPC_E_INVAL; }
-  }
-  p = find_val("'shape'");
-  size_t a = p == std::string::npos ? p : hdr.find('(', p), b = a == std::string::npos ? a : hdr.find(')', a);
-  if (b == std::string::npos) { err = ".npy shape malformed"; return MPC_E_PARSE; }
-  std::vector<u64> dims;
-  const char *c = hdr.c_str() + a + 1, *e = hdr.c_str() + b;
-  while (c < e) {
-    while (c < e && (*c < '0' || *c > '9')) c++;
-    if (c >= e) break;
-    u64 v = 0;
-    while (c < e && *c >= '0' && *c <= '9') v = v * 10 + (u64)(*c++ - '0');
-    dims.push_back(v);
-  }
-  if (dims.size() != 2) { err = ".npy array must be 2-D [lines, line_size]"; return MPC_E_INVAL; }
-  *rows = dims[0];
-  *cols = dims[1];
-  *data_off = off + hlen;
-  return MPC_OK;
-}
-
-// ---- streaming a trace file through the staging slots.  The file walkers below are written once, against a
-// "feed": who owns the two slots and what a submitted chunk is launched on -- one handle, or a group of them.
-struct HandleFeed {
-  mpc_handle *h;
-  int L() const { return h->L; }
-  int device() const { return h->device; }
-  int fail(int code, const std::string &msg) const { return set_err(h, code, msg); }
-  int ensure() const { return ensure_slots(h); }
-  u64 stage_lines() const { return (u64)h->stage_lines; }
-  uint8_t *buffer(int which) const { return h->slots[which].h_in; }
-  int retire(int which) const { return ::retire(h, h->slots[which]); }
-  int submit(int which, u64 lines) const { return ::submit(h, h->slots[which], lines, nullptr, nullptr); }
-  int finish() const { return sync_all(h); }
-  void abandon() const { abandon_slots(h); }
-};
-
-template <class Feed>
-int feed_npy(Feed fd_, const char *path, uint64_t first_row, uint64_t n_rows, int skip_last_row, uint64_t *rows_done)
-{
-  if (rows_done) *rows_done = 0;
-  FILE *f = fopen(path, "rb");
-  if (!f) return fd_.fail(MPC_E_NOENT, std::string("cannot open ") + path);
-  u64 rows, cols, off;
-  std::string err;
-  int rc = parse_npy_header(f, &rows, &cols, &off, err);
-  if (rc != MPC_OK) { fclose(f); return fd_.fail(rc, err); }
-  if (cols != (u64)fd_.L()) {
-    fclose(f);
-    return fd_.fail(MPC_E_INVAL, "trace line size " + std::to_string(cols) + " differs from the evaluator's " + std::to_string(fd_.L()));
-  }
-  // the reference driver drops the final row (LoaderNPY.cpp:28-32 + main.cpp:240)
-  u64 usable = (skip_last_row && rows > 0) ? rows - 1 : rows;
-  u64 begin = first_row < usable ? first_row : usable;
-  u64 end = (n_rows > usable - begin) ? usable : begin + n_rows;
-  if (hipSetDevice(fd_.device()) != hipSuccess) { fclose(f); return fd_.fail(MPC_E_HIP, "hipSetDevice failed"); }
-  rc = fd_.ensure();
-  if (rc != MPC_OK) { fclose(f); return rc; }
-  const int fd = fileno(f);
-  u64 done = begin;
-  int which = 0;
-  while (done < end) {
-    rc = fd_.retire(which);
-    if (rc != MPC_OK) break;
-    const u64 take = (end - done) < fd_.stage_lines() ? (end - done) : fd_.stage_lines();
-    if (!parallel_pread(fd, fd_.buffer(which), (size_t)(take * cols), off + done * cols)) { rc = fd_.fail(MPC_E_PARSE, "short read: .npy file is truncated"); break; }
-    rc = fd_.submit(which, take);
-    if (rc != MPC_OK) break;
-    done += take;
-    which ^= 1;
-  }
-  fclose(f);
-  if (rc == MPC_OK) rc = fd_.finish();
-  if (rc != MPC_OK) fd_.abandon();
-  if (rc == MPC_OK && rows_done) *rows_done = end - begin;
-  return rc;
-}
-
-constexpr int kLogKeys = 17, kLogRecordHeader = 62;
-
-template <class Feed>
-int feed_gpgpusim_log(Feed fd_, const char *log_path, uint64_t *requests_read, uint64_t *lines_done)
-{
-  if (requests_read) *requests_read = 0;
-  if (lines_done) *lines_done = 0;
-  // the file is mapped and walked in memory (per-request stdio calls cap the rate at ~35 M requests/s)
-  const int fd = open(log_path, O_RDONLY);
-  if (fd < 0) return fd_.fail(MPC_E_NOENT, std::string("Failed to open a file. Check the path of the file: ") + log_path);
-  struct stat st;
-  if (fstat(fd, &st) != 0) { close(fd); return fd_.fail(MPC_E_NOENT, std::string("cannot stat ") + log_path); }
-  const u64 size = (u64)st.st_size;
-  constexpr u64 kFileHeader = 1 + 7 * kLogKeys;
-  const unsigned char *base = nullptr;
-  if (size > 0) {
-    void *m = mmap(nullptr, (size_t)size, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (m == MAP_FAILED) { close(fd); return fd_.fail(MPC_E_NOMEM, std::string("cannot map ") + log_path); }
-    base = static_cast<const unsigned char *>(m);
-    (void)madvise(m, (size_t)size, MADV_SEQUENTIAL);
-  }
-  close(fd);
-  auto unmap = [&]() { if (base) munmap(const_cast<unsigned char *>(base), (size_t)size); };
-  if (size < kFileHeader || base[0] != kLogKeys) {
-    unmap();
-    return fd_.fail(MPC_E_PARSE, "The header of the GPGPU-sim trace file is not valid.");
-  }
-  if (hipSetDevice(fd_.device()) != hipSuccess) { unmap(); return fd_.fail(MPC_E_HIP, "hipSetDevice failed"); }
-  int rc = fd_.ensure();
-  if (rc != MPC_OK) { unmap(); return rc; }
-  const u64 L = (u64)fd_.L();
-  u64 requests = 0, lines = 0, fill = 0, pos = kFileHeader;
-  bool first = true;
-  int which = 0;
-  rc = fd_.retire(which);
-  while (rc == MPC_OK && pos + kLogRecordHeader <= size) {
-    uint32_t req_type, req_size;
-    std::memcpy(&req_type, base + pos + 38, 4);
-    std::memcpy(&req_size, base + pos + 58, 4);
-    if (first && req_size != L) {
-      rc = fd_.fail(MPC_E_INVAL, "trace line size " + std::to_string(req_size) + " differs from the evaluator's " + std::to_string(L));
-      break;
-    }
-    first = false;
-    const u64 next = pos + kLogRecordHeader + (u64)req_size;
-    if (next > size) break;                                      // incomplete trailing request
-    if (req_type == 0u || req_type == 4u) {                      // GLOBAL_ACC_R, GLOBAL_ACC_W
-      if (req_size != L) {
-        rc = fd_.fail(MPC_E_INVAL, "the GPGPU-sim trace mixes request sizes (" + std::to_string(req_size) + " after " + std::to_string(L) + " bytes)");
-        break;
-      }
-      std::memcpy(fd_.buffer(which) + fill * L, base + pos + kLogRecordHeader, (size_t)L);
-      fill++;
-    }
-    pos = next;
-    requests++;
-    if (fill == fd_.stage_lines()) {
-      rc = fd_.submit(which, fill);
-      if (rc != MPC_OK) break;
-      lines += fill;
-      fill = 0;
-      which ^= 1;
-      rc = fd_.retire(which);
-    }
-  }
-  if (rc == MPC_OK && fill) {
-    rc = fd_.submit(which, fill);
-    if (rc == MPC_OK) lines += fill;
-  }
-  if (rc == MPC_OK) rc = fd_.finish();
-  if (rc != MPC_OK) fd_.abandon();
-  unmap();
-  if (rc == MPC_OK) {
-    if (requests_read) *requests_read = requests;
-    if (lines_done) *lines_done = lines;
-  }
-  return rc;
-}
-
 // ---------------------------------------------------------------------------
 // groups: several handles of one line size on one device, fed together
 // ---------------------------------------------------------------------------
-int group_err(mpc_group *g, int code, const std::string &msg)
-{
-  if (g) g->error = msg; else g_create_error = msg;
-  return code;
-}
-
-#define GHIPCHK(g, call)                                                                        \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess)                                                                       \
-      return group_err((g), MPC_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));      \
-  } while (0)
-
-const char *algorithm_name(int algorithm)
-{
-  static const char *const name[] = {"VPC", "BDI", "FPC", "BPC", "SC2", "PATTERN"};
-  return name[algorithm];
-}
-
 // Which members share baselines_kernel: the first BDI, FPC and BPC handle of the group when the line size has an
 // instantiation and at least two of the three are there; every other member launches its own kernel.
 void group_route(mpc_group *g)
 {
   int found[3] = {-1, -1, -1}, n = 0;
   for (size_t i = 0; i < g->m.size(); i++) {
-    const int a = g->m[i]->algorithm;
-    if (a >= 1 && a <= 3 && found[a - 1] < 0) {
+    const int a = (int)g->m[i]->algorithm;
+    if (a >= (int)Algo::BDI && a <= (int)Algo::BPC && found[a - 1] < 0) {
       found[a - 1] = (int)i;
       n++;
     }
   }
-  if (n >= 2 && (g->L == 32 || g->L == 64 || g->L == 128)) {
+  if (n >= 2 && (g->stage.L == 32 || g->stage.L == 64 || g->stage.L == 128)) {
     for (int k = 0; k < 3; k++) {
       g->shared[k] = found[k];
       if (found[k] >= 0 && (g->first_shared < 0 || found[k] < g->first_shared)) g->first_shared = found[k];
@@ -983,7 +610,7 @@ void group_route(mpc_group *g)
         if (is_shared(j)) part += (part.empty() ? "" : "+") + std::string(algorithm_name(g->m[(size_t)j]->algorithm));
       part += ": one kernel";
     } else {
-      part = std::string(algorithm_name(h->algorithm)) + ": " + (h->algorithm == 0 ? mpc_kernel_form(h) : h->algorithm == 5 ? "own kernels" : "own kernel");
+      part = std::string(algorithm_name(h->algorithm)) + ": " + (h->algorithm == Algo::VPC ? mpc_kernel_form(h) : h->algorithm == Algo::Pattern ? "own kernels" : "own kernel");
     }
     form += (form.empty() ? "" : "; ") + part;
   }
@@ -1009,7 +636,7 @@ int group_launch(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_si
         out[k]->sel = d_sel ? d_sel[j] : nullptr;
         out[k]->raw = g->m[(size_t)j]->d_raw;
       }
-      const hipError_t e = mpc_launch_baselines(d_lines, n, g->L, &A, grid_for(h, n, 256, kWgPerCu), s);
+      const hipError_t e = mpc_launch_baselines(d_lines, n, g->stage.L, &A, grid_for(h, n, 256, kWgPerCu), s);
       if (e != hipSuccess) return group_err(g, MPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
       continue;
     }
@@ -1017,98 +644,6 @@ int group_launch(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_si
     if (rc != MPC_OK) return group_err(g, rc, "member " + std::to_string(i) + " (" + algorithm_name(h->algorithm) + "): " + h->error);
   }
   return MPC_OK;
-}
-
-int group_ensure_slots(mpc_group *g)
-{
-  if (g->slots_ready) return MPC_OK;
-  g->stage_lines = kStageBytes / (size_t)g->L;
-  for (int i = 0; i < 2; i++) {
-    GroupSlot &s = g->slots[i];
-    if (!s.h_in) GHIPCHK(g, hipHostMalloc((void **)&s.h_in, kStageBytes, hipHostMallocDefault));
-    if (!s.d_in) GHIPCHK(g, hipMalloc((void **)&s.d_in, kStageBytes));
-  }
-  g->slots_ready = true;
-  return MPC_OK;
-}
-
-// the per-line output buffers of member i in a slot, when a call asks for them for the first time
-int group_ensure_outputs(mpc_group *g, GroupSlot &s, size_t i, bool sizes, bool sel)
-{
-  if (sizes && !s.d_sizes[i]) {
-    GHIPCHK(g, hipMalloc((void **)&s.d_sizes[i], g->stage_lines * sizeof(uint16_t)));
-    GHIPCHK(g, hipHostMalloc((void **)&s.h_sizes[i], g->stage_lines * sizeof(uint16_t), hipHostMallocDefault));
-  }
-  if (sel && !s.d_sel[i]) {
-    GHIPCHK(g, hipMalloc((void **)&s.d_sel[i], g->stage_lines));
-    GHIPCHK(g, hipHostMalloc((void **)&s.h_sel[i], g->stage_lines, hipHostMallocDefault));
-  }
-  return MPC_OK;
-}
-
-int group_retire(mpc_group *g, GroupSlot &s)
-{
-  if (!s.busy) return MPC_OK;
-  GHIPCHK(g, hipEventSynchronize(s.done));
-  for (size_t i = 0; i < g->m.size(); i++) {
-    if (s.user_sizes[i]) std::memcpy(s.user_sizes[i], s.h_sizes[i], s.pending_lines * sizeof(uint16_t));
-    if (s.user_sel[i]) std::memcpy(s.user_sel[i], s.h_sel[i], s.pending_lines);
-  }
-  s.busy = false;
-  return MPC_OK;
-}
-
-// submit the chunk already sitting in s.h_in: one copy, then every member's launch on the slot's stream.
-// sizes / sel: the callers' arrays of per-member pointers (or null), `first` the chunk's first line in them.
-int group_submit(mpc_group *g, GroupSlot &s, u64 lines, uint16_t *const *sizes, int8_t *const *sel, u64 first)
-{
-  const size_t n = g->m.size();
-  std::vector<uint16_t *> ds(n, nullptr);
-  std::vector<int8_t *> dl(n, nullptr);
-  for (size_t i = 0; i < n; i++) {
-    s.user_sizes[i] = (sizes && sizes[i]) ? sizes[i] + first : nullptr;
-    s.user_sel[i] = (sel && sel[i]) ? sel[i] + first : nullptr;
-    const int rc = group_ensure_outputs(g, s, i, s.user_sizes[i] != nullptr, s.user_sel[i] != nullptr);
-    if (rc != MPC_OK) return rc;
-    if (s.user_sizes[i]) ds[i] = s.d_sizes[i];
-    if (s.user_sel[i]) dl[i] = s.d_sel[i];
-  }
-  GHIPCHK(g, hipMemcpyAsync(s.d_in, s.h_in, lines * (u64)g->L, hipMemcpyHostToDevice, s.stream));
-  const int rc = group_launch(g, s.d_in, lines, ds.data(), dl.data(), s.stream);
-  if (rc != MPC_OK) return rc;
-  for (size_t i = 0; i < n; i++) {
-    if (ds[i]) GHIPCHK(g, hipMemcpyAsync(s.h_sizes[i], ds[i], lines * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
-    if (dl[i]) GHIPCHK(g, hipMemcpyAsync(s.h_sel[i], dl[i], lines, hipMemcpyDeviceToHost, s.stream));
-  }
-  GHIPCHK(g, hipEventRecord(s.done, s.stream));
-  s.pending_lines = lines;
-  s.busy = true;
-  return MPC_OK;
-}
-
-// after an error: nothing of the failed call may be delivered later (abandon_slots)
-void group_abandon(mpc_group *g)
-{
-  for (int i = 0; i < 2; i++) {
-    GroupSlot &s = g->slots[i];
-    if (s.stream) (void)hipStreamSynchronize(s.stream);
-    s.busy = false;
-    s.pending_lines = 0;
-    std::fill(s.user_sizes.begin(), s.user_sizes.end(), nullptr);
-    std::fill(s.user_sel.begin(), s.user_sel.end(), nullptr);
-  }
-}
-
-int group_members_status(mpc_group *g);
-
-int group_finish(mpc_group *g)
-{
-  for (int i = 0; i < 2; i++) {
-    const int rc = group_retire(g, g->slots[i]);
-    if (rc != MPC_OK) return rc;
-  }
-  for (int i = 0; i < 2; i++) GHIPCHK(g, hipStreamSynchronize(g->slots[i].stream));
-  return group_members_status(g);
 }
 
 // a Pattern member that ran into its capacity fails the group call (checked wherever the group has synchronised)
@@ -1121,45 +656,46 @@ int group_members_status(mpc_group *g)
   return MPC_OK;
 }
 
-// n <= kMiniLines lines, evaluated in place from pinned host memory: one launch per member or per shared launch on the
-// first slot's stream (idle: every group call ends synchronised), one synchronisation
-int group_small(mpc_group *g, const uint8_t *lines, u64 n, uint16_t *const *sizes, int8_t *const *sel)
+// the line sizes an algorithm of the table takes (the refusal lands in mpc_last_error(NULL))
+int check_line_size(Algo a, unsigned line_size)
 {
-  const size_t nm = g->m.size();
-  if (!g->mini) GHIPCHK(g, hipHostMalloc((void **)&g->mini, kMiniLines * ((size_t)g->L + nm * (sizeof(uint16_t) + 1)), hipHostMallocDefault));
-  uint16_t *out_sizes = reinterpret_cast<uint16_t *>(g->mini + kMiniLines * (size_t)g->L);
-  int8_t *out_sel = reinterpret_cast<int8_t *>(out_sizes + nm * kMiniLines);
-  std::vector<uint16_t *> ds(nm, nullptr);
-  std::vector<int8_t *> dl(nm, nullptr);
-  for (size_t i = 0; i < nm; i++) {
-    if (sizes && sizes[i]) ds[i] = out_sizes + i * kMiniLines;
-    if (sel && sel[i]) dl[i] = out_sel + i * kMiniLines;
-  }
-  std::memcpy(g->mini, lines, (size_t)(n * (u64)g->L));
-  hipStream_t s = g->slots[0].stream;
-  const int rc = group_launch(g, g->mini, n, ds.data(), dl.data(), s);
-  if (rc != MPC_OK) { (void)hipStreamSynchronize(s); return rc; }
-  GHIPCHK(g, hipStreamSynchronize(s));
-  for (size_t i = 0; i < nm; i++) {
-    if (ds[i]) std::memcpy(sizes[i], ds[i], (size_t)n * sizeof(uint16_t));
-    if (dl[i]) std::memcpy(sel[i], dl[i], (size_t)n);
-  }
-  return group_members_status(g);
+  const AlgoFacts &f = facts(a);
+  if (line_size >= f.min_line && line_size <= f.max_line && line_size % f.multiple == 0) return MPC_OK;
+  return set_err(nullptr, MPC_E_INVAL, std::string(f.label) + " line size must be a multiple of " + std::to_string(f.multiple) + " in " +
+                                           std::to_string(f.min_line) + ".." + std::to_string(f.max_line) + " bytes");
 }
 
-struct GroupFeed {
-  mpc_group *g;
-  int L() const { return g->L; }
-  int device() const { return g->device; }
-  int fail(int code, const std::string &msg) const { return group_err(g, code, msg); }
-  int ensure() const { return group_ensure_slots(g); }
-  u64 stage_lines() const { return (u64)g->stage_lines; }
-  uint8_t *buffer(int which) const { return g->slots[which].h_in; }
-  int retire(int which) const { return group_retire(g, g->slots[which]); }
-  int submit(int which, u64 lines) const { return group_submit(g, g->slots[which], lines, nullptr, nullptr, 0); }
-  int finish() const { return group_finish(g); }
-  void abandon() const { group_abandon(g); }
-};
+// A handle of an algorithm whose lengths are in the table: BDI, FPC and BPC are done with it, SC2 and Pattern add their
+// own allocations.  *out is the handle or null.
+int create_fixed(Algo a, unsigned line_size, int device, mpc_handle **out)
+{
+  if (!out) return MPC_E_INVAL;
+  *out = nullptr;
+  int rc = check_line_size(a, line_size);
+  if (rc != MPC_OK) return rc;
+  mpc_handle *h = new (std::nothrow) mpc_handle();
+  if (!h) return MPC_E_NOMEM;
+  h->algorithm = a;
+  h->L = (int)line_size;
+  h->raw_len = facts(a).raw_len;
+  h->stats_len = facts(a).stats_len;
+  rc = pick_device(device, &h->device, &h->num_cus);
+  if (rc == MPC_OK) rc = finish_create(h);
+  if (rc != MPC_OK) {
+    mpc_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return MPC_OK;
+}
+
+// (for SC2 and Pattern) the algorithm's own allocations failed: no handle
+int create_failed(int rc, mpc_handle **out)
+{
+  mpc_destroy(*out);
+  *out = nullptr;
+  return rc;
+}
 
 uint32_t *g_sine_dev[16] = {nullptr};   // per device float32 sine period for mpc_synth_fill
 
@@ -1187,132 +723,44 @@ int mpc_create_vpc(const char *path, int device, mpc_handle **out)
   return create_vpc_from_text(text, device, out);
 }
 
-int mpc_create_bdi(unsigned line_size, int device, mpc_handle **out)
-{
-  if (!out) return MPC_E_INVAL;
-  *out = nullptr;
-  // BDI.cpp:8 takes any dataLine.size(); values are 8, 4 and 2 bytes wide, so a multiple of 8
-  if (line_size < 8 || line_size > MPC_MAX_LINE || (line_size % 8)) {
-    g_create_error = "BDI line size must be a multiple of 8 in 8.." + std::to_string(MPC_MAX_LINE) + " bytes";
-    return MPC_E_INVAL;
-  }
-  mpc_handle *h = new (std::nothrow) mpc_handle();
-  if (!h) return MPC_E_NOMEM;
-  h->algorithm = 1;
-  h->L = (int)line_size;
-  h->raw_len = MPC_BDI_RAW_LEN;
-  h->stats_len = 12;
-  int rc = pick_device(device, &h->device, &h->num_cus);
-  if (rc == MPC_OK) rc = finish_create(h);
-  if (rc != MPC_OK) {
-    mpc_destroy(h);
-    return rc;
-  }
-  *out = h;
-  return MPC_OK;
-}
-
-int mpc_create_bpc(unsigned line_size, int device, mpc_handle **out)
-{
-  if (!out) return MPC_E_INVAL;
-  *out = nullptr;
-  // 32-bit words; a plane has one bit per delta and is held in an int32_t (BPC.cpp:53-63): 2..32 words
-  if (line_size < 8 || line_size > 128 || (line_size % 4)) {
-    g_create_error = "BPC line size must be a multiple of 4 in 8..128 bytes";
-    return MPC_E_INVAL;
-  }
-  mpc_handle *h = new (std::nothrow) mpc_handle();
-  if (!h) return MPC_E_NOMEM;
-  h->algorithm = 3;
-  h->L = (int)line_size;
-  h->raw_len = MPC_BPC_RAW_LEN;
-  h->stats_len = 11;
-  int rc = pick_device(device, &h->device, &h->num_cus);
-  if (rc == MPC_OK) rc = finish_create(h);
-  if (rc != MPC_OK) {
-    mpc_destroy(h);
-    return rc;
-  }
-  *out = h;
-  return MPC_OK;
-}
-
-int mpc_create_fpc(unsigned line_size, int device, mpc_handle **out)
-{
-  if (!out) return MPC_E_INVAL;
-  *out = nullptr;
-  if (line_size < 4 || line_size > MPC_MAX_LINE || (line_size % 4)) {
-    g_create_error = "FPC line size must be a multiple of 4 in 4.." + std::to_string(MPC_MAX_LINE) + " bytes";
-    return MPC_E_INVAL;
-  }
-  mpc_handle *h = new (std::nothrow) mpc_handle();
-  if (!h) return MPC_E_NOMEM;
-  h->algorithm = 2;
-  h->L = (int)line_size;
-  h->raw_len = MPC_FPC_RAW_LEN;
-  h->stats_len = 11;
-  int rc = pick_device(device, &h->device, &h->num_cus);
-  if (rc == MPC_OK) rc = finish_create(h);
-  if (rc != MPC_OK) {
-    mpc_destroy(h);
-    return rc;
-  }
-  *out = h;
-  return MPC_OK;
-}
+int mpc_create_bdi(unsigned line_size, int device, mpc_handle **out) { return create_fixed(Algo::BDI, line_size, device, out); }
+int mpc_create_fpc(unsigned line_size, int device, mpc_handle **out) { return create_fixed(Algo::FPC, line_size, device, out); }
+int mpc_create_bpc(unsigned line_size, int device, mpc_handle **out) { return create_fixed(Algo::BPC, line_size, device, out); }
 
 int mpc_create_pattern(unsigned line_size, int device, mpc_handle **out)
 {
-  if (!out) return MPC_E_INVAL;
-  *out = nullptr;
-  // 8-, 4- and 2-byte values (Pattern.cpp:26-58): a multiple of 8, or checkPattern reads past the line
-  if (line_size < 8 || line_size > MPC_MAX_LINE || (line_size % 8)) {
-    g_create_error = "Pattern line size must be a multiple of 8 in 8.." + std::to_string(MPC_MAX_LINE) + " bytes";
-    return MPC_E_INVAL;
-  }
-  mpc_handle *h = new (std::nothrow) mpc_handle();
-  if (!h) return MPC_E_NOMEM;
-  h->algorithm = 5;
-  h->L = (int)line_size;
-  h->raw_len = MPC_PATTERN_RAW_LEN;
-  h->stats_len = 534;
-  int rc = pick_device(device, &h->device, &h->num_cus);
-  if (rc == MPC_OK) rc = finish_create(h);
-  if (rc == MPC_OK) {
-    MpcPatternSet &S = h->pat.set;
-    const size_t slots = (size_t)1 << MPC_PATTERN_SLOT_BITS;
-    S.tag_mask = ~0ull;
+  int rc = create_fixed(Algo::Pattern, line_size, device, out);
+  if (rc != MPC_OK) return rc;
+  mpc_handle *h = *out;
+  MpcPatternSet &S = h->pat.set;
+  const size_t slots = (size_t)1 << MPC_PATTERN_SLOT_BITS;
+  S.tag_mask = ~0ull;
 #if MPC_TESTING
-    // test library only: a hash of a few bits, so that unequal lines meet on the tag and in the chains
-    if (const char *e = getenv("MPC_TEST_PATTERN_TAG_BITS")) {
-      const long bits = atol(e);
-      if (bits >= 1 && bits < 64) S.tag_mask = (1ull << bits) - 1ull;
-    }
+  // test library only: a hash of a few bits, so that unequal lines meet on the tag and in the chains
+  if (const char *e = getenv("MPC_TEST_PATTERN_TAG_BITS")) {
+    const long bits = atol(e);
+    if (bits >= 1 && bits < 64) S.tag_mask = (1ull << bits) - 1ull;
+  }
 #endif
-    if (hipMalloc((void **)&S.tags, slots * sizeof(u64)) != hipSuccess || hipMalloc((void **)&S.store, slots * (size_t)line_size) != hipSuccess ||
-        hipMalloc((void **)&S.ctl, MPC_PSET_WORDS * sizeof(u64)) != hipSuccess ||
-        hipMalloc((void **)&S.pend_a, (size_t)MPC_PATTERN_CHUNK * sizeof(uint2)) != hipSuccess ||
-        hipMalloc((void **)&S.pend_b, (size_t)MPC_PATTERN_CHUNK * sizeof(uint2)) != hipSuccess) {
-      g_create_error = "hipMalloc of the Pattern line set (" + std::to_string(slots * (sizeof(u64) + line_size)) + " bytes) failed";
-      rc = MPC_E_NOMEM;
-    } else if (hipMemset(S.tags, 0, slots * sizeof(u64)) != hipSuccess || hipMemset(S.ctl, 0, MPC_PSET_WORDS * sizeof(u64)) != hipSuccess ||
-               hipDeviceSynchronize() != hipSuccess ||          // (the kernels run on non-blocking streams)
-               hipEventCreateWithFlags(&h->pat.done, hipEventDisableTiming) != hipSuccess) {
-      g_create_error = "initialising the Pattern line set failed";
-      rc = MPC_E_NODEVICE;
-    }
+  if (hipMalloc((void **)&S.tags, slots * sizeof(u64)) != hipSuccess || hipMalloc((void **)&S.store, slots * (size_t)line_size) != hipSuccess ||
+      hipMalloc((void **)&S.ctl, MPC_PSET_WORDS * sizeof(u64)) != hipSuccess ||
+      hipMalloc((void **)&S.pend_a, (size_t)MPC_PATTERN_CHUNK * sizeof(uint2)) != hipSuccess ||
+      hipMalloc((void **)&S.pend_b, (size_t)MPC_PATTERN_CHUNK * sizeof(uint2)) != hipSuccess) {
+    g_create_error = "hipMalloc of the Pattern line set (" + std::to_string(slots * (sizeof(u64) + line_size)) + " bytes) failed";
+    return create_failed(MPC_E_NOMEM, out);
   }
-  if (rc != MPC_OK) {
-    mpc_destroy(h);
-    return rc;
+  if (hipMemset(S.tags, 0, slots * sizeof(u64)) != hipSuccess || hipMemset(S.ctl, 0, MPC_PSET_WORDS * sizeof(u64)) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess ||          // (the kernels run on non-blocking streams)
+      hipEventCreateWithFlags(&h->pat.done, hipEventDisableTiming) != hipSuccess) {
+    g_create_error = "initialising the Pattern line set failed";
+    return create_failed(MPC_E_NODEVICE, out);
   }
-  *out = h;
   return MPC_OK;
 }
 
 int mpc_pattern_distinct_lines(mpc_handle *h, uint64_t *n)
 {
-  if (!h || !n || h->algorithm != 5) return MPC_E_INVAL;
+  if (!h || !n || h->algorithm != Algo::Pattern) return MPC_E_INVAL;
   HIPCHK(h, hipSetDevice(h->device));
   int rc = sync_all(h);
   if (rc != MPC_OK) return rc;
@@ -1344,10 +792,9 @@ int mpc_create_sc2(unsigned line_size, uint64_t sampling_lines, int device, mpc_
 {
   if (!out) return MPC_E_INVAL;
   *out = nullptr;
-  if (line_size < 4 || line_size > MPC_MAX_LINE || (line_size % 4)) {
-    g_create_error = "SC2 line size must be a multiple of 4 in 4.." + std::to_string(MPC_MAX_LINE) + " bytes";
-    return MPC_E_INVAL;
-  }
+  // (the refusals in the order they have always come in: the line size, then the sample, and only then the device)
+  int rc = check_line_size(Algo::SC2, line_size);
+  if (rc != MPC_OK) return rc;
   if (sampling_lines == 0) {
     g_create_error = "SC2 needs at least one warm-up line (the reference builds its table from an empty map otherwise)";
     return MPC_E_INVAL;
@@ -1357,36 +804,26 @@ int mpc_create_sc2(unsigned line_size, uint64_t sampling_lines, int device, mpc_
     g_create_error = "SC2 warm-up sample of more than 2^28 words (its frequency table would exceed 4 GiB)";
     return MPC_E_INVAL;
   }
-  mpc_handle *h = new (std::nothrow) mpc_handle();
-  if (!h) return MPC_E_NOMEM;
-  h->algorithm = 4;
-  h->L = (int)line_size;
-  h->raw_len = MPC_SC2_RAW_LEN;
-  h->stats_len = 6;
+  rc = create_fixed(Algo::SC2, line_size, device, out);
+  if (rc != MPC_OK) return rc;
+  mpc_handle *h = *out;
   h->sc2.S = sampling_lines;
   u64 slots = 2;
   while (slots < 2 * words) slots <<= 1;
   h->sc2.hash_mask = slots - 1;
-  int rc = pick_device(device, &h->device, &h->num_cus);
-  if (rc == MPC_OK) rc = finish_create(h);
-  if (rc == MPC_OK && (hipMalloc((void **)&h->sc2.d_hash, slots * sizeof(u64)) != hipSuccess ||
-                       hipMalloc((void **)&h->sc2.d_buckets, MPC_SC2_MAX_BUCKETS * sizeof(uint4)) != hipSuccess ||
-                       hipMemset(h->sc2.d_hash, 0, slots * sizeof(u64)) != hipSuccess ||
-                       hipDeviceSynchronize() != hipSuccess)) {        // (the kernels run on non-blocking streams)
+  if (hipMalloc((void **)&h->sc2.d_hash, slots * sizeof(u64)) != hipSuccess ||
+      hipMalloc((void **)&h->sc2.d_buckets, MPC_SC2_MAX_BUCKETS * sizeof(uint4)) != hipSuccess ||
+      hipMemset(h->sc2.d_hash, 0, slots * sizeof(u64)) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess) {        // (the kernels run on non-blocking streams)
     g_create_error = "hipMalloc of the SC2 frequency table (" + std::to_string(slots * sizeof(u64)) + " bytes) failed";
-    rc = MPC_E_NOMEM;
+    return create_failed(MPC_E_NOMEM, out);
   }
-  if (rc != MPC_OK) {
-    mpc_destroy(h);
-    return rc;
-  }
-  *out = h;
   return MPC_OK;
 }
 
 int mpc_sc2_table(mpc_handle *h, uint32_t *symbols, uint16_t *lengths, size_t cap, size_t *n)
 {
-  if (!h || !n || h->algorithm != 4) return MPC_E_INVAL;
+  if (!h || !n || h->algorithm != Algo::SC2) return MPC_E_INVAL;
   const size_t m = h->sc2.symbols.size();
   *n = m;
   if (m == 0) return MPC_OK;
@@ -1400,23 +837,10 @@ void mpc_destroy(mpc_handle *h)
 {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  for (int i = 0; i < 2; i++) {
-    Slot &s = h->slots[i];
-    if (s.stream) (void)hipStreamSynchronize(s.stream);
-    if (s.h_in) (void)hipHostFree(s.h_in);
-    if (s.d_in) (void)hipFree(s.d_in);
-    if (s.d_sizes) (void)hipFree(s.d_sizes);
-    if (s.d_sel) (void)hipFree(s.d_sel);
-    if (s.h_sizes) (void)hipHostFree(s.h_sizes);
-    if (s.h_sel) (void)hipHostFree(s.h_sel);
-    if (s.done) (void)hipEventDestroy(s.done);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-  }
-  if (h->stream) {
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipStreamDestroy(h->stream);
-  }
-  if (h->mini) (void)hipHostFree(h->mini);
+  // (the handle's own stream first: an in-place call that failed half way may have left work that reads the stager's buffer)
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  mpcstage::destroy(h->stage);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
   if (h->d_tab) (void)hipFree(h->d_tab);
   if (h->d_gtab) (void)hipFree(h->d_gtab);
   if (h->d_raw) (void)hipFree(h->d_raw);
@@ -1435,13 +859,13 @@ int mpc_get_info(const mpc_handle *h, mpc_info *info)
 {
   if (!h || !info) return MPC_E_INVAL;
   info->abi_version = MPC_ABI_VERSION;
-  info->algorithm = h->algorithm;
+  const bool vpc = h->algorithm == Algo::VPC;
+  info->algorithm = (int)h->algorithm;
   info->line_size = h->L;
-  info->num_modules = h->algorithm == 0 ? h->cfg.M : 0;
-  info->num_clusters = h->algorithm == 0 ? h->cfg.M + 1 : (h->algorithm == 1 ? 9 : (h->algorithm == 2 ? 8 : h->algorithm == 3 ? 7 : h->algorithm == 5 ? 10 : 2));
-  info->hist_bins = h->algorithm == 0 ? h->cfg.hist_bins : 0;
-  info->kernel_path = h->algorithm == 5 ? MPC_PATH_PATTERN : h->algorithm == 4 ? MPC_PATH_SC2 : h->algorithm == 3 ? MPC_PATH_BPC : h->algorithm == 2 ? MPC_PATH_FPC
-                      : h->algorithm == 1 ? MPC_PATH_BDI : (h->route.kernel != VpcKernel::Generic ? MPC_PATH_VPC_FAST : MPC_PATH_VPC_GENERIC);
+  info->num_modules = vpc ? h->cfg.M : 0;
+  info->num_clusters = vpc ? h->cfg.M + 1 : facts(h->algorithm).clusters;
+  info->hist_bins = vpc ? h->cfg.hist_bins : 0;
+  info->kernel_path = vpc && h->route.kernel == VpcKernel::Generic ? MPC_PATH_VPC_GENERIC : facts(h->algorithm).path;
   info->device = h->device;
   info->stats_len = h->stats_len;
   return MPC_OK;
@@ -1477,9 +901,9 @@ long long mpc_jit_compile_check(const char *json_text, char *log, size_t cap)
 const char *mpc_kernel_form(const mpc_handle *h)
 {
   if (!h) return "";
-  if (h->algorithm == 4) return h->sc2.built ? "table sizing" : "warm-up counting";
-  if (h->algorithm == 5) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled, then the set passes" : "run-time loop, then the set passes";
-  if (h->algorithm != 0) return "unrolled";
+  if (h->algorithm == Algo::SC2) return h->sc2.built ? "table sizing" : "warm-up counting";
+  if (h->algorithm == Algo::Pattern) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled, then the set passes" : "run-time loop, then the set passes";
+  if (h->algorithm != Algo::VPC) return "unrolled";
   if (h->route.kernel == VpcKernel::AtCreation && h->jit.from_cache) return "unrolled, compiled at creation (from the cache)";
   static const char *const form[] = {"unrolled", "unrolled, general layout", "unrolled, compiled at creation", "run-time loop", "generic"};
   return form[(int)h->route.kernel];      // (VpcKernel order)
@@ -1487,7 +911,7 @@ const char *mpc_kernel_form(const mpc_handle *h)
 
 const char *mpc_path_reason(const mpc_handle *h)
 {
-  return (h && h->algorithm == 0) ? h->route.why_generic.c_str() : "";
+  return (h && h->algorithm == Algo::VPC) ? h->route.why_generic.c_str() : "";
 }
 
 int mpc_compress_batch_device(mpc_handle *h, const void *d_lines, uint64_t n, uint16_t *d_sizes, int8_t *d_sel,
@@ -1513,29 +937,7 @@ int mpc_compress_batch(mpc_handle *h, const uint8_t *lines, uint64_t n, uint16_t
 {
   if (!h || (!lines && n)) return MPC_E_INVAL;
   if (n == 0) return MPC_OK;
-  if (n <= kMiniLines) {
-    HIPCHK(h, hipSetDevice(h->device));
-    return compress_small(h, lines, n, sizes, sel);
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc = ensure_slots(h);
-  if (rc != MPC_OK) return rc;
-  u64 done = 0;
-  int which = 0;
-  while (done < n) {
-    Slot &s = h->slots[which];
-    rc = retire(h, s);   // the slot's previous chunk (overlapped with the other slot's work)
-    if (rc != MPC_OK) break;
-    const u64 take = (n - done) < (u64)h->stage_lines ? (n - done) : (u64)h->stage_lines;
-    parallel_copy(s.h_in, lines + done * (u64)h->L, (size_t)(take * (u64)h->L));
-    rc = submit(h, s, take, sizes ? sizes + done : nullptr, sel ? sel + done : nullptr);
-    if (rc != MPC_OK) break;
-    done += take;
-    which ^= 1;
-  }
-  if (rc == MPC_OK) rc = sync_all(h);
-  if (rc != MPC_OK) abandon_slots(h);
-  return rc;
+  return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, &sizes, &sel);   // (a group of one)
 }
 
 int mpc_npy_shape(const char *path, uint64_t *rows, uint64_t *cols)
@@ -1545,7 +947,7 @@ int mpc_npy_shape(const char *path, uint64_t *rows, uint64_t *cols)
   if (!f) { g_create_error = std::string("cannot open ") + path; return MPC_E_NOENT; }
   u64 r, c, off;
   std::string err;
-  int rc = parse_npy_header(f, &r, &c, &off, err);
+  int rc = mpctrace::parse_npy_header(f, &r, &c, &off, err);
   fclose(f);
   if (rc != MPC_OK) { g_create_error = err; return rc; }
   *rows = r;
@@ -1557,37 +959,8 @@ int mpc_compress_npy(mpc_handle *h, const char *path, uint64_t first_row, uint64
                      uint64_t *rows_done)
 {
   if (!h || !path) return MPC_E_INVAL;
-  return feed_npy(HandleFeed{h}, path, first_row, n_rows, skip_last_row, rows_done);
+  return mpcstage::compress_npy(h->stage, sink_of(h), h->stream, path, first_row, n_rows, skip_last_row, rows_done);
 }
-
-namespace {
-
-// validates the file header of a GPGPU-Sim trace (LoaderGPGPU.cpp:93-119)
-int log_open(const char *path, FILE **out, std::string &err)
-{
-  FILE *f = fopen(path, "rb");
-  if (!f) { err = std::string("Failed to open a file. Check the path of the file: ") + path; return MPC_E_NOENT; }
-  unsigned char hdr[1 + 7 * kLogKeys];
-  if (fread(hdr, 1, sizeof(hdr), f) != sizeof(hdr) || hdr[0] != kLogKeys) {
-    fclose(f);
-    err = "The header of the GPGPU-sim trace file is not valid.";
-    return MPC_E_PARSE;
-  }
-  *out = f;
-  return MPC_OK;
-}
-
-// one request header; false at the end of the file (or inside an incomplete header)
-bool log_next(FILE *f, uint32_t *req_type, uint32_t *req_size)
-{
-  unsigned char h[kLogRecordHeader];
-  if (fread(h, 1, sizeof(h), f) != sizeof(h)) return false;
-  std::memcpy(req_type, h + 38, 4);
-  std::memcpy(req_size, h + 58, 4);
-  return true;
-}
-
-}  // namespace
 
 int mpc_gpgpusim_log_line_size(const char *log_path, uint32_t *line_size)
 {
@@ -1595,10 +968,10 @@ int mpc_gpgpusim_log_line_size(const char *log_path, uint32_t *line_size)
   *line_size = 0;
   FILE *f = nullptr;
   std::string err;
-  int rc = log_open(log_path, &f, err);
+  int rc = mpctrace::log_open(log_path, &f, err);
   if (rc != MPC_OK) return set_err(nullptr, rc, err);
   uint32_t t = 0, sz = 0;
-  if (log_next(f, &t, &sz)) *line_size = sz;
+  if (mpctrace::log_next(f, &t, &sz)) *line_size = sz;
   fclose(f);
   return MPC_OK;
 }
@@ -1606,7 +979,7 @@ int mpc_gpgpusim_log_line_size(const char *log_path, uint32_t *line_size)
 int mpc_compress_gpgpusim_log(mpc_handle *h, const char *log_path, uint64_t *requests_read, uint64_t *lines_done)
 {
   if (!h || !log_path) return MPC_E_INVAL;
-  return feed_gpgpusim_log(HandleFeed{h}, log_path, requests_read, lines_done);
+  return mpcstage::compress_gpgpusim_log(h->stage, sink_of(h), h->stream, log_path, requests_read, lines_done);
 }
 
 // ---- groups ---------------------------------------------------------------
@@ -1630,23 +1003,18 @@ int mpc_group_create(mpc_handle *const *members, size_t n, mpc_group **out)
   mpc_group *g = new (std::nothrow) mpc_group();
   if (!g) return MPC_E_NOMEM;
   g->m.assign(members, members + n);
-  g->L = members[0]->L;
-  g->device = members[0]->device;
+  mpcstage::init(g->stage, members[0]->device, members[0]->L, n);
   group_route(g);
-  bool ok = hipSetDevice(g->device) == hipSuccess;
-  for (int i = 0; i < 2 && ok; i++) {
-    GroupSlot &s = g->slots[i];
-    ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
+  // the streams and events now, not at the first staged call: the members wait for them in sc2_build
+  bool ok = hipSetDevice(g->stage.device) == hipSuccess;
+  for (mpcstage::Slot &s : g->stage.slots)
+    ok = ok && hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
          hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
-    s.d_sizes.assign(n, nullptr); s.h_sizes.assign(n, nullptr); s.user_sizes.assign(n, nullptr);
-    s.d_sel.assign(n, nullptr); s.h_sel.assign(n, nullptr); s.user_sel.assign(n, nullptr);
-  }
   if (!ok) {
     mpc_group_destroy(g);
     return group_err(nullptr, MPC_E_HIP, "hipStreamCreate / hipEventCreate failed for the group's slots");
   }
-  for (mpc_handle *h : g->m)
-    for (int i = 0; i < 2; i++) h->group_streams.push_back(g->slots[i].stream);
+  for (mpc_handle *h : g->m) h->fed_by.push_back(&g->stage);
   *out = g;
   return MPC_OK;
 }
@@ -1654,22 +1022,9 @@ int mpc_group_create(mpc_handle *const *members, size_t n, mpc_group **out)
 void mpc_group_destroy(mpc_group *g)
 {
   if (!g) return;
-  (void)hipSetDevice(g->device);
-  for (int i = 0; i < 2; i++) {
-    GroupSlot &s = g->slots[i];
-    if (s.stream) (void)hipStreamSynchronize(s.stream);
-    for (mpc_handle *h : g->m)
-      h->group_streams.erase(std::remove(h->group_streams.begin(), h->group_streams.end(), s.stream), h->group_streams.end());
-    if (s.h_in) (void)hipHostFree(s.h_in);
-    if (s.d_in) (void)hipFree(s.d_in);
-    for (uint16_t *p : s.d_sizes) if (p) (void)hipFree(p);
-    for (uint16_t *p : s.h_sizes) if (p) (void)hipHostFree(p);
-    for (int8_t *p : s.d_sel) if (p) (void)hipFree(p);
-    for (int8_t *p : s.h_sel) if (p) (void)hipHostFree(p);
-    if (s.done) (void)hipEventDestroy(s.done);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-  }
-  if (g->mini) (void)hipHostFree(g->mini);
+  (void)hipSetDevice(g->stage.device);
+  for (mpc_handle *h : g->m) h->fed_by.erase(std::remove(h->fed_by.begin(), h->fed_by.end(), &g->stage), h->fed_by.end());
+  mpcstage::destroy(g->stage);
   delete g;
 }
 
@@ -1681,26 +1036,7 @@ int mpc_group_compress_batch(mpc_group *g, const uint8_t *lines, uint64_t n, uin
 {
   if (!g || (!lines && n)) return MPC_E_INVAL;
   if (n == 0) return MPC_OK;
-  GHIPCHK(g, hipSetDevice(g->device));
-  if (n <= kMiniLines) return group_small(g, lines, n, sizes, sel);
-  int rc = group_ensure_slots(g);
-  if (rc != MPC_OK) return rc;
-  u64 done = 0;
-  int which = 0;
-  while (done < n) {
-    GroupSlot &s = g->slots[which];
-    rc = group_retire(g, s);   // the slot's previous chunk (overlapped with the other slot's work)
-    if (rc != MPC_OK) break;
-    const u64 take = (n - done) < (u64)g->stage_lines ? (n - done) : (u64)g->stage_lines;
-    parallel_copy(s.h_in, lines + done * (u64)g->L, (size_t)(take * (u64)g->L));
-    rc = group_submit(g, s, take, sizes, sel, done);
-    if (rc != MPC_OK) break;
-    done += take;
-    which ^= 1;
-  }
-  if (rc == MPC_OK) rc = group_finish(g);
-  if (rc != MPC_OK) group_abandon(g);
-  return rc;
+  return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, sizes, sel);
 }
 
 int mpc_group_compress_batch_device(mpc_group *g, const void *d_lines, uint64_t n, uint16_t *const *d_sizes, int8_t *const *d_sel,
@@ -1708,29 +1044,29 @@ int mpc_group_compress_batch_device(mpc_group *g, const void *d_lines, uint64_t 
 {
   if (!g || (!d_lines && n)) return MPC_E_INVAL;
   if (((uintptr_t)d_lines) & 15u) return group_err(g, MPC_E_INVAL, "device line buffer must be 16-byte aligned");
-  GHIPCHK(g, hipSetDevice(g->device));
+  HIPCHK(g, hipSetDevice(g->stage.device));
   return group_launch(g, d_lines, n, d_sizes, d_sel, (hipStream_t)hip_stream);
 }
 
 int mpc_group_compress_npy(mpc_group *g, const char *path, uint64_t first_row, uint64_t n_rows, int skip_last_row, uint64_t *rows_done)
 {
   if (!g || !path) return MPC_E_INVAL;
-  return feed_npy(GroupFeed{g}, path, first_row, n_rows, skip_last_row, rows_done);
+  return mpcstage::compress_npy(g->stage, sink_of(g), nullptr, path, first_row, n_rows, skip_last_row, rows_done);
 }
 
 int mpc_group_compress_gpgpusim_log(mpc_group *g, const char *log_path, uint64_t *requests_read, uint64_t *lines_done)
 {
   if (!g || !log_path) return MPC_E_INVAL;
-  return feed_gpgpusim_log(GroupFeed{g}, log_path, requests_read, lines_done);
+  return mpcstage::compress_gpgpusim_log(g->stage, sink_of(g), nullptr, log_path, requests_read, lines_done);
 }
 
 int mpc_group_sync(mpc_group *g)
 {
   if (!g) return MPC_E_INVAL;
-  GHIPCHK(g, hipSetDevice(g->device));
-  const int rc = group_finish(g);
+  HIPCHK(g, hipSetDevice(g->stage.device));
+  const int rc = mpcstage::finish(g->stage, sink_of(g), nullptr);
   if (rc != MPC_OK) return rc;
-  GHIPCHK(g, hipDeviceSynchronize());   // batches may have been queued on caller streams
+  HIPCHK(g, hipDeviceSynchronize());   // batches may have been queued on caller streams
   return group_members_status(g);
 }
 

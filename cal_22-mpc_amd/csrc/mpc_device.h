@@ -1,6 +1,6 @@
 // mpc_device.h -- parameter blocks shared by the host side (mpc_capi.hip) and the
-// gfx950 kernels (mpc_kernels.hip).  Plain C structs, passed by value as kernel
-// arguments.
+// gfx950 kernels (mpc_kernels.hip, mpc_vpc_lane.hip).  Plain C structs, passed by value as kernel
+// arguments; the launchers that take them are declared in mpc_launch.h.
 #pragma once
 
 #ifndef __HIPCC_RTC__

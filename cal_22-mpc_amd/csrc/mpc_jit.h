@@ -46,8 +46,7 @@
 
 #include "mpc_config.h"
 #include "mpc_device.h"
-
-extern "C" size_t mpc_vpc_lane_ring_plan(const MpcVpcParams *P, unsigned *ring_cfg, int *wpb);
+#include "mpc_launch.h"
 
 namespace mpcjit {
 

@@ -8,6 +8,7 @@
 //   synth_kernel / read_probe_kernel   measurement helpers
 #include "mpc_kernel_common.h"
 #include "mpc_ring.h"
+#include "mpc_launch.h"
 
 // ---------------------------------------------------------------------------
 // generic VPC kernel: one lane per line, byte loops, any configuration.

@@ -1,0 +1,67 @@
+// mpc_launch.h -- every host-callable launcher of the kernel translation units, declared once.
+//
+// The launchers have C linkage, so a declaration that drifted from its definition would still link and then misbehave.
+// This header is therefore included by the callers (mpc_capi.hip, mpc_jit.h) AND by the units that define the
+// launchers (mpc_kernels.hip, mpc_sc2.hip, mpc_pattern.hip, the host section of mpc_vpc_lane.hip): the compiler sees
+// declaration and definition together and refuses a mismatch.  Host code only -- the run-time compiled source of
+// mpc_jit.h (-DMPC_LANE_JIT) never sees it, and it is not one of the files that key the code object cache.
+//
+// The parameter blocks are only named here (their definitions: mpc_device.h, mpc_sc2.h, mpc_pattern.h).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+struct MpcVpcParams;
+struct MpcBaselinesArgs;
+struct MpcSc2Table;
+struct MpcPatternSet;
+
+extern "C" {
+// mpc_kernels.hip
+size_t mpc_vpc_generic_smem(const MpcVpcParams *P);
+hipError_t mpc_launch_vpc_generic(const void *d_lines, unsigned long long n_lines, const MpcVpcParams *P, uint16_t *d_sizes, int8_t *d_sel,
+                                  unsigned long long *d_stats, int grid, hipStream_t stream);
+hipError_t mpc_launch_bdi(const void *d_lines, unsigned long long n_lines, int L, uint16_t *d_sizes, int8_t *d_sel, unsigned long long *d_stats,
+                          int grid, hipStream_t stream);
+hipError_t mpc_launch_fpc(const void *d_lines, unsigned long long n_lines, int L, uint16_t *d_sizes, int8_t *d_sel, unsigned long long *d_stats,
+                          int grid, hipStream_t stream);
+hipError_t mpc_launch_bpc(const void *d_lines, unsigned long long n_lines, int L, uint16_t *d_sizes, int8_t *d_sel, unsigned long long *d_stats,
+                          int grid, hipStream_t stream);
+hipError_t mpc_launch_baselines(const void *d_lines, unsigned long long n_lines, int L, const MpcBaselinesArgs *A, int grid, hipStream_t stream);
+hipError_t mpc_launch_synth(void *d_out, unsigned long long n_lines, unsigned L, int kind, unsigned long long first_line, unsigned long long seed,
+                            const uint32_t *d_sine, hipStream_t stream);
+hipError_t mpc_launch_read_probe(const void *d_buf, unsigned long long bytes, uint32_t *d_sink, int grid, hipStream_t stream);
+
+// mpc_vpc_lane.hip (the dispatcher unit, and one unit per line size)
+int mpc_vpc_lane_unrolled(const MpcVpcParams *P);
+size_t mpc_vpc_lane_ring_plan(const MpcVpcParams *P, unsigned *ring_cfg, int *wpb);
+size_t mpc_vpc_lane_smem(const MpcVpcParams *P);
+hipError_t mpc_launch_vpc_lane(const void *d_lines, unsigned long long n_lines, const MpcVpcParams *P, uint16_t *d_sizes, int8_t *d_sel,
+                               unsigned long long *d_stats, int grid, hipStream_t stream);
+hipError_t mpc_launch_vpc_lane_w8(const void *d_lines, unsigned long long n_lines, const MpcVpcParams *P, uint16_t *d_sizes, int8_t *d_sel,
+                                  unsigned long long *d_stats, int grid, hipStream_t stream);
+hipError_t mpc_launch_vpc_lane_w16(const void *d_lines, unsigned long long n_lines, const MpcVpcParams *P, uint16_t *d_sizes, int8_t *d_sel,
+                                   unsigned long long *d_stats, int grid, hipStream_t stream);
+hipError_t mpc_launch_vpc_lane_w32(const void *d_lines, unsigned long long n_lines, const MpcVpcParams *P, uint16_t *d_sizes, int8_t *d_sel,
+                                   unsigned long long *d_stats, int grid, hipStream_t stream);
+hipError_t mpc_launch_vpc_lane_jit(hipFunction_t fn_stats, hipFunction_t fn_lines, const void *d_lines, unsigned long long n_lines,
+                                   const MpcVpcParams *P, uint16_t *d_sizes, int8_t *d_sel, unsigned long long *d_stats, int grid,
+                                   hipStream_t stream);
+
+// mpc_sc2.hip
+hipError_t mpc_launch_sc2_count(const void *d_lines, unsigned long long n_lines, int L, unsigned long long *d_tab, unsigned long long mask,
+                                uint16_t *d_sizes, int8_t *d_sel, unsigned long long *d_stats, hipStream_t stream);
+hipError_t mpc_launch_sc2_hist(const unsigned long long *d_tab, unsigned long long n_slots, unsigned long long prefix, int shift, uint32_t *d_hist,
+                               int grid, hipStream_t stream);
+hipError_t mpc_launch_sc2_collect(const unsigned long long *d_tab, unsigned long long n_slots, unsigned long long threshold,
+                                  unsigned long long *d_out, uint32_t *d_count, int grid, hipStream_t stream);
+hipError_t mpc_launch_sc2_size(const void *d_lines, unsigned long long n_lines, int L, const MpcSc2Table *T, uint16_t *d_sizes, int8_t *d_sel,
+                               unsigned long long *d_stats, int grid, hipStream_t stream);
+
+// mpc_pattern.hip
+hipError_t mpc_launch_pattern(const void *d_lines, unsigned long long n_lines, int L, uint16_t *d_sizes, int8_t *d_sel,
+                              unsigned long long *d_stats, int grid, hipStream_t stream);
+hipError_t mpc_launch_pattern_set(const void *d_lines, uint32_t n_lines, int L, const MpcPatternSet *S, unsigned long long *d_stats,
+                                  int compare_grid, hipStream_t stream);
+}

@@ -1,5 +1,5 @@
-// mpc_pattern.h -- what the host side (mpc_capi.hip) and the gfx950 kernels of the Pattern analyser
-// (mpc_pattern.hip; reference src/compressor/Pattern.{h,cpp}, LRU.h) share: the raw statistics layout and the
+// mpc_pattern.h -- what the host side (mpc_capi.hip: launch_pattern, pattern_status) and the gfx950 kernels of the
+// Pattern analyser (mpc_pattern.hip, launchers in mpc_launch.h; reference src/compressor/Pattern.{h,cpp}, LRU.h) share: the raw statistics layout and the
 // control block of the distinct-line set.
 #pragma once
 

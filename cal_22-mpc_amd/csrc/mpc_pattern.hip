@@ -45,6 +45,7 @@
 // an equal line may just have joined); a winner that was given a number beyond the capacity raises it too.
 #include "mpc_kernel_common.h"
 #include "mpc_pattern.h"
+#include "mpc_launch.h"
 
 constexpr int kThreads = 256;
 // the byte histogram's spreading (development switches): interleaved copies picked by lane >> 2, and the

@@ -1,5 +1,5 @@
 // mpc_sc2.h -- SC2 (reference src/compressor/SC2.cpp): the host side of the code table, shared by the C ABI
-// (mpc_capi.hip) and the kernels (mpc_sc2.hip).
+// (mpc_capi.hip: sc2_build, launch_sc2) and the kernels (mpc_sc2.hip; their launchers: mpc_launch.h).
 //
 //   code_lengths()   the reference's table build, step for step: eviction to the 1024 largest (freq, symbol) pairs
 //                    (SC2.cpp:292-308), MinHeap over the kept symbols in ascending symbol order (:24-37), the Huffman

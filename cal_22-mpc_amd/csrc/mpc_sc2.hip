@@ -18,6 +18,7 @@
 // all-zero sample sends one atomic per workgroup, not one per word, to the zero word's slot.
 #include "mpc_kernel_common.h"
 #include "mpc_sc2.h"
+#include "mpc_launch.h"
 
 constexpr int kCountThreads = 256;
 constexpr int kCountWords = 4096;             // words per workgroup

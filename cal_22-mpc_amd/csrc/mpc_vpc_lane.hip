@@ -1661,6 +1661,7 @@ static bool lane_has_line_size(int L)
 #endif   // !MPC_LANE_JIT
 }  // namespace
 #ifndef MPC_LANE_JIT
+#include "mpc_launch.h"
 
 // Build layout.  Compiled as it is, this file holds every line size (development builds).  The product build
 // (cal_22-mpc_amd/build.py) compiles it four times in parallel: -DMPC_LANE_W=8 / 16 / 32 give the kernels of one

@@ -780,6 +780,44 @@ def test_stager_multi_chunk_and_npy(mpc, oracle, configs, traces, tmp_path):
     assert (ev.stats_vector() == o.stats_vector()).all()
 
 
+def test_stager_allocates_per_line_outputs_when_first_asked(mpc, traces, tmp_path):
+    """A handle's per-line output buffers exist per slot from the first call that asks for that output (as a group's
+    always did): calls asking for neither, sizes only, clusters only and both, across a slot boundary (a slot holds
+    2^19 lines of 128 B), then the in-place path; every array equals a fresh handle's that was asked for both."""
+    L, n = 128, (1 << 19) + 513
+    lines = traces.structured(n, L)
+    fresh = mpc.BDI(L)
+    s_ref, c_ref = fresh.compress_lines(lines)
+    v_ref = fresh.stats_vector()
+    fresh.close()
+    small = mpc.BDI(L)
+    small.compress_lines(lines[:512])
+    v_small = small.stats_vector()
+    small.close()
+
+    ev = mpc.BDI(L)
+    assert ev.compress_lines(lines, want_sizes=False, want_selected=False) == (None, None)
+    s, c = ev.compress_lines(lines, want_selected=False)
+    assert c is None and (s == s_ref).all()
+    s, c = ev.compress_lines(lines, want_sizes=False)
+    assert s is None and (c == c_ref).all()
+    s, c = ev.compress_lines(lines)
+    assert (s == s_ref).all() and (c == c_ref).all()
+    assert (ev.stats_vector() == 4 * v_ref).all()
+    # a failed call leaves nothing behind: the next one delivers as before
+    p = traces.save_npy(str(tmp_path / "narrow.npy"), np.zeros((8, 32), dtype=np.uint8))
+    with pytest.raises(mpc.MpcError) as e:
+        ev.compress_npy(p)
+    assert e.value.code == -22 and "trace line size 32 differs" in str(e.value)
+    s, c = ev.compress_lines(lines)
+    assert (s == s_ref).all() and (c == c_ref).all()
+    # in place (<= 512 lines), clusters only
+    s, c = ev.compress_lines(lines[:512], want_sizes=False)
+    assert s is None and (c == c_ref[:512]).all()
+    assert (ev.stats_vector() == 5 * v_ref + v_small).all()
+    ev.close()
+
+
 def test_gpgpusim_log_streaming(mpc, oracle, configs, traces, tmp_path):
     """mpc_compress_gpgpusim_log: several staging chunks, every request type, an incomplete
     trailing request; against the oracle on oracle/gpgpusim_log.py's reading of the file."""

@@ -8,6 +8,7 @@
 the variant against the CPU oracle on a mixed bag of 64-byte lines, then times the kernel on each
 workload (256 Mi lines resident, HIP events, like bench.py).  Variants are interleaved across rounds.
 """
+import importlib
 import json
 import os
 import subprocess
@@ -19,22 +20,31 @@ CSRC = os.path.join(ROOT, "cal_22-mpc_amd", "csrc")
 
 
 def build(specs):
+    sys.path.insert(0, ROOT)
+    units = importlib.import_module("cal_22-mpc_amd.build").lib_units      # the library's own translation units
     os.makedirs(OUT, exist_ok=True)
-    procs = []
+    procs, links = [], []
     for spec in specs:
         name, _, flags = spec.partition("=")
         name, _, src = name.partition("@")          # NAME@DIR: sources from another csrc directory (a saved baseline)
         csrc = os.path.abspath(src) if src else CSRC
         # NAME: the timed library; NAME_t: the same with -DMPC_TESTING=1 (honours MPC_TEST_GRID) for the capped-grid parity check
         for suffix, extra in (("", []), ("_t", ["-DMPC_TESTING=1"])):
-            so = os.path.join(OUT, f"libmpc_hip_{name}{suffix}.so")
-            cmd = ["hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-DMPC_DEV_ONLY64", *flags.split(), *extra,
-                   "-shared", "-o", so] + [os.path.join(csrc, f) for f in ("mpc_vpc_lane.hip", "mpc_kernels.hip", "mpc_capi.hip")]
-            procs.append((name + suffix, subprocess.Popen(cmd)))
-    bad = [n for n, p in procs if p.wait() != 0]
+            objdir = os.path.join(OUT, f"obj_{name}{suffix}")
+            os.makedirs(objdir, exist_ok=True)
+            objs = []
+            for source, obj, unit_flags in units(csrc):
+                objs.append(os.path.join(objdir, obj))
+                cmd = ["hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-DMPC_DEV_ONLY64", *flags.split(), *extra, *unit_flags,
+                       "-c", source, "-o", objs[-1]]
+                procs.append((name + suffix, subprocess.Popen(cmd)))
+            links.append((name + suffix, ["hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", "-o",
+                                          os.path.join(OUT, f"libmpc_hip_{name}{suffix}.so"), *objs]))
+    bad = sorted({n for n, p in procs if p.wait() != 0})
+    bad += [n for n, cmd in links if n not in bad and subprocess.run(cmd).returncode != 0]
     if bad:
         raise SystemExit(f"build failed: {bad}")
-    print("built", [n for n, _ in procs])
+    print("built", [n for n, _ in links])
 
 
 CHILD = r'''

@@ -6,15 +6,14 @@
 #   W=random_u32 VARIANTS="a b a b" tools/ablate.sh run
 set -e
 cd "$(dirname "$0")/.."
-C=cal_22-mpc_amd/csrc
 mkdir -p tools/ablate
 V=${VARIANTS:-0 1 2 4 8 15}
 if [ "$1" == "build" ]; then
   rm -f tools/ablate/*.so
-  for a in $V; do
-    hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -D${FLAG:-MPC_ABLATE}=$a -shared -o tools/ablate/libmpc_hip_$a.so $C/mpc_vpc_lane.hip $C/mpc_kernels.hip $C/mpc_capi.hip &
-  done
-  wait
+  # tools/ab.py links the library's own list of translation units (64-byte lines only: -DMPC_DEV_ONLY64)
+  specs=""
+  for a in $V; do specs="$specs $a=-D${FLAG:-MPC_ABLATE}=$a"; done
+  python tools/ab.py build $specs
 else
   for a in $V; do
     MPC_HIP_LIB=$PWD/tools/ablate/libmpc_hip_$a.so python - <<PY

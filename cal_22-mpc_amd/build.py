@@ -46,7 +46,7 @@ def lib_units(csrc: str = CSRC):
     lane = os.path.join(csrc, "mpc_vpc_lane.hip")
     units = [(lane, f"lane_w{w}.o", [f"-DMPC_LANE_W={w}"]) for w in (16, 32, 8, 0)]
     units += [(os.path.join(csrc, "mpc_kernels.hip"), "kernels.o", []),
-              (os.path.join(csrc, "mpc_kernels.hip"), "baselines.o", ["-DMPC_BASELINES_UNIT=1"]),      # the group's shared kernel
+              (os.path.join(csrc, "mpc_baselines.hip"), "baselines.o", []),      # the group's shared kernel
               (os.path.join(csrc, "mpc_sc2.hip"), "sc2.o", []),
               (os.path.join(csrc, "mpc_pattern.hip"), "pattern.o", []),
               (os.path.join(csrc, "mpc_capi.hip"), "capi.o", [])]
@@ -56,7 +56,7 @@ def lib_units(csrc: str = CSRC):
 def build_lib(force: bool = False, verbose: bool = False, test: bool = False) -> str:
     """libmpc_hip.so (test=True: libmpc_hip_test.so, the same sources with -DMPC_TESTING=1).  The translation units
     are compiled in parallel: the lane kernel file once per line size (-DMPC_LANE_W=8/16/32) plus its dispatcher
-    (-DMPC_LANE_W=0), the other kernels (and once more for the group's shared kernel alone), the C ABI; then linked."""
+    (-DMPC_LANE_W=0), every other source once; then linked."""
     LIB = TEST_LIB if test else globals()["LIB"]
     deps = _sources(CSRC) + [os.path.join(ROOT, "include", "mpc_hip.h")]
     if not force and _newer(LIB, deps):

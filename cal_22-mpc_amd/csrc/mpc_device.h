@@ -101,7 +101,7 @@ static inline uint64_t mpc_vpc_raw_len(int K, int bins) { return 2ull * (uint64_
 /*   BPC: [0,7) Counts (BPCPattern order)  [7] TotalWords  [8] compressed_bits  */
 #define MPC_BPC_RAW_LEN 9
 
-/* The stateless baselines evaluated by one launch (baselines_kernel, mpc_kernels.hip): per member its optional per-line
+/* The stateless baselines evaluated by one launch (baselines_kernel, mpc_baselines.hip): per member its optional per-line
  * outputs and its raw statistics.  raw == NULL: the algorithm is not a member of the launch.                      */
 struct MpcBaselineOut {
   uint16_t *sizes;

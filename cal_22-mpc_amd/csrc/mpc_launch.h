@@ -2,9 +2,10 @@
 //
 // The launchers have C linkage, so a declaration that drifted from its definition would still link and then misbehave.
 // This header is therefore included by the callers (mpc_capi.hip, mpc_jit.h) AND by the units that define the
-// launchers (mpc_kernels.hip, mpc_sc2.hip, mpc_pattern.hip, the host section of mpc_vpc_lane.hip): the compiler sees
-// declaration and definition together and refuses a mismatch.  Host code only -- the run-time compiled source of
-// mpc_jit.h (-DMPC_LANE_JIT) never sees it, and it is not one of the files that key the code object cache.
+// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, the host section of mpc_vpc_lane.hip):
+// the compiler sees declaration and definition together and refuses a mismatch.  Host code only -- the run-time
+// compiled source of mpc_jit.h (-DMPC_LANE_JIT) never sees it, and it is not one of the files that key the code
+// object cache.
 //
 // The parameter blocks are only named here (their definitions: mpc_device.h, mpc_sc2.h, mpc_pattern.h).
 #pragma once
@@ -28,10 +29,12 @@ hipError_t mpc_launch_fpc(const void *d_lines, unsigned long long n_lines, int L
                           int grid, hipStream_t stream);
 hipError_t mpc_launch_bpc(const void *d_lines, unsigned long long n_lines, int L, uint16_t *d_sizes, int8_t *d_sel, unsigned long long *d_stats,
                           int grid, hipStream_t stream);
-hipError_t mpc_launch_baselines(const void *d_lines, unsigned long long n_lines, int L, const MpcBaselinesArgs *A, int grid, hipStream_t stream);
 hipError_t mpc_launch_synth(void *d_out, unsigned long long n_lines, unsigned L, int kind, unsigned long long first_line, unsigned long long seed,
                             const uint32_t *d_sine, hipStream_t stream);
 hipError_t mpc_launch_read_probe(const void *d_buf, unsigned long long bytes, uint32_t *d_sink, int grid, hipStream_t stream);
+
+// mpc_baselines.hip
+hipError_t mpc_launch_baselines(const void *d_lines, unsigned long long n_lines, int L, const MpcBaselinesArgs *A, int grid, hipStream_t stream);
 
 // mpc_vpc_lane.hip (the dispatcher unit, and one unit per line size)
 int mpc_vpc_lane_unrolled(const MpcVpcParams *P);

@@ -1,6 +1,6 @@
 // mpc_ring.h -- lines from global memory straight into LDS (global_load_lds_dwordx4) and out of it one line per
-// lane: the helpers of the per-wave line rings (mpc_vpc_lane.hip explains the design; mpc_kernels.hip uses the same
-// ring for the BDI baseline).  gfx950 only.
+// lane: the helpers of the per-wave line rings (mpc_vpc_lane.hip explains the design; ring_feed of mpc_baselines.h uses the
+// same ring for the BDI baseline and the group's kernel).  gfx950 only.
 #pragma once
 #include "mpc_kernel_common.h"
 

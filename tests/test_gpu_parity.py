@@ -1170,6 +1170,49 @@ print("ROUTES " + json.dumps(res))
     assert b["bdi_deferred"] > 0 and b["bdi_drains"] > 64 and b["bdi_deferred"] <= 64 * b["bdi_drains"], b
 
 
+def test_baseline_accumulators_flush_inside_the_loop(oracle, traces):
+    """A lane of fpc_kernel, bpc_kernel and baselines_kernel keeps its totals in registers and flushes them into the
+    workgroup's counts inside the loop: BPC's 16-bit pattern fields after 1023 lines (a field gains up to 33 counts per
+    line and would overflow after 65536 / 33 = 1986 lines).  With the grid capped to one workgroup of 256 lanes
+    (MPC_TEST_GRID, test library only) every lane walks more than 1986 lines of one launch: 2100 x 256 + 5 x 64 + 37
+    lines, random words but for 3000 structured and 2000 counter lines, permuted, the end ragged.  At 128 bytes the
+    random lines put 32.7 of a line's 33 planes into one field (Uncomp), 67 000 in the 2048 lines a lane walks in the
+    first 64 MiB chunk: a lane that did not flush would carry into the next field and the statistics would differ.  (At
+    32 bytes a plane has 7 bits and 28.6 per line are Uncomp: the fields stay below 2^16 either way, and the case
+    checks the flushes that run.)  Solo FPC and BPC, and a BDI + FPC + BPC group (32 bytes: the ring feed, 128 bytes:
+    the staged feed of the group's kernel), per-line results and statistics against the oracle, in a fresh process (the
+    cap is read once per process)."""
+    code = r"""
+n = 2100 * 256 + 5 * 64 + 37
+for L in (32, 128):
+    lines = np.concatenate([T.random_u32(n - 5000, L), T.structured(3000, L, seed=3), T.counters_u32(2000, L)])
+    lines = lines[np.random.default_rng(11).permutation(n)]
+    bo, fo, po = O.BdiOracle(L), O.FpcOracle(L), O.BpcOracle(L)
+    want = {"BDI": bo.compress(lines), "FPC": (fo.compress(lines), np.zeros(n, np.int8)), "BPC": (po.compress(lines), np.zeros(n, np.int8))}
+    want_stats = {"BDI": bo.stats_vector(), "FPC": fo.stats_vector(), "BPC": po.stats_vector()}
+    def check(tag, ev, out, c):
+        assert (out[0] == want[c][0]).all() and (out[1] == want[c][1]).all(), (L, tag, c, "per-line results")
+        assert (ev.stats_vector() == want_stats[c]).all(), (L, tag, c, ev.stats_vector().tolist(), want_stats[c].tolist())
+    for c in ("FPC", "BPC"):
+        ev = getattr(mpc, c)(L)
+        check("solo", ev, ev.compress_lines(lines), c)
+        ev.close()
+    comps = ("BDI", "FPC", "BPC")
+    members = [getattr(mpc, c)(L) for c in comps]
+    group = mpc.EvaluatorSet(members)
+    assert group.form == "BDI+FPC+BPC: one kernel", group.form
+    outs = group.compress_lines(lines)
+    for c, ev, out in zip(comps, members, outs):
+        check("group", ev, out, c)
+    group.close()
+    for ev in members:
+        ev.close()
+print("ROUTES " + json.dumps({"lines": n}))
+"""
+    res = _run_with_test_library(code, grid_cap=1)
+    assert res["lines"] // 256 > 65536 // 33          # every lane passed the line count at which an unflushed field overflows
+
+
 def test_general_layout_twins_under_a_capped_grid(oracle, configs, traces, tmp_path):
     """The general-layout twins (RootIndex 1..15, whole-plane truncation) share the streaming loop of the plain unrolled
     kernels: with the grid capped to one workgroup (test library) every wave reuses its ring stages hundreds of times,

@@ -2,13 +2,15 @@
 """Development only: same-box A/B timing of variant builds of libmpc_hip.so.
 
     tools/ab.py build NAME[@CSRC_DIR][=FLAGS] ...       # here: tools/ablate/libmpc_hip_NAME.so, each with -DMPC_DEV_ONLY64 FLAGS
+                                                        # (@CSRC_DIR: the csrc of another tree, e.g. a worktree of the parent commit;
+                                                        #  its translation units are those of the build.py beside it)
     tools/ab.py run [--rounds R] [--workloads a,b] [--algo VPC] NAME ...   # on the GPU box (one gpurun call)
 
 `run` starts one child process per (variant, round) -- a process binds one library -- which first checks
 the variant against the CPU oracle on a mixed bag of 64-byte lines, then times the kernel on each
 workload (256 Mi lines resident, HIP events, like bench.py).  Variants are interleaved across rounds.
 """
-import importlib
+import importlib.util
 import json
 import os
 import subprocess
@@ -19,21 +21,28 @@ OUT = os.path.join(ROOT, "tools", "ablate")
 CSRC = os.path.join(ROOT, "cal_22-mpc_amd", "csrc")
 
 
+def lib_units(csrc):
+    """The translation units of the tree that csrc belongs to: lib_units() of the build.py beside it (another commit may
+    split its sources differently)."""
+    spec = importlib.util.spec_from_file_location("mpc_build_beside_csrc", os.path.join(os.path.dirname(csrc), "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.lib_units(csrc)
+
+
 def build(specs):
-    sys.path.insert(0, ROOT)
-    units = importlib.import_module("cal_22-mpc_amd.build").lib_units      # the library's own translation units
     os.makedirs(OUT, exist_ok=True)
     procs, links = [], []
     for spec in specs:
         name, _, flags = spec.partition("=")
-        name, _, src = name.partition("@")          # NAME@DIR: sources from another csrc directory (a saved baseline)
+        name, _, src = name.partition("@")          # NAME@DIR: the csrc directory of another tree (a worktree of the parent)
         csrc = os.path.abspath(src) if src else CSRC
         # NAME: the timed library; NAME_t: the same with -DMPC_TESTING=1 (honours MPC_TEST_GRID) for the capped-grid parity check
         for suffix, extra in (("", []), ("_t", ["-DMPC_TESTING=1"])):
             objdir = os.path.join(OUT, f"obj_{name}{suffix}")
             os.makedirs(objdir, exist_ok=True)
             objs = []
-            for source, obj, unit_flags in units(csrc):
+            for source, obj, unit_flags in lib_units(csrc):
                 objs.append(os.path.join(objdir, obj))
                 cmd = ["hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-DMPC_DEV_ONLY64", *flags.split(), *extra, *unit_flags,
                        "-c", source, "-o", objs[-1]]

@@ -10,7 +10,8 @@ mkdir -p tools/ablate
 V=${VARIANTS:-0 1 2 4 8 15}
 if [ "$1" == "build" ]; then
   rm -f tools/ablate/*.so
-  # tools/ab.py links the library's own list of translation units (64-byte lines only: -DMPC_DEV_ONLY64)
+  # tools/ab.py links the translation units that build.py lists (for NAME@DIR: the build.py beside DIR), 64-byte lines
+  # only (-DMPC_DEV_ONLY64)
   specs=""
   for a in $V; do specs="$specs $a=-D${FLAG:-MPC_ABLATE}=$a"; done
   python tools/ab.py build $specs

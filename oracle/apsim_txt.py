@@ -13,7 +13,10 @@ Follows trace::apsim::LoaderGPGPU (reference src/loader/LoaderGPGPU.cpp:116-525)
   * getCacheline64 (:330-441): two consecutive beats of one channel make a 64-byte line (first beat
     first); beats without a partner at the end of the file are dropped.
 
-Parity is pinned by the source reading only: the reference ships no .txt fixture."""
+Parity is pinned by tests/golden/ref_loader_vectors.json, recorded from the reference's LoaderGPGPU.cpp compiled
+unmodified (tests/test_loader_ref.py: the lines of a freshly constructed loader at 32 and 64 bytes).  After a Reset() the
+reference re-uses beats left in its channel queues (64-byte lines only); that is recorded there too and not restated
+here.  Traces larger than the fixture's rest on the source reading."""
 import numpy as np
 
 NUM_CH = 4

@@ -13,8 +13,10 @@ Follows trace::gpgpusim::LoaderGPGPU (reference src/loader/LoaderGPGPU.cpp):
 and the driver's filter (reference src/main.cpp:222-224): only GLOBAL_ACC_R (0) and
 GLOBAL_ACC_W (4) requests are evaluated.
 
-Parity is pinned by the format as read from the source only: the reference ships no
-.log fixture ("loader parity unpinned" in DESIGN.md)."""
+Parity is pinned by tests/golden/ref_loader_vectors.json, recorded from the reference's
+LoaderGPGPU.cpp compiled unmodified (tests/test_loader_ref.py: line size, GetNumLines,
+the evaluated lines' count and digest for every case); traces larger than the fixture's
+rest on the source reading."""
 import numpy as np
 
 NUM_KEYS = 17

@@ -401,7 +401,7 @@ def test_per_line_drop_in_matches_batch(cli, oracle, configs, traces, tmp_path):
 def test_cli_apsim_txt(cli, oracle, configs, traces, tmp_path):
     """APSim .txt traffic files through the CLI (reference main.cpp:80-81: 32-byte lines): the data beats of
     handshaking channels, batch and per-line loop alike.  Expected text from the oracle run on
-    oracle/apsim_txt.py's reading of the same file (parity unpinned: no fixture exists)."""
+    oracle/apsim_txt.py's reading of the same file (pinned to the reference's loader by tests/test_loader_ref.py)."""
     import sys
     sys.path.insert(0, ROOT)
     from oracle import apsim_txt as A

@@ -171,12 +171,43 @@ def jit_compile_check(cfg) -> int:
     return int(n)
 
 
-class _Evaluator:
-    """Common part of VPC / BDI: owns one ``mpc_handle``."""
+def _as_lines(lines, line_size: int) -> np.ndarray:
+    """The ``[n, L] uint8`` argument of ``compress_lines``, C-contiguous."""
+    lines = np.ascontiguousarray(lines, dtype=np.uint8)
+    if lines.ndim != 2 or lines.shape[1] != line_size:
+        raise ValueError(f"expected [n, {line_size}] uint8")
+    return lines
 
-    def __init__(self):
+
+def _ratio(original, compressed, lines) -> float:
+    """VPC (``VPC.h:49-60``): inf once lines of 0 bits are all there are, 0 before the first line."""
+    if not lines:
+        return 0.0
+    return float(original) / float(compressed) if compressed else float("inf")
+
+
+def _ratio_or_zero(original, compressed, lines) -> float:
+    """BDI, FPC, BPC and SC2: 0 while there are no compressed bits."""
+    return float(original) / float(compressed) if compressed else 0.0
+
+
+def _totals(v, ratio=_ratio_or_zero) -> Dict:
+    """What every ``result()`` starts with, from the head of the statistics vector."""
+    return {"lines": int(v[0]), "original_bits": int(v[1]), "compressed_bits": int(v[2]), "comp_ratio": ratio(v[1], v[2], v[0])}
+
+
+class _Evaluator:
+    """Common part of the six evaluators: creates and owns one ``mpc_handle``."""
+
+    def __init__(self, create: str, *args):
+        """``create``: name of the library's create function; ``args``: its arguments in front of the handle."""
         self._h = C.c_void_p()
         self.info = Info()
+        rc = getattr(lib(), create)(*args, C.byref(self._h))
+        if rc != 0:
+            raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
+        self._finish()
+        self.kernel_path = self.info.kernel_path
 
     def _check(self, rc: int) -> None:
         if rc != 0:
@@ -204,9 +235,7 @@ class _Evaluator:
                        want_selected: bool = True) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
         """Host buffer [n, L] uint8 -> (size_bits uint16[n], selected int8[n]); staged
         through the pinned double buffers.  Statistics accumulate in the handle."""
-        lines = np.ascontiguousarray(lines, dtype=np.uint8)
-        if lines.ndim != 2 or lines.shape[1] != self.line_size:
-            raise ValueError(f"expected [n, {self.line_size}] uint8")
+        lines = _as_lines(lines, self.line_size)
         n = lines.shape[0]
         sizes = np.empty(n, dtype=np.uint16) if want_sizes else None
         sel = np.empty(n, dtype=np.int8) if want_selected else None
@@ -278,17 +307,12 @@ class VPC(_Evaluator):
     """``comp::VPC(configPath)`` (reference ``VPC.h:244-249``)."""
 
     def __init__(self, config, device: int = -1):
-        super().__init__()
         if isinstance(config, dict):
-            rc = lib().mpc_create_vpc_from_string(json.dumps(config).encode(), device, C.byref(self._h))
+            super().__init__("mpc_create_vpc_from_string", json.dumps(config).encode(), device)
         else:
-            rc = lib().mpc_create_vpc(str(config).encode(), device, C.byref(self._h))
-        if rc != 0:
-            raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
-        self._finish()
+            super().__init__("mpc_create_vpc", str(config).encode(), device)
         self.num_modules = self.info.num_modules
         self.hist_bins = self.info.hist_bins
-        self.kernel_path = self.info.kernel_path
         self.path_reason = (lib().mpc_path_reason(self._h) or b"").decode()   # why the generic kernel, if it is
         # "unrolled" | "unrolled, general layout" | "unrolled, compiled at creation[ (from the cache)]" | "run-time loop" | "generic"
         self.kernel_form = (lib().mpc_kernel_form(self._h) or b"").decode()
@@ -302,54 +326,33 @@ class BDI(_Evaluator):
     """``comp::BDI(lineSize)`` (reference ``BDI.h:90-107``)."""
 
     def __init__(self, line_size: int, device: int = -1):
-        super().__init__()
-        rc = lib().mpc_create_bdi(line_size, device, C.byref(self._h))
-        if rc != 0:
-            raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
-        self._finish()
-        self.kernel_path = self.info.kernel_path
+        super().__init__("mpc_create_bdi", line_size, device)
 
     def result(self) -> Dict:
         v = self.stats_vector()
-        return {"lines": int(v[0]), "original_bits": int(v[1]), "compressed_bits": int(v[2]),
-                "comp_ratio": (float(v[1]) / float(v[2])) if v[2] else 0.0,
-                "counts": [int(x) for x in v[3:12]]}
+        return {**_totals(v), "counts": [int(x) for x in v[3:12]]}
 
 
 class FPC(_Evaluator):
     """``comp::FPC(lineSize)`` (reference ``FPC.h:91-103``); per-line ``selected`` is always 0."""
 
     def __init__(self, line_size: int, device: int = -1):
-        super().__init__()
-        rc = lib().mpc_create_fpc(line_size, device, C.byref(self._h))
-        if rc != 0:
-            raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
-        self._finish()
-        self.kernel_path = self.info.kernel_path
+        super().__init__("mpc_create_fpc", line_size, device)
 
     def result(self) -> Dict:
         v = self.stats_vector()
-        return {"lines": int(v[0]), "original_bits": int(v[1]), "compressed_bits": int(v[2]),
-                "comp_ratio": (float(v[1]) / float(v[2])) if v[2] else 0.0,
-                "total_words": int(v[3:11].sum()), "counts": [int(x) for x in v[3:11]]}
+        return {**_totals(v), "total_words": int(v[3:11].sum()), "counts": [int(x) for x in v[3:11]]}
 
 
 class BPC(_Evaluator):
     """``comp::BPC(lineSize)`` (reference ``BPC.h:90-107``); per-line ``selected`` is always 0."""
 
     def __init__(self, line_size: int, device: int = -1):
-        super().__init__()
-        rc = lib().mpc_create_bpc(line_size, device, C.byref(self._h))
-        if rc != 0:
-            raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
-        self._finish()
-        self.kernel_path = self.info.kernel_path
+        super().__init__("mpc_create_bpc", line_size, device)
 
     def result(self) -> Dict:
         v = self.stats_vector()
-        return {"lines": int(v[0]), "original_bits": int(v[1]), "compressed_bits": int(v[2]),
-                "comp_ratio": (float(v[1]) / float(v[2])) if v[2] else 0.0,
-                "total_words": int(v[3]), "counts": [int(x) for x in v[4:11]]}
+        return {**_totals(v), "total_words": int(v[3]), "counts": [int(x) for x in v[4:11]]}
 
 
 class SC2(_Evaluator):
@@ -358,13 +361,8 @@ class SC2(_Evaluator):
     Per-line ``selected``: 0 for a warm-up line, 1 for a line sized against the table."""
 
     def __init__(self, line_size: int, sampling_lines: int, device: int = -1):
-        super().__init__()
-        rc = lib().mpc_create_sc2(line_size, sampling_lines, device, C.byref(self._h))
-        if rc != 0:
-            raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
-        self._finish()
+        super().__init__("mpc_create_sc2", line_size, sampling_lines, device)
         self.sampling_lines = int(sampling_lines)
-        self.kernel_path = self.info.kernel_path
 
     @property
     def kernel_form(self) -> str:
@@ -374,9 +372,7 @@ class SC2(_Evaluator):
     def result(self) -> Dict:
         """``CompResult`` (OriginalSize, CompressedSize, CompRatio; name "SC2-Huffman") plus the SC2 counters."""
         v = self.stats_vector()
-        return {"name": "SC2-Huffman", "lines": int(v[0]), "original_bits": int(v[1]), "compressed_bits": int(v[2]),
-                "comp_ratio": (float(v[1]) / float(v[2])) if v[2] else 0.0, "warmup_lines": int(v[3]),
-                "table_symbols": int(v[4]), "words_in_table": int(v[5])}
+        return {"name": "SC2-Huffman", **_totals(v), "warmup_lines": int(v[3]), "table_symbols": int(v[4]), "words_in_table": int(v[5])}
 
     def table(self) -> Tuple[np.ndarray, np.ndarray]:
         """(symbols uint32, code lengths uint16) in ascending symbol order; empty before line S."""
@@ -419,12 +415,7 @@ class Pattern(_Evaluator):
     raises ``MpcError`` instead).  One object per trace and per GPU."""
 
     def __init__(self, line_size: int, device: int = 0):
-        super().__init__()
-        rc = lib().mpc_create_pattern(line_size, device, C.byref(self._h))
-        if rc != 0:
-            raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
-        self._finish()
-        self.kernel_path = self.info.kernel_path
+        super().__init__("mpc_create_pattern", line_size, device)
 
     def result(self) -> Dict:
         """The counts of ``PatternResult`` and both entropies (the reference computes them in ``Print``)."""
@@ -480,9 +471,7 @@ class EvaluatorSet:
 
     def compress_lines(self, lines: np.ndarray, want_sizes: bool = True, want_selected: bool = True):
         """Host buffer [n, L] uint8 -> one ``(size_bits, selected)`` pair per member, in member order."""
-        lines = np.ascontiguousarray(lines, dtype=np.uint8)
-        if lines.ndim != 2 or lines.shape[1] != self.line_size:
-            raise ValueError(f"expected [n, {self.line_size}] uint8")
+        lines = _as_lines(lines, self.line_size)
         n = lines.shape[0]
         sizes = [np.empty(n, dtype=np.uint16) if want_sizes else None for _ in self.members]
         sel = [np.empty(n, dtype=np.int8) if want_selected else None for _ in self.members]
@@ -533,18 +522,11 @@ def sc2_code_lengths(symbols, freqs) -> np.ndarray:
     return out
 
 
-def _ratio(original, compressed, lines) -> float:
-    if not lines:
-        return 0.0
-    return float(original) / float(compressed) if compressed else float("inf")
-
-
 def vpc_result_from_vector(v: np.ndarray, M: int, bins: int, L: int) -> Dict:
     K = M + 1
     # VPC.h:49-60: (double)original / (double)compressed after every line -- inf once lines of 0 bits are all there are
     # (a cluster whose id bits are 0: all-zero lines), 0 before the first line
-    out = {"lines": int(v[0]), "original_bits": int(v[1]), "compressed_bits": int(v[2]),
-           "comp_ratio": _ratio(v[1], v[2], v[0]), "clusters": {}}
+    out = {**_totals(v, _ratio), "clusters": {}}
     for k in range(K):
         cnt, ob, cb, rl, sr, sr2 = (int(x) for x in v[3 + 6 * k: 3 + 6 * k + 6])
         out["clusters"][k - 1] = {

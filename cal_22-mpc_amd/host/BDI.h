@@ -4,7 +4,7 @@
 #define MPC_HOST_BDI_H
 
 #include "CompResult.h"
-#include "Compressor.h"
+#include "DeviceCompressor.h"
 
 namespace comp
 {
@@ -26,21 +26,13 @@ struct BDIResult : public CompResult {
   std::vector<uint64_t> Counts;
 };
 
-class BDI : public Compressor
+class BDI : public DeviceCompressor
 {
 public:
   BDI(unsigned lineSize);
-  virtual ~BDI();
-  virtual unsigned CompressLine(std::vector<uint8_t> &dataLine);
-  virtual CompResult *GetResult();
-  virtual void CompressBatch(const uint8_t *lines, unsigned long long n);
-  virtual unsigned long long CompressFile(const std::string &tracePath);
-  virtual unsigned GetLineSize() { return m_LineSize; }
-  virtual mpc_handle *DeviceHandle() { FlushLines(); return m_Handle; }
 
-private:
-  mpc_handle *m_Handle;
-  unsigned m_LineSize;
+protected:
+  virtual void LoadResult(const uint64_t *v) { static_cast<BDIResult *>(m_Stat)->LoadVector(v); }
 };
 
 }  // namespace comp

@@ -4,7 +4,7 @@
 #define MPC_HOST_BPC_H
 
 #include "CompResult.h"
-#include "Compressor.h"
+#include "DeviceCompressor.h"
 
 #define NUM_BPC_PATTERN 7
 
@@ -26,21 +26,13 @@ struct BPCResult : public CompResult {
   uint64_t TotalWords;
 };
 
-class BPC : public Compressor
+class BPC : public DeviceCompressor
 {
 public:
   BPC(unsigned lineSize);
-  virtual ~BPC();
-  virtual unsigned CompressLine(std::vector<uint8_t> &dataLine);
-  virtual CompResult *GetResult();
-  virtual void CompressBatch(const uint8_t *lines, unsigned long long n);
-  virtual unsigned long long CompressFile(const std::string &tracePath);
-  virtual unsigned GetLineSize() { return m_LineSize; }
-  virtual mpc_handle *DeviceHandle() { FlushLines(); return m_Handle; }
 
-private:
-  mpc_handle *m_Handle;
-  unsigned m_LineSize;
+protected:
+  virtual void LoadResult(const uint64_t *v) { static_cast<BPCResult *>(m_Stat)->LoadVector(v); }
 };
 
 }  // namespace comp

@@ -3,17 +3,12 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "DeviceCompressor.h"
+#include "TraceFile.h"
 #include "mpc_hip.h"
 
 namespace comp
 {
-
-static void fail(const char *what, int rc, mpc_group *g)
-{
-  const char *msg = mpc_group_last_error(g);
-  printf("%s (%d): %s\n", what, rc, msg ? msg : "");
-  exit(1);
-}
 
 CompressorSet::CompressorSet(const std::vector<Compressor *> &members) : m_Members(members), m_Group(nullptr)
 {
@@ -28,7 +23,7 @@ CompressorSet::CompressorSet(const std::vector<Compressor *> &members) : m_Membe
     handles.push_back(h);
   }
   int rc = mpc_group_create(handles.data(), handles.size(), &m_Group);
-  if (rc != MPC_OK) fail("CompressorSet: cannot create the group", rc, nullptr);
+  if (rc != MPC_OK) fail("CompressorSet: cannot create the group", rc, mpc_group_last_error(nullptr));
 }
 
 CompressorSet::~CompressorSet() { mpc_group_destroy(m_Group); }
@@ -44,17 +39,16 @@ void CompressorSet::CompressBatch(const uint8_t *lines, unsigned long long n)
 {
   Prepare();
   int rc = mpc_group_compress_batch(m_Group, lines, n, nullptr, nullptr);
-  if (rc != MPC_OK) fail("CompressorSet::CompressBatch", rc, m_Group);
+  if (rc != MPC_OK) fail("CompressorSet::CompressBatch", rc, mpc_group_last_error(m_Group));
 }
 
 unsigned long long CompressorSet::CompressFile(const std::string &tracePath)
 {
   Prepare();
   uint64_t done = 0;
-  const bool isLog = tracePath.size() > 4 && tracePath.compare(tracePath.size() - 4, 4, ".log") == 0;
-  int rc = isLog ? mpc_group_compress_gpgpusim_log(m_Group, tracePath.c_str(), nullptr, &done)
-                 : mpc_group_compress_npy(m_Group, tracePath.c_str(), 0, ~0ull, 1, &done);
-  if (rc != MPC_OK) fail("CompressorSet::CompressFile", rc, m_Group);
+  int rc = trace::IsGpgpuSimLog(tracePath) ? mpc_group_compress_gpgpusim_log(m_Group, tracePath.c_str(), nullptr, &done)
+                                           : mpc_group_compress_npy(m_Group, tracePath.c_str(), 0, ~0ull, 1, &done);
+  if (rc != MPC_OK) fail("CompressorSet::CompressFile", rc, mpc_group_last_error(m_Group));
   return done;
 }
 

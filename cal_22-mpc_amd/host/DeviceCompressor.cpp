@@ -1,0 +1,77 @@
+#include "DeviceCompressor.h"
+
+#include <cstdio>
+#include <cstdlib>
+
+#include "TraceFile.h"
+#include "mpc_hip.h"
+
+namespace comp
+{
+
+void fail(const std::string &what, int rc, const char *msg)
+{
+  printf("%s (%d): %s\n", what.c_str(), rc, msg ? msg : "");
+  exit(1);
+}
+
+void DeviceCompressor::Fail(const std::string &what, int rc) { fail(what, rc, mpc_last_error(m_Handle)); }
+
+// (a failed create call leaves m_Handle null: the message is the library's creation error)
+void DeviceCompressor::CheckCreated(int rc)
+{
+  if (rc != MPC_OK) Fail(m_Tag + ": cannot create the evaluator", rc);
+}
+
+DeviceCompressor::~DeviceCompressor() { mpc_destroy(m_Handle); }
+
+void DeviceCompressor::RefuseLine(size_t bytes)
+{
+  printf("%s: line of %zu bytes, expected %u.\n", m_Tag.c_str(), bytes, m_LineSize);
+  exit(1);
+}
+
+unsigned DeviceCompressor::CompressLine(std::vector<uint8_t> &dataLine)
+{
+  if (dataLine.size() != m_LineSize) RefuseLine(dataLine.size());
+  if (LineBuffering()) {
+    BufferLine(dataLine);
+    return 0;
+  }
+  uint16_t bits = 0;
+  int rc = mpc_compress_batch(DeviceHandle(), dataLine.data(), 1, &bits, nullptr);
+  if (rc != MPC_OK) Fail(m_Tag + "::CompressLine", rc);
+  return bits;
+}
+
+void DeviceCompressor::CompressBatch(const uint8_t *lines, unsigned long long n)
+{
+  FlushLines();
+  m_Fed = m_Fed || n > 0;
+  int rc = mpc_compress_batch(m_Handle, lines, n, nullptr, nullptr);
+  if (rc != MPC_OK) Fail(m_Tag + "::CompressBatch", rc);
+}
+
+unsigned long long DeviceCompressor::CompressFile(const std::string &tracePath)
+{
+  mpc_handle *h = DeviceHandle();
+  uint64_t done = 0;
+  int rc = trace::IsGpgpuSimLog(tracePath) ? mpc_compress_gpgpusim_log(h, tracePath.c_str(), nullptr, &done)
+                                           : mpc_compress_npy(h, tracePath.c_str(), 0, ~0ull, 1, &done);
+  if (rc != MPC_OK) Fail(m_Tag + "::CompressFile", rc);
+  return done;
+}
+
+CompResult *DeviceCompressor::GetResult()
+{
+  FlushLines();
+  uint64_t len = 0;
+  mpc_stats_len(m_Handle, &len);
+  std::vector<uint64_t> v(len);
+  int rc = mpc_stats_get(m_Handle, v.data(), v.size());
+  if (rc != MPC_OK) Fail(m_Tag + "::GetResult", rc);
+  LoadResult(v.data());
+  return m_Stat;
+}
+
+}  // namespace comp

@@ -1,0 +1,55 @@
+// DeviceCompressor.h -- ADDITIVE, no counterpart in the reference: what the six GPU evaluators (VPC, BDI, FPC, BPC,
+// SC2, Pattern) share over one libmpc_hip handle (include/mpc_hip.h).  A derived class keeps its constructor (the
+// create call, its result object, its name), LoadResult() and whatever the reference's class of that name has of its own.
+#ifndef MPC_HOST_DEVICECOMPRESSOR_H
+#define MPC_HOST_DEVICECOMPRESSOR_H
+
+#include <string>
+
+#include "Compressor.h"
+
+namespace comp
+{
+
+// Prints "<what> (<rc>): <msg>" to stdout and exits with 1, as every failure of a library call does here.
+[[noreturn]] void fail(const std::string &what, int rc, const char *msg);
+
+class DeviceCompressor : public Compressor
+{
+public:
+  virtual ~DeviceCompressor();
+  virtual unsigned CompressLine(std::vector<uint8_t> &dataLine);
+  // the statistics vector of the handle through LoadResult() into m_Stat
+  virtual CompResult *GetResult();
+  virtual void CompressBatch(const uint8_t *lines, unsigned long long n);
+  // a .npy file or a GPGPU-Sim .log file, streamed by the library
+  virtual unsigned long long CompressFile(const std::string &tracePath);
+  virtual unsigned GetLineSize() { return m_LineSize; }
+  // (a handle that has been handed out counts as fed: whoever holds it may have sent lines through it)
+  virtual mpc_handle *DeviceHandle() { FlushLines(); m_Fed = true; return m_Handle; }
+
+protected:
+  // tag: the short name in front of this class's messages ("BDI", "VPC", ...)
+  DeviceCompressor(const char *tag, unsigned lineSize = 0) : m_Handle(nullptr), m_LineSize(lineSize), m_Tag(tag) {}
+  // after the create call of a constructor: "<tag>: cannot create the evaluator (rc): ..." unless it succeeded
+  void CheckCreated(int rc);
+  // "<what> (rc): <the handle's last error>", exit(1)
+  [[noreturn]] void Fail(const std::string &what, int rc);
+  // m_Stat from the statistics vector (layout per algorithm in include/mpc_hip.h)
+  virtual void LoadResult(const uint64_t *v) = 0;
+  // a line of the wrong length: message and exit(1)
+  virtual void RefuseLine(size_t bytes);
+  // whether a line has arrived by any route, buffered lines flushed first
+  bool Fed() { FlushLines(); return m_Fed; }
+
+  mpc_handle *m_Handle;
+  unsigned m_LineSize;
+
+private:
+  std::string m_Tag;
+  bool m_Fed = false;
+};
+
+}  // namespace comp
+
+#endif

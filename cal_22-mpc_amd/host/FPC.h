@@ -4,7 +4,7 @@
 #define MPC_HOST_FPC_H
 
 #include "CompResult.h"
-#include "Compressor.h"
+#include "DeviceCompressor.h"
 
 #define PREFIX_SIZE 3
 #define NUM_FPC_PATTERN 8
@@ -30,21 +30,13 @@ struct FPCResult : public CompResult {
   uint64_t TotalWords;
 };
 
-class FPC : public Compressor
+class FPC : public DeviceCompressor
 {
 public:
   FPC(unsigned lineSize);
-  virtual ~FPC();
-  virtual unsigned CompressLine(std::vector<uint8_t> &dataLine);
-  virtual CompResult *GetResult();
-  virtual void CompressBatch(const uint8_t *lines, unsigned long long n);
-  virtual unsigned long long CompressFile(const std::string &tracePath);
-  virtual unsigned GetLineSize() { return m_LineSize; }
-  virtual mpc_handle *DeviceHandle() { FlushLines(); return m_Handle; }
 
-private:
-  mpc_handle *m_Handle;
-  unsigned m_LineSize;
+protected:
+  virtual void LoadResult(const uint64_t *v) { static_cast<FPCResult *>(m_Stat)->LoadVector(v); }
 };
 
 }  // namespace comp

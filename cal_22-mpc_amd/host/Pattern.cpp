@@ -61,65 +61,11 @@ void PatternResult::LoadVector(const uint64_t *v)
   }
 }
 
-static void fail(const char *what, int rc, mpc_handle *h)
+Pattern::Pattern(unsigned lineSize) : DeviceCompressor("Pattern", lineSize)
 {
-  const char *msg = mpc_last_error(h);
-  printf("%s (%d): %s\n", what, rc, msg ? msg : "");
-  exit(1);
-}
-
-Pattern::Pattern(unsigned lineSize) : m_Handle(nullptr), m_LineSize(lineSize)
-{
-  int rc = mpc_create_pattern(lineSize, -1, &m_Handle);
-  if (rc != MPC_OK) fail("Pattern: cannot create the evaluator", rc, nullptr);
+  CheckCreated(mpc_create_pattern(lineSize, -1, &m_Handle));
   m_Stat = new PatternResult(lineSize);
   m_Stat->CompressorName = "Pattern Checker";
-}
-
-Pattern::~Pattern() { mpc_destroy(m_Handle); }
-
-unsigned Pattern::CompressLine(std::vector<uint8_t> &dataLine)
-{
-  if (dataLine.size() != m_LineSize) {
-    printf("Pattern: line of %zu bytes, expected %u.\n", dataLine.size(), m_LineSize);
-    exit(1);
-  }
-  if (LineBuffering()) {
-    BufferLine(dataLine);
-    return 0;
-  }
-  uint16_t bits = 0;
-  int rc = mpc_compress_batch(m_Handle, dataLine.data(), 1, &bits, nullptr);
-  if (rc != MPC_OK) fail("Pattern::CompressLine", rc, m_Handle);
-  return bits;
-}
-
-void Pattern::CompressBatch(const uint8_t *lines, unsigned long long n)
-{
-  FlushLines();
-  int rc = mpc_compress_batch(m_Handle, lines, n, nullptr, nullptr);
-  if (rc != MPC_OK) fail("Pattern::CompressBatch", rc, m_Handle);
-}
-
-unsigned long long Pattern::CompressFile(const std::string &tracePath)
-{
-  FlushLines();
-  uint64_t done = 0;
-  const bool isLog = tracePath.size() > 4 && tracePath.compare(tracePath.size() - 4, 4, ".log") == 0;
-  int rc = isLog ? mpc_compress_gpgpusim_log(m_Handle, tracePath.c_str(), nullptr, &done)
-                 : mpc_compress_npy(m_Handle, tracePath.c_str(), 0, ~0ull, 1, &done);
-  if (rc != MPC_OK) fail("Pattern::CompressFile", rc, m_Handle);
-  return done;
-}
-
-CompResult *Pattern::GetResult()
-{
-  FlushLines();
-  std::vector<uint64_t> v(534);
-  int rc = mpc_stats_get(m_Handle, v.data(), v.size());
-  if (rc != MPC_OK) fail("Pattern::GetResult", rc, m_Handle);
-  static_cast<PatternResult *>(m_Stat)->LoadVector(v.data());
-  return m_Stat;
 }
 
 unsigned long long Pattern::DistinctLines()
@@ -127,7 +73,7 @@ unsigned long long Pattern::DistinctLines()
   FlushLines();
   uint64_t n = 0;
   int rc = mpc_pattern_distinct_lines(m_Handle, &n);
-  if (rc != MPC_OK) fail("Pattern::DistinctLines", rc, m_Handle);
+  if (rc != MPC_OK) Fail("Pattern::DistinctLines", rc);
   return n;
 }
 

@@ -9,7 +9,7 @@
 #include <map>
 
 #include "CompResult.h"
-#include "Compressor.h"
+#include "DeviceCompressor.h"
 
 namespace comp
 {
@@ -36,23 +36,15 @@ struct PatternResult : public CompResult {
   uint64_t Total;
 };
 
-class Pattern : public Compressor
+class Pattern : public DeviceCompressor
 {
 public:
   Pattern(unsigned lineSize);
-  virtual ~Pattern();
-  virtual unsigned CompressLine(std::vector<uint8_t> &dataLine);
-  virtual CompResult *GetResult();
-  virtual void CompressBatch(const uint8_t *lines, unsigned long long n);
-  virtual unsigned long long CompressFile(const std::string &tracePath);
-  virtual unsigned GetLineSize() { return m_LineSize; }
-  virtual mpc_handle *DeviceHandle() { FlushLines(); return m_Handle; }
   // lines in the set (at most 2^24 - 1: the reference evicts beyond that, this evaluator stops with an error)
   unsigned long long DistinctLines();
 
-private:
-  mpc_handle *m_Handle;
-  unsigned m_LineSize;
+protected:
+  virtual void LoadResult(const uint64_t *v) { static_cast<PatternResult *>(m_Stat)->LoadVector(v); }
 };
 
 }  // namespace comp

@@ -5,7 +5,7 @@
 #define MPC_HOST_SC2_H
 
 #include "CompResult.h"
-#include "Compressor.h"
+#include "DeviceCompressor.h"
 
 #define SC2_ENTRIES 1024
 #define WARM_UP_CNT 1000000
@@ -13,26 +13,18 @@
 namespace comp
 {
 
-class SC2 : public Compressor
+class SC2 : public DeviceCompressor
 {
 public:
   // warmupCnt: lines whose words only feed the frequency table (each costs lineSize / 4 x 33 bits); the table is built
   // when line warmupCnt arrives.  The reference driver passes max(10000, min(numLines / 100, WARM_UP_CNT)).
   SC2(unsigned lineSize, unsigned warmupCnt = 100000);
-  virtual ~SC2();
-  virtual unsigned CompressLine(std::vector<uint8_t> &dataLine);
-  virtual CompResult *GetResult();
-  virtual void CompressBatch(const uint8_t *lines, unsigned long long n);
-  virtual unsigned long long CompressFile(const std::string &tracePath);
-  virtual unsigned GetLineSize() { return m_LineSize; }
-  virtual mpc_handle *DeviceHandle() { FlushLines(); m_Started = true; return m_Handle; }
   // Before the first line only: the evaluator is created again with the new warm-up count.
   void SetSamplingCnt(unsigned cnt);
 
-private:
-  mpc_handle *m_Handle;
-  unsigned m_LineSize;
-  bool m_Started;
+protected:
+  // CompResult only (SC2's PrintDetail is empty)
+  virtual void LoadResult(const uint64_t *v);
 };
 
 }  // namespace comp

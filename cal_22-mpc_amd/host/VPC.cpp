@@ -126,14 +126,7 @@ void VPCResult::PrintDetail(std::string workloadName, std::string filePath)
 // ---------------------------------------------------------------------------
 // VPC (reference VPC.h:241-283, VPC.cpp:22-25, 72-330)
 // ---------------------------------------------------------------------------
-static void fail(const char *what, int rc, mpc_handle *h)
-{
-  const char *msg = mpc_last_error(h);
-  printf("%s (%d): %s\n", what, rc, msg ? msg : "");
-  exit(1);
-}
-
-VPC::VPC(std::string configPath) : m_Handle(nullptr)
+VPC::VPC(std::string configPath) : DeviceCompressor("VPC")
 {
   int rc = mpc_create_vpc(configPath.c_str(), -1, &m_Handle);
   if (rc == MPC_E_NOENT) {
@@ -145,65 +138,23 @@ VPC::VPC(std::string configPath) : m_Handle(nullptr)
     printf("Parsing ERROR! \"%s\" is not valid json file.\n", configPath.c_str());
     exit(1);
   }
-  if (rc != MPC_OK) fail("VPC: cannot create the evaluator", rc, nullptr);
+  CheckCreated(rc);
   mpc_info info;
   mpc_get_info(m_Handle, &info);
-  m_LineSize = info.line_size;
+  m_LineSize = (unsigned)info.line_size;
   m_NumModules = info.num_modules;
   m_NumClusters = info.num_clusters;
   m_HistBins = info.hist_bins;
-  m_Stat = new VPCResult((unsigned)m_LineSize, m_NumModules);
+  m_Stat = new VPCResult(m_LineSize, m_NumModules);
   m_Stat->CompressorName = "Contrastive Clustering Compressor";
   if (info.kernel_path == MPC_PATH_VPC_GENERIC)     // never silently: this path is some hundred times slower
     fprintf(stderr, "note: this configuration runs on the generic (slow, exact) kernel: %s\n", mpc_path_reason(m_Handle));
 }
 
-VPC::~VPC() { mpc_destroy(m_Handle); }
-
-unsigned VPC::CompressLine(std::vector<uint8_t> &dataLine)
+void VPC::RefuseLine(size_t bytes)
 {
-  if ((int)dataLine.size() != m_LineSize) {
-    printf("VPC: line of %zu bytes, configuration lineSize is %d.\n", dataLine.size(), m_LineSize);
-    exit(1);
-  }
-  if (LineBuffering()) {
-    BufferLine(dataLine);
-    return 0;
-  }
-  uint16_t bits = 0;
-  int rc = mpc_compress_batch(m_Handle, dataLine.data(), 1, &bits, nullptr);
-  if (rc != MPC_OK) fail("VPC::CompressLine", rc, m_Handle);
-  return bits;
-}
-
-void VPC::CompressBatch(const uint8_t *lines, unsigned long long n)
-{
-  FlushLines();
-  int rc = mpc_compress_batch(m_Handle, lines, n, nullptr, nullptr);
-  if (rc != MPC_OK) fail("VPC::CompressBatch", rc, m_Handle);
-}
-
-unsigned long long VPC::CompressFile(const std::string &tracePath)
-{
-  FlushLines();
-  uint64_t done = 0;
-  const bool isLog = tracePath.size() > 4 && tracePath.compare(tracePath.size() - 4, 4, ".log") == 0;
-  int rc = isLog ? mpc_compress_gpgpusim_log(m_Handle, tracePath.c_str(), nullptr, &done)
-                 : mpc_compress_npy(m_Handle, tracePath.c_str(), 0, ~0ull, 1, &done);
-  if (rc != MPC_OK) fail("VPC::CompressFile", rc, m_Handle);
-  return done;
-}
-
-CompResult *VPC::GetResult()
-{
-  FlushLines();
-  uint64_t len = 0;
-  mpc_stats_len(m_Handle, &len);
-  std::vector<uint64_t> v(len);
-  int rc = mpc_stats_get(m_Handle, v.data(), v.size());
-  if (rc != MPC_OK) fail("VPC::GetResult", rc, m_Handle);
-  static_cast<VPCResult *>(m_Stat)->LoadVector(v.data(), m_NumModules, m_HistBins);
-  return m_Stat;
+  printf("VPC: line of %zu bytes, configuration lineSize is %d.\n", bytes, (int)m_LineSize);
+  exit(1);
 }
 
 }  // namespace comp

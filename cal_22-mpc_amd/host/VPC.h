@@ -11,7 +11,7 @@
 #include <utility>
 
 #include "CompResult.h"
-#include "Compressor.h"
+#include "DeviceCompressor.h"
 
 namespace comp
 {
@@ -50,26 +50,20 @@ struct VPCResult : public CompResult {
   int m_NumModules;
 };
 
-class VPC : public Compressor
+class VPC : public DeviceCompressor
 {
 public:
   VPC(std::string configPath);
-  virtual ~VPC();
 
-  int GetCachelineSize() { return m_LineSize; }
+  int GetCachelineSize() { return (int)m_LineSize; }
   int GetNumModules() { return m_NumModules; }
   int GetNumClusters() { return m_NumClusters; }
 
-  virtual unsigned CompressLine(std::vector<uint8_t> &dataLine);
-  virtual CompResult *GetResult();
-  virtual void CompressBatch(const uint8_t *lines, unsigned long long n);
-  virtual unsigned long long CompressFile(const std::string &tracePath);
-  virtual unsigned GetLineSize() { return (unsigned)m_LineSize; }
-  virtual mpc_handle *DeviceHandle() { FlushLines(); return m_Handle; }
+protected:
+  virtual void LoadResult(const uint64_t *v) { static_cast<VPCResult *>(m_Stat)->LoadVector(v, m_NumModules, m_HistBins); }
+  virtual void RefuseLine(size_t bytes);
 
 private:
-  mpc_handle *m_Handle;
-  int m_LineSize;
   int m_NumModules;
   int m_NumClusters;
   int m_HistBins;

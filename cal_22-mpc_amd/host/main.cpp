@@ -19,15 +19,11 @@
 #include "BPC.h"
 #include "CompressorSet.h"
 #include "FPC.h"
-#include "LoaderAPSim.h"
-#include "LoaderGPGPU.h"
-#include "LoaderNPY.h"
+#include "TraceFile.h"
 #include "VPC.h"
-#include "utils.h"
 
 #define REQ_SIZE 32   // line size asked of the APSim loader (reference main.cpp:23)
 
-static comp::CompResult *compressLines(comp::Compressor *compressor, trace::Loader *loader, bool perLine);
 static int runList(const std::vector<std::string> &names, const std::string &tracePath, const std::string &configPath,
                    const std::string &outputDirPath);
 
@@ -77,6 +73,86 @@ static bool take_value(int argc, char **argv, int &i, const std::string &arg, co
   return false;
 }
 
+// The algorithms the reference knows and this build leaves out: one message, true when name is one of them.
+static bool refusedAsNotBuilt(const std::string &name)
+{
+  if (!(name == "CPACK" || name == "SC2" || name == "PATTERN" || name == "VIEWER")) return false;
+  std::cout << "Algorithm " << name << " is not part of this build: VPC, BDI, FPC and BPC are (see DESIGN.md, \"Out of scope\")." << std::endl;
+  return true;
+}
+
+// compressor by name (reference main.cpp:85-127); nullptr for a name this build does not evaluate
+static comp::Compressor *makeEvaluator(const std::string &name, const std::string &configPath, unsigned lineSize)
+{
+  if (name == "VPC") return new comp::VPC(configPath);
+  if (name == "BDI") return new comp::BDI(lineSize);
+  if (name == "FPC") return new comp::FPC(lineSize);
+  if (name == "BPC") return new comp::BPC(lineSize);
+  return nullptr;
+}
+
+// loader by extension (reference main.cpp:74-83)
+static trace::Loader *openTrace(const std::string &tracePath, trace::MemReq_t **memReq)
+{
+  trace::Loader *loader = trace::OpenByExtension(tracePath, REQ_SIZE, memReq);
+  if (!loader) {
+    std::cerr << "Unsupported extension." << std::endl;
+    abort();
+  }
+  return loader;
+}
+
+static void requireLineSize(unsigned traceLineSize, unsigned evaluatorLineSize)
+{
+  if (evaluatorLineSize == traceLineSize) return;
+  printf("The trace has %u-byte lines but the evaluator is configured for %u-byte lines.\n", traceLineSize, evaluatorLineSize);
+  exit(1);
+}
+
+// workload name = <parent directory>_<file stem> (reference main.cpp:141-157); false, with a message, without a '/'
+static bool workloadNameOf(const std::string &tracePath, std::string &workloadName)
+{
+  std::vector<std::string> parts = mpctext::split(tracePath, "/");
+  if (parts.size() < 2) {
+    std::cout << "The trace path needs at least one '/' (workload name = <directory>_<file>)." << std::endl;
+    return false;
+  }
+  std::string appName = parts[parts.size() - 1];
+  mpctext::replace_all(appName, ".log", "");
+  mpctext::replace_all(appName, ".npy", "");
+  mpctext::replace_all(appName, ".txt", "");
+  workloadName = parts[parts.size() - 2] + "_" + appName;
+  return true;
+}
+
+// The whole trace to a comp::Compressor or a comp::CompressorSet: streamed by the library when the loader allows it,
+// else in batches of 64 MiB.
+template <class Sink>
+static void compressBatches(Sink *sink, trace::Loader *loader)
+{
+  const std::string path = loader->GetStreamablePath();
+  if (!path.empty()) {
+    sink->CompressFile(path);
+    return;
+  }
+  const unsigned L = loader->GetCachelineSize();
+  const unsigned long long cap = (64ull << 20) / L;
+  std::vector<uint8_t> buf((size_t)(cap * L));
+  for (;;) {
+    unsigned long long n = loader->GetBatch(buf.data(), cap);
+    if (n == 0) break;
+    sink->CompressBatch(buf.data(), n);
+  }
+}
+
+// result files (reference main.cpp:129-136)
+static void writeResults(comp::CompResult *compStat, const std::string &workloadName, const std::string &outputDirPath,
+                         const std::string &saveFileName)
+{
+  compStat->Print(workloadName, outputDirPath + "/" + saveFileName + "_results.csv");
+  compStat->PrintDetail(workloadName, outputDirPath + "/" + saveFileName + "_results_detail.csv");
+}
+
 int main(int argc, char **argv)
 {
   Args a;
@@ -108,10 +184,7 @@ int main(int argc, char **argv)
   if (algorithm.find(',') != std::string::npos) list = mpctext::split(algorithm, ",");      // ("BDI," has an empty element)
   for (size_t i = 0; i < list.size() && !help; i++) {
     const std::string &n = list[i];
-    if (n == "CPACK" || n == "SC2" || n == "PATTERN" || n == "VIEWER") {
-      std::cout << "Algorithm " << n << " is not part of this build: VPC, BDI, FPC and BPC are (see DESIGN.md, \"Out of scope\")." << std::endl;
-      return 1;
-    }
+    if (refusedAsNotBuilt(n)) return 1;
     if (!(n == "VPC" || n == "BDI" || n == "FPC" || n == "BPC")) {
       std::cout << "Invalid name of algorithm in the list \"" << algorithm << "\": \"" << n << "\"." << std::endl;
       return 1;
@@ -135,115 +208,36 @@ int main(int argc, char **argv)
   const std::string tracePath = a.input, configPath = a.config, outputDirPath = a.has_output ? a.output : "";
   if (!list.empty()) return runList(list, tracePath, configPath, outputDirPath);
 
-  // loader by extension (reference main.cpp:74-83)
-  trace::Loader *loader = nullptr;
-  if (mpctext::ends_with(tracePath, ".npy")) {
-    loader = new trace::LoaderNPY(tracePath);
-  } else if (mpctext::ends_with(tracePath, ".log")) {
-    loader = new trace::gpgpusim::LoaderGPGPU(tracePath);
-  } else if (mpctext::ends_with(tracePath, ".txt")) {
-    loader = new trace::apsim::LoaderGPGPU(tracePath, REQ_SIZE);
-  } else {
-    std::cerr << "Unsupported extension." << std::endl;
-    abort();
-  }
+  trace::MemReq_t *memReq = nullptr;
+  trace::Loader *loader = openTrace(tracePath, &memReq);
 
-  // compressor by name (reference main.cpp:85-127)
-  const unsigned lineSize = loader->GetCachelineSize();
-  comp::Compressor *compressor = nullptr;
-  if (algorithm == "VPC") {
-    compressor = new comp::VPC(configPath);
-  } else if (algorithm == "BDI") {
-    compressor = new comp::BDI(lineSize);
-  } else if (algorithm == "FPC") {
-    compressor = new comp::FPC(lineSize);
-  } else if (algorithm == "BPC") {
-    compressor = new comp::BPC(lineSize);
-  } else if (algorithm == "CPACK" || algorithm == "SC2" || algorithm == "PATTERN" || algorithm == "VIEWER") {
-    std::cout << "Algorithm " << algorithm << " is not part of this build: VPC, BDI, FPC and BPC are (see DESIGN.md, \"Out of scope\")."
-              << std::endl;
-    return 1;
-  } else {
+  comp::Compressor *compressor = makeEvaluator(algorithm, configPath, loader->GetCachelineSize());
+  if (!compressor) {
+    if (refusedAsNotBuilt(algorithm)) return 1;
     std::cerr << "Invalid name of algorithm." << std::endl;
     abort();
   }
-
-  // result files (reference main.cpp:129-136)
   const std::string saveFileName = (algorithm == "VPC") ? parseConfig(configPath) : algorithm;
-  const std::string compOutputSavePath = outputDirPath + "/" + saveFileName + "_results.csv";
-  const std::string compDetailedOutputSavePath = outputDirPath + "/" + saveFileName + "_results_detail.csv";
 
+  // The reference's per-line loop (main.cpp:208-248) as a batch loop, unless --per-line / --line-buffer ask for that
+  // loop itself or the loader hands out single lines only.
   if (a.line_buffer) compressor->SetLineBuffering(a.line_buffer);
-  comp::CompResult *compStat = compressLines(compressor, loader, a.per_line);
+  requireLineSize(loader->GetCachelineSize(), compressor->GetLineSize());
+  if (!a.per_line && (loader->SupportsBatch() || !loader->GetStreamablePath().empty()))
+    compressBatches(compressor, loader);
+  else
+    trace::CompressPerLine(compressor, loader, memReq);
+  comp::CompResult *compStat = compressor->GetResult();
 
-  // workload name = <parent directory>_<file stem> (reference main.cpp:141-157)
   std::string workloadName;
-  {
-    std::vector<std::string> parts = mpctext::split(tracePath, "/");
-    if (parts.size() < 2) {
-      std::cout << "The trace path needs at least one '/' (workload name = <directory>_<file>)." << std::endl;
-      return 1;
-    }
-    std::string benchmarkName = parts[parts.size() - 2];
-    std::string appName = parts[parts.size() - 1];
-    mpctext::replace_all(appName, ".log", "");
-    mpctext::replace_all(appName, ".npy", "");
-    mpctext::replace_all(appName, ".txt", "");
-    workloadName = benchmarkName + "_" + appName;
-  }
+  if (!workloadNameOf(tracePath, workloadName)) return 1;
   std::cout << "comp.ratio: " << mpctext::num(compStat->CompRatio) << std::endl;
+  writeResults(compStat, workloadName, outputDirPath, saveFileName);
 
-  compStat->Print(workloadName, compOutputSavePath);
-  compStat->PrintDetail(workloadName, compDetailedOutputSavePath);
-
+  delete memReq;      // (the reference leaks its request object)
   delete loader;
   delete compressor;
   return 0;
-}
-
-// The reference's per-line loop (main.cpp:208-248) as a batch loop: stream the file
-// through the evaluator when the loader allows it, else pull batches, else lines.
-static comp::CompResult *compressLines(comp::Compressor *compressor, trace::Loader *loader, bool perLine)
-{
-  if (compressor->GetLineSize() != loader->GetCachelineSize()) {
-    printf("The trace has %u-byte lines but the evaluator is configured for %u-byte lines.\n",
-           loader->GetCachelineSize(), compressor->GetLineSize());
-    exit(1);
-  }
-  const std::string path = perLine ? std::string() : loader->GetStreamablePath();
-  if (!path.empty()) {
-    compressor->CompressFile(path);
-    return compressor->GetResult();
-  }
-  if (!perLine && loader->SupportsBatch()) {
-    const unsigned L = loader->GetCachelineSize();
-    const unsigned long long cap = (64ull << 20) / L;
-    std::vector<uint8_t> buf((size_t)(cap * L));
-    for (;;) {
-      unsigned long long n = loader->GetBatch(buf.data(), cap);
-      if (n == 0) break;
-      compressor->CompressBatch(buf.data(), n);
-    }
-  } else {
-    // the reference's loop (main.cpp:208-248): one request object handed back and forth, a .log
-    // trace's requests filtered to GLOBAL_ACC_R / GLOBAL_ACC_W (main.cpp:222-224)
-    trace::gpgpusim::LoaderGPGPU *gpgpu = dynamic_cast<trace::gpgpusim::LoaderGPGPU *>(loader);
-    trace::MemReq_t *memReq = gpgpu ? static_cast<trace::MemReq_t *>(new trace::gpgpusim::MemReqGPU_t)
-                              : dynamic_cast<trace::apsim::LoaderGPGPU *>(loader) ? static_cast<trace::MemReq_t *>(new trace::apsim::MemReqGPU_t)
-                                                                                  : new trace::MemReq_t;
-    memReq->Reset();
-    while (1) {
-      memReq = loader->GetCacheline(memReq);
-      if (memReq->isEnd) break;
-      if (gpgpu) {
-        const trace::gpgpusim::reqTypeGPU t = static_cast<trace::gpgpusim::MemReqGPU_t *>(memReq)->reqType;
-        if (!(t == trace::gpgpusim::GLOBAL_ACC_R || t == trace::gpgpusim::GLOBAL_ACC_W)) continue;
-      }
-      compressor->CompressLine(memReq->data);
-    }
-    delete memReq;      // (the reference leaks its request object)
-  }
-  return compressor->GetResult();
 }
 
 // -a with a list: one pass over the trace for all of them, then each algorithm's own result files and one
@@ -251,63 +245,28 @@ static comp::CompResult *compressLines(comp::Compressor *compressor, trace::Load
 static int runList(const std::vector<std::string> &names, const std::string &tracePath, const std::string &configPath,
                    const std::string &outputDirPath)
 {
-  std::vector<std::string> parts = mpctext::split(tracePath, "/");
-  if (parts.size() < 2) {
-    std::cout << "The trace path needs at least one '/' (workload name = <directory>_<file>)." << std::endl;
-    return 1;
-  }
-  std::string appName = parts[parts.size() - 1];
-  mpctext::replace_all(appName, ".log", "");
-  mpctext::replace_all(appName, ".npy", "");
-  mpctext::replace_all(appName, ".txt", "");
-  const std::string workloadName = parts[parts.size() - 2] + "_" + appName;
+  std::string workloadName;
+  if (!workloadNameOf(tracePath, workloadName)) return 1;
 
-  trace::Loader *loader = nullptr;
-  if (mpctext::ends_with(tracePath, ".npy")) {
-    loader = new trace::LoaderNPY(tracePath);
-  } else if (mpctext::ends_with(tracePath, ".log")) {
-    loader = new trace::gpgpusim::LoaderGPGPU(tracePath);
-  } else if (mpctext::ends_with(tracePath, ".txt")) {
-    loader = new trace::apsim::LoaderGPGPU(tracePath, REQ_SIZE);
-  } else {
-    std::cerr << "Unsupported extension." << std::endl;
-    abort();
-  }
+  trace::MemReq_t *memReq = nullptr;
+  trace::Loader *loader = openTrace(tracePath, &memReq);
   const unsigned lineSize = loader->GetCachelineSize();
   std::vector<comp::Compressor *> members;
   for (const std::string &n : names) {
-    comp::Compressor *c = n == "VPC" ? static_cast<comp::Compressor *>(new comp::VPC(configPath))
-                          : n == "BDI" ? static_cast<comp::Compressor *>(new comp::BDI(lineSize))
-                          : n == "FPC" ? static_cast<comp::Compressor *>(new comp::FPC(lineSize))
-                                       : static_cast<comp::Compressor *>(new comp::BPC(lineSize));
-    if (c->GetLineSize() != lineSize) {
-      printf("The trace has %u-byte lines but the evaluator is configured for %u-byte lines.\n", lineSize, c->GetLineSize());
-      exit(1);
-    }
-    members.push_back(c);
+    members.push_back(makeEvaluator(n, configPath, lineSize));      // (main() has checked the names)
+    requireLineSize(lineSize, members.back()->GetLineSize());
   }
   {
     comp::CompressorSet set(members);
-    const std::string path = loader->GetStreamablePath();
-    if (!path.empty()) {
-      set.CompressFile(path);
-    } else {
-      const unsigned long long cap = (64ull << 20) / lineSize;
-      std::vector<uint8_t> buf((size_t)(cap * lineSize));
-      for (;;) {
-        unsigned long long n = loader->GetBatch(buf.data(), cap);
-        if (n == 0) break;
-        set.CompressBatch(buf.data(), n);
-      }
-    }
+    compressBatches(&set, loader);
     for (size_t i = 0; i < names.size(); i++) {
       comp::CompResult *compStat = set.GetResult(i);
       const std::string saveFileName = (names[i] == "VPC") ? parseConfig(configPath) : names[i];
       std::cout << names[i] << " comp.ratio: " << mpctext::num(compStat->CompRatio) << std::endl;
-      compStat->Print(workloadName, outputDirPath + "/" + saveFileName + "_results.csv");
-      compStat->PrintDetail(workloadName, outputDirPath + "/" + saveFileName + "_results_detail.csv");
+      writeResults(compStat, workloadName, outputDirPath, saveFileName);
     }
   }
+  delete memReq;
   delete loader;
   for (comp::Compressor *c : members) delete c;
   return 0;

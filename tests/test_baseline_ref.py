@@ -129,7 +129,7 @@ def test_host_result_print_is_the_reference_text(fixture, tmp_path):
     host = os.path.join(ROOT, "cal_22-mpc_amd", "host")
     libdir = os.path.join(ROOT, "cal_22-mpc_amd")
     exe = str(tmp_path / "result_print_probe")
-    srcs = [os.path.join(host, f) for f in ("BDI.cpp", "FPC.cpp", "BPC.cpp", "VPC.cpp", "Compressor.cpp", "CompResult.cpp",
+    srcs = [os.path.join(host, f) for f in ("BDI.cpp", "FPC.cpp", "BPC.cpp", "VPC.cpp", "DeviceCompressor.cpp", "Compressor.cpp", "CompResult.cpp",
                                             "LoaderNPY.cpp", "LoaderGPGPU.cpp", "LoaderAPSim.cpp", "utils.cpp")]
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", host, "-I", os.path.join(ROOT, "include"),
                         os.path.join(ROOT, "tests", "native", "result_print_probe.cpp"), *srcs,

@@ -148,7 +148,7 @@ def probe(tmp_path_factory):
     build = pkg("build")
     build.build_lib()
     out = str(tmp_path_factory.mktemp("pattern_probe") / "pattern_probe")
-    srcs = [os.path.join(ROOT, "tests", "native", "pattern_probe.cpp")] + [os.path.join(HOST, f) for f in ("Pattern.cpp", "CompResult.cpp", "Compressor.cpp", "utils.cpp")]
+    srcs = [os.path.join(ROOT, "tests", "native", "pattern_probe.cpp")] + [os.path.join(HOST, f) for f in ("Pattern.cpp", "DeviceCompressor.cpp", "CompResult.cpp", "Compressor.cpp", "utils.cpp")]
     srcs += [os.path.join(HOST, f) for f in sorted(os.listdir(HOST)) if f.startswith("Loader") and f.endswith(".cpp")]
     pkg_dir = os.path.dirname(build.LIB)
     subprocess.run([build.HIPCC, "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), "-I", HOST, *srcs, "-L", pkg_dir,

@@ -188,7 +188,7 @@ def test_cpp_mirror_runs_the_reference_loop(mpc, traces, tmp_path):
     libdir = os.path.join(ROOT, "cal_22-mpc_amd")
     exe = str(tmp_path / "sc2_probe")
     subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", host, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "native", "sc2_probe.cpp"), os.path.join(host, "SC2.cpp"),
+                    os.path.join(ROOT, "tests", "native", "sc2_probe.cpp"), os.path.join(host, "SC2.cpp"), os.path.join(host, "DeviceCompressor.cpp"),
                     os.path.join(host, "Compressor.cpp"), os.path.join(host, "CompResult.cpp"), os.path.join(host, "LoaderNPY.cpp"),
                     os.path.join(host, "LoaderGPGPU.cpp"), os.path.join(host, "LoaderAPSim.cpp"), os.path.join(host, "utils.cpp"),
                     "-L", libdir, "-lmpc_hip", f"-Wl,-rpath,{libdir}", "-o", exe], check=True, capture_output=True, text=True)

@@ -23,6 +23,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPC_HIP_LIB") or os.path.join(HERE, "libmpc_hip.so")   # override: development builds only
 
+MPC_SIZE_BINS = 4096          # bins of a size histogram (include/mpc_hip_sizes.h)
 MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2, MPC_PATH_PATTERN = 1, 2, 3, 4, 5, 6, 7
 SYNTH_KINDS = {"zeros": 0, "random_u32": 1, "sine_f32": 2, "mixed": 3, "pointers_u64": 4}
 
@@ -115,6 +116,13 @@ def lib() -> C.CDLL:
             "mpc_group_sync": ([H], C.c_int),
             "mpc_synth_fill": ([C.c_void_p, C.c_uint64, C.c_uint, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p], C.c_int),
             "mpc_read_bandwidth_probe": ([C.c_void_p, C.c_uint64, C.c_void_p], C.c_int),
+            "mpc_size_hist_enable": ([H], C.c_int),
+            "mpc_size_hist_get": ([H, C.c_void_p, C.c_size_t], C.c_int),
+            "mpc_group_best_enable": ([H], C.c_int),
+            "mpc_group_best_get": ([H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
+            "mpc_group_best_reset": ([H], C.c_int),
+            "mpc_size_sectors": ([C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_double)], C.c_int),
         }
         for name, (args, res) in sigs.items():
             fn = getattr(L, name)
@@ -138,6 +146,9 @@ EXPORTED_SYMBOLS = [
 # The SC2 entry points of include/mpc_hip.h.  Kept apart from EXPORTED_SYMBOLS, which lists the names of the
 # header's lowercase-letter form (mpc_[a-z_]+) only; every one of both lists is exported by libmpc_hip.so.
 EXPORTED_SC2_SYMBOLS = ["mpc_create_sc2", "mpc_sc2_sampling_lines", "mpc_sc2_code_lengths", "mpc_sc2_table"]
+# The size accounting entry points, declared in include/mpc_hip_sizes.h (which mpc_hip.h includes).
+EXPORTED_SIZE_SYMBOLS = ["mpc_size_hist_enable", "mpc_size_hist_get", "mpc_group_best_enable", "mpc_group_best_get",
+                         "mpc_group_best_reset", "mpc_size_sectors"]
 
 
 def gpgpusim_log_line_size(path: str) -> int:
@@ -301,6 +312,18 @@ class _Evaluator:
 
     def reset(self) -> None:
         self._check(lib().mpc_stats_reset(self._h))
+
+    # -- size accounting ------------------------------------------------------
+    def enable_size_histogram(self) -> None:
+        """Count, from now on, how many lines compress to how many bits (``mpc_size_hist_enable``); idempotent."""
+        self._check(lib().mpc_size_hist_enable(self._h))
+
+    def size_histogram(self) -> np.ndarray:
+        """``uint64[MPC_SIZE_BINS]``: bin s = lines of s bits since accounting was switched on or the last ``reset()``
+        (the last bin also takes larger sizes).  Raises ``MpcError`` (MPC_E_INVAL) when accounting is off."""
+        bins = np.zeros(MPC_SIZE_BINS, dtype=np.uint64)
+        self._check(lib().mpc_size_hist_get(self._h, bins.ctypes.data, MPC_SIZE_BINS))
+        return bins
 
 
 class VPC(_Evaluator):
@@ -501,6 +524,48 @@ class EvaluatorSet:
 
     def sync(self) -> None:
         self._check(lib().mpc_group_sync(self._g))
+
+    # -- best-of ---------------------------------------------------------------
+    def enable_best(self) -> None:
+        """Account, from now on, the per-line smallest size over the members (all but ``Pattern`` ones); idempotent."""
+        self._check(lib().mpc_group_best_enable(self._g))
+
+    def best(self) -> Dict:
+        """``bins``: histogram of the best size without tag bits; ``wins``: lines won per member (ties go to the first
+        minimal member; 0 for a member outside the set); ``best_bits``: sum of the best sizes; ``lines``; ``tag_bits``:
+        ceil(log2(members taking part)), what a hybrid stores per line to name the winner."""
+        bins = np.zeros(MPC_SIZE_BINS, dtype=np.uint64)
+        wins = np.zeros(len(self.members), dtype=np.uint64)
+        bits, lines = C.c_uint64(), C.c_uint64()
+        self._check(lib().mpc_group_best_get(self._g, bins.ctypes.data, MPC_SIZE_BINS, wins.ctypes.data, len(self.members),
+                                             C.byref(bits), C.byref(lines)))
+        taking_part = sum(1 for e in self.members if not isinstance(e, Pattern))
+        return {"bins": bins, "wins": wins, "best_bits": int(bits.value), "lines": int(lines.value),
+                "tag_bits": (taking_part - 1).bit_length()}
+
+    def reset_best(self) -> None:
+        self._check(lib().mpc_group_best_reset(self._g))
+
+
+def size_sectors(bins, line_size: int, sector_bytes: int = 32) -> Dict:
+    """The sectors of ``sector_bytes`` bytes that lines of ``line_size`` bytes with the size histogram ``bins`` occupy
+    (``mpc_size_sectors``; no device): a line of s bits takes ``min(max(1, ceil(s / (8 * sector_bytes))),
+    ceil(line_size / sector_bytes))``.  ``classes[c - 1]``: lines that occupy c sectors; ``total_sectors``; ``ratio`` =
+    lines x classes / total sectors (0.0 without lines)."""
+    bins = np.ascontiguousarray(bins, dtype=np.uint64)
+    if bins.shape != (MPC_SIZE_BINS,):
+        raise ValueError(f"a size histogram has {MPC_SIZE_BINS} bins")
+    line_size, sector_bytes = int(line_size), int(sector_bytes)
+    if line_size < 0 or sector_bytes < 0 or line_size >= 1 << 32 or sector_bytes >= 1 << 32:
+        raise MpcError(-22, "mpc_size_sectors: line_size and sector_bytes are unsigned")
+    n_classes = -(-line_size // sector_bytes) if sector_bytes > 0 else 0
+    classes = np.zeros(max(n_classes, 1), dtype=np.uint64)
+    total, ratio = C.c_uint64(), C.c_double()
+    rc = lib().mpc_size_sectors(bins.ctypes.data, MPC_SIZE_BINS, line_size, sector_bytes, classes.ctypes.data, n_classes,
+                                C.byref(total), C.byref(ratio))
+    if rc != 0:
+        raise MpcError(rc, "mpc_size_sectors: sector_bytes must be 1 .. line_size")
+    return {"classes": classes[:n_classes].copy(), "total_sectors": int(total.value), "ratio": float(ratio.value)}
 
 
 def sc2_sampling_lines(num_lines: int) -> int:

@@ -18,6 +18,7 @@
 #include "mpc_device.h"
 #include "mpc_sc2.h"
 #include "mpc_pattern.h"
+#include "mpc_sizes.h"
 #include "mpc_launch.h"
 
 // libmpc_hip_test.so (build.py, -DMPC_TESTING=1): route counters behind the raw statistics and a cap on the launch grid,
@@ -28,6 +29,10 @@
 constexpr size_t kRouteWords = MPC_TESTING ? 16 : 0;
 
 typedef unsigned long long u64;
+
+// Size accounting on mpc_compress_batch_device without a sizes array of the caller's: the batch is evaluated in pieces of
+// this many lines, each evaluator launch followed by the accounting pass over a scratch array (8 MiB per member).
+constexpr u64 kAccountLines = 4ull << 20;
 
 #include "mpc_jit.h"
 #include "mpc_stage.h"
@@ -110,6 +115,15 @@ struct mpc_handle {
     bool over = false;           // a line beyond the capacity arrived: the handle takes no more lines
   } pat;
   std::vector<Stager *> fed_by;  // every stager that feeds this handle: its own, then those of the groups it is a member of (sc2_build)
+  // size accounting (mpc_sizes.h): nothing of it exists before mpc_size_hist_enable
+  struct {
+    bool on = false;
+    u64 *d_hist = nullptr;             // [MPC_SIZE_BINS]; not for VPC, whose histogram is in its statistics
+    std::vector<u64> vpc_base;         // VPC: that histogram when accounting was switched on (only later lines count)
+    uint16_t *d_scratch = nullptr;     // [kAccountLines] sizes of a piece of a device batch
+    hipEvent_t scratch_done = nullptr; // behind the last pass that read the scratch, whichever stream that was
+    bool recorded = false;
+  } acct;
   std::string error;
 };
 
@@ -118,6 +132,17 @@ struct mpc_group {
   int shared[3] = {-1, -1, -1};  // member index of the BDI, FPC, BPC handle that baselines_kernel evaluates (all -1: no shared launch)
   int first_shared = -1;         // ... the first of them in member order: where the shared launch is enqueued
   Stager stage;                  // m.size() members; its streams and events exist from creation (the members' fed_by), the rest as for a handle
+  // best-of (mpc_sizes.h): nothing of it exists before mpc_group_best_enable
+  struct {
+    bool on = false;
+    std::vector<int> set;              // member indices that take part, in member order (every member but Pattern ones)
+    u64 *d_acc = nullptr;              // [MPC_SIZES_BEST_LEN]: histogram | wins in the order of `set` | bits
+  } best;
+  // device batches with accounting: per member the scratch sizes of a piece (null until needed), the pointers of the piece
+  std::vector<uint16_t *> d_scratch, piece_sizes;
+  std::vector<int8_t *> piece_sel;
+  hipEvent_t scratch_done = nullptr;
+  bool recorded = false;
   std::string form, error;
 };
 
@@ -141,12 +166,14 @@ int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t 
 int pattern_status(mpc_handle *h);
 int group_launch(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, hipStream_t s);
 int group_members_status(mpc_group *g);
+int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
+int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, hipStream_t s);
 
 Sink sink_of(mpc_handle *h)
 {
   return {h,
           [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, hipStream_t s) {
-            return launch(static_cast<mpc_handle *>(c), d, n, ds ? ds[0] : nullptr, dl ? dl[0] : nullptr, s);
+            return launch_accounted(static_cast<mpc_handle *>(c), d, n, ds ? ds[0] : nullptr, dl ? dl[0] : nullptr, s);
           },
           [](void *c, int code, const std::string &msg) { return set_err(static_cast<mpc_handle *>(c), code, msg); },
           [](void *c) { return pattern_status(static_cast<mpc_handle *>(c)); }};
@@ -156,7 +183,7 @@ Sink sink_of(mpc_group *g)
 {
   return {g,
           [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, hipStream_t s) {
-            return group_launch(static_cast<mpc_group *>(c), d, n, ds, dl, s);
+            return group_launch_accounted(static_cast<mpc_group *>(c), d, n, ds, dl, s);
           },
           [](void *c, int code, const std::string &msg) { return group_err(static_cast<mpc_group *>(c), code, msg); },
           [](void *c) { return group_members_status(static_cast<mpc_group *>(c)); }};
@@ -656,6 +683,105 @@ int group_members_status(mpc_group *g)
   return MPC_OK;
 }
 
+// ---------------------------------------------------------------------------
+// size accounting (mpc_sizes.h): one pass over the sizes the evaluators of a chunk wrote, on the same stream behind them
+// ---------------------------------------------------------------------------
+// a handle whose sizes feed the pass for its own histogram (a VPC handle's histogram is in its statistics)
+bool accounts(const mpc_handle *h) { return h->acct.on && h->algorithm != Algo::VPC; }
+
+bool in_best(const mpc_group *g, int i) { return g->best.on && std::find(g->best.set.begin(), g->best.set.end(), i) != g->best.set.end(); }
+
+// ... a member whose sizes a group needs on the device, asked for by the caller or not
+bool group_accounts(const mpc_group *g, int i) { return accounts(g->m[(size_t)i]) || in_best(g, i); }
+
+// (a handle's accounting may have been switched on since the group's last call)
+void group_refresh(mpc_group *g)
+{
+  for (int i = 0; i < (int)g->m.size(); i++) g->stage.account[(size_t)i] = group_accounts(g, i) ? 1 : 0;
+}
+
+hipError_t sizes_pass(const mpc_handle *h, const MpcSizesArgs &A, u64 n, hipStream_t s)
+{
+  return mpc_launch_sizes(&A, n, grid_for(h, n / 8 + 1, 256, mpc_sizes_wg_per_cu(&A)), s);
+}
+
+int account(mpc_handle *h, const uint16_t *d_sizes, u64 n, hipStream_t s)
+{
+  MpcSizesArgs A{};
+  A.m = 1;
+  A.sizes[0] = d_sizes;
+  A.hist[0] = h->acct.d_hist;
+  const hipError_t e = sizes_pass(h, A, n, s);
+  if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch (size accounting): ") + hipGetErrorString(e));
+  return MPC_OK;
+}
+
+// a staged or in-place chunk of a handle: the stager has asked for the sizes of a handle that accounts
+int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s)
+{
+  const int rc = launch(h, d_lines, n, d_sizes, d_sel, s);
+  if (rc != MPC_OK || n == 0 || !accounts(h)) return rc;
+  if (!d_sizes) return set_err(h, MPC_E_INVAL, "size accounting: the chunk has no sizes array");
+  return account(h, d_sizes, n, s);
+}
+
+// The members' sizes of one chunk (one pointer per member, non-null for every member that group_accounts): first the
+// best-of set in one launch, with the histograms of its members that have one; then the other histograms (Pattern
+// members, or every member when best-of is off), MPC_SIZES_MAX arrays a launch.
+int group_account(mpc_group *g, uint16_t *const *d_sizes, u64 n, hipStream_t s)
+{
+  const mpc_handle *h0 = g->m[0];
+  auto pass = [&](const MpcSizesArgs &A) {
+    const hipError_t e = sizes_pass(h0, A, n, s);
+    return e == hipSuccess ? MPC_OK : group_err(g, MPC_E_HIP, std::string("kernel launch (size accounting): ") + hipGetErrorString(e));
+  };
+  if (g->best.on) {
+    MpcSizesArgs A{};
+    for (int i : g->best.set) {
+      A.sizes[A.m] = d_sizes[i];
+      A.hist[A.m] = accounts(g->m[(size_t)i]) ? g->m[(size_t)i]->acct.d_hist : nullptr;
+      A.m++;
+    }
+    A.best = g->best.d_acc;
+    const int rc = pass(A);
+    if (rc != MPC_OK) return rc;
+  }
+  MpcSizesArgs A{};
+  for (int i = 0; i < (int)g->m.size(); i++) {
+    if (!accounts(g->m[(size_t)i]) || in_best(g, i)) continue;
+    A.sizes[A.m] = d_sizes[i];
+    A.hist[A.m] = g->m[(size_t)i]->acct.d_hist;
+    if (++A.m == MPC_SIZES_MAX) {
+      const int rc = pass(A);
+      if (rc != MPC_OK) return rc;
+      A = MpcSizesArgs{};
+    }
+  }
+  return A.m ? pass(A) : MPC_OK;
+}
+
+int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, hipStream_t s)
+{
+  const int rc = group_launch(g, d_lines, n, d_sizes, d_sel, s);
+  if (rc != MPC_OK || n == 0) return rc;
+  bool any = false;
+  for (int i = 0; i < (int)g->m.size(); i++) {
+    if (!group_accounts(g, i)) continue;
+    if (!d_sizes || !d_sizes[i]) return group_err(g, MPC_E_INVAL, "size accounting: the chunk has no sizes array for member " + std::to_string(i));
+    any = true;
+  }
+  return any ? group_account(g, d_sizes, n, s) : MPC_OK;
+}
+
+// VPC: the size histogram is the sum over the clusters of the histogram in the raw statistics, clipped into MPC_SIZE_BINS bins
+void vpc_size_hist(const mpc_handle *h, const std::vector<u64> &raw, std::vector<u64> &bins)
+{
+  const int K = h->cfg.M + 1, B = h->cfg.hist_bins;
+  bins.assign(MPC_SIZE_BINS, 0);
+  for (int k = 0; k < K; k++)
+    for (int s = 0; s < B; s++) bins[(size_t)std::min(s, MPC_SIZE_BINS - 1)] += raw[2 * K + (u64)k * B + s];
+}
+
 // the line sizes an algorithm of the table takes (the refusal lands in mpc_last_error(NULL))
 int check_line_size(Algo a, unsigned line_size)
 {
@@ -852,6 +978,9 @@ void mpc_destroy(mpc_handle *h)
   if (h->pat.set.pend_a) (void)hipFree(h->pat.set.pend_a);
   if (h->pat.set.pend_b) (void)hipFree(h->pat.set.pend_b);
   if (h->pat.done) (void)hipEventDestroy(h->pat.done);
+  if (h->acct.d_hist) (void)hipFree(h->acct.d_hist);
+  if (h->acct.d_scratch) (void)hipFree(h->acct.d_scratch);
+  if (h->acct.scratch_done) (void)hipEventDestroy(h->acct.scratch_done);
   delete h;
 }
 
@@ -920,7 +1049,22 @@ int mpc_compress_batch_device(mpc_handle *h, const void *d_lines, uint64_t n, ui
   if (!h || (!d_lines && n)) return MPC_E_INVAL;
   if (((uintptr_t)d_lines) & 15u) return set_err(h, MPC_E_INVAL, "device line buffer must be 16-byte aligned");
   HIPCHK(h, hipSetDevice(h->device));
-  return launch(h, d_lines, n, d_sizes, d_sel, (hipStream_t)hip_stream);
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (!accounts(h) || d_sizes) return launch_accounted(h, d_lines, n, d_sizes, d_sel, s);
+  // accounting without a sizes array of the caller's: pieces of kAccountLines lines over the handle's scratch array
+  if (!h->acct.d_scratch) {
+    HIPCHK(h, hipMalloc((void **)&h->acct.d_scratch, kAccountLines * sizeof(uint16_t)));
+    HIPCHK(h, hipEventCreateWithFlags(&h->acct.scratch_done, hipEventDisableTiming));
+  }
+  if (h->acct.recorded) HIPCHK(h, hipStreamWaitEvent(s, h->acct.scratch_done, 0));
+  for (u64 at = 0; at < n; at += kAccountLines) {
+    const u64 take = std::min<u64>(n - at, kAccountLines);
+    const int rc = launch_accounted(h, static_cast<const uint8_t *>(d_lines) + at * (u64)h->L, take, h->acct.d_scratch, d_sel ? d_sel + at : nullptr, s);
+    if (rc != MPC_OK) return rc;
+  }
+  HIPCHK(h, hipEventRecord(h->acct.scratch_done, s));
+  h->acct.recorded = true;
+  return MPC_OK;
 }
 
 int mpc_sync(mpc_handle *h)
@@ -1025,6 +1169,9 @@ void mpc_group_destroy(mpc_group *g)
   (void)hipSetDevice(g->stage.device);
   for (mpc_handle *h : g->m) h->fed_by.erase(std::remove(h->fed_by.begin(), h->fed_by.end(), &g->stage), h->fed_by.end());
   mpcstage::destroy(g->stage);
+  if (g->best.d_acc) (void)hipFree(g->best.d_acc);
+  for (uint16_t *p : g->d_scratch) if (p) (void)hipFree(p);
+  if (g->scratch_done) (void)hipEventDestroy(g->scratch_done);
   delete g;
 }
 
@@ -1036,6 +1183,7 @@ int mpc_group_compress_batch(mpc_group *g, const uint8_t *lines, uint64_t n, uin
 {
   if (!g || (!lines && n)) return MPC_E_INVAL;
   if (n == 0) return MPC_OK;
+  group_refresh(g);
   return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, sizes, sel);
 }
 
@@ -1045,18 +1193,50 @@ int mpc_group_compress_batch_device(mpc_group *g, const void *d_lines, uint64_t 
   if (!g || (!d_lines && n)) return MPC_E_INVAL;
   if (((uintptr_t)d_lines) & 15u) return group_err(g, MPC_E_INVAL, "device line buffer must be 16-byte aligned");
   HIPCHK(g, hipSetDevice(g->stage.device));
-  return group_launch(g, d_lines, n, d_sizes, d_sel, (hipStream_t)hip_stream);
+  hipStream_t s = (hipStream_t)hip_stream;
+  const size_t nm = g->m.size();
+  bool any = false, scratch = false;
+  for (size_t i = 0; i < nm; i++) {
+    if (!group_accounts(g, (int)i)) continue;
+    any = true;
+    scratch = scratch || !(d_sizes && d_sizes[i]);
+  }
+  if (!any) return group_launch(g, d_lines, n, d_sizes, d_sel, s);
+  if (!scratch) return group_launch_accounted(g, d_lines, n, d_sizes, d_sel, s);
+  // accounting of a member without a sizes array of the caller's: pieces of kAccountLines lines, that member's sizes in a scratch array
+  g->d_scratch.resize(nm, nullptr);
+  g->piece_sizes.assign(nm, nullptr);
+  g->piece_sel.assign(nm, nullptr);
+  for (size_t i = 0; i < nm; i++)
+    if (group_accounts(g, (int)i) && !(d_sizes && d_sizes[i]) && !g->d_scratch[i])
+      HIPCHK(g, hipMalloc((void **)&g->d_scratch[i], kAccountLines * sizeof(uint16_t)));
+  if (!g->scratch_done) HIPCHK(g, hipEventCreateWithFlags(&g->scratch_done, hipEventDisableTiming));
+  if (g->recorded) HIPCHK(g, hipStreamWaitEvent(s, g->scratch_done, 0));
+  for (u64 at = 0; at < n; at += kAccountLines) {
+    const u64 take = std::min<u64>(n - at, kAccountLines);
+    for (size_t i = 0; i < nm; i++) {
+      g->piece_sizes[i] = (d_sizes && d_sizes[i]) ? d_sizes[i] + at : group_accounts(g, (int)i) ? g->d_scratch[i] : nullptr;
+      g->piece_sel[i] = (d_sel && d_sel[i]) ? d_sel[i] + at : nullptr;
+    }
+    const int rc = group_launch_accounted(g, static_cast<const uint8_t *>(d_lines) + at * (u64)g->stage.L, take, g->piece_sizes.data(), g->piece_sel.data(), s);
+    if (rc != MPC_OK) return rc;
+  }
+  HIPCHK(g, hipEventRecord(g->scratch_done, s));
+  g->recorded = true;
+  return MPC_OK;
 }
 
 int mpc_group_compress_npy(mpc_group *g, const char *path, uint64_t first_row, uint64_t n_rows, int skip_last_row, uint64_t *rows_done)
 {
   if (!g || !path) return MPC_E_INVAL;
+  group_refresh(g);
   return mpcstage::compress_npy(g->stage, sink_of(g), nullptr, path, first_row, n_rows, skip_last_row, rows_done);
 }
 
 int mpc_group_compress_gpgpusim_log(mpc_group *g, const char *log_path, uint64_t *requests_read, uint64_t *lines_done)
 {
   if (!g || !log_path) return MPC_E_INVAL;
+  group_refresh(g);
   return mpcstage::compress_gpgpusim_log(g->stage, sink_of(g), nullptr, log_path, requests_read, lines_done);
 }
 
@@ -1134,6 +1314,8 @@ int mpc_stats_reset(mpc_handle *h)
   if (rc != MPC_OK) return rc;
   HIPCHK(h, hipDeviceSynchronize());
   HIPCHK(h, hipMemset(h->d_raw, 0, (h->raw_len + kRouteWords) * sizeof(u64)));
+  if (h->acct.d_hist) HIPCHK(h, hipMemset(h->acct.d_hist, 0, MPC_SIZE_BINS * sizeof(u64)));
+  if (h->acct.on) h->acct.vpc_base.assign(h->acct.vpc_base.size(), 0);
   h->extra.assign(h->stats_len, 0);
   h->sc2.lines = h->sc2.warm = 0;     // SC2: the table and the line counter stay
   return MPC_OK;
@@ -1145,6 +1327,131 @@ int mpc_stats_set(mpc_handle *h, const uint64_t *vec, size_t n)
   int rc = mpc_stats_reset(h);
   if (rc != MPC_OK) return rc;
   for (size_t i = 0; i < n; i++) h->extra[i] = vec[i];
+  return MPC_OK;
+}
+
+// ---- size accounting (include/mpc_hip_sizes.h) ----------------------------------
+int mpc_size_hist_enable(mpc_handle *h)
+{
+  if (!h) return MPC_E_INVAL;
+  if (h->acct.on) return MPC_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->algorithm == Algo::VPC) {
+    // nothing to allocate: remember the statistics' histogram of the lines before this point
+    int rc = sync_all(h);
+    if (rc != MPC_OK) return rc;
+    HIPCHK(h, hipDeviceSynchronize());
+    std::vector<u64> raw(h->raw_len);
+    HIPCHK(h, hipMemcpy(raw.data(), h->d_raw, h->raw_len * sizeof(u64), hipMemcpyDeviceToHost));
+    vpc_size_hist(h, raw, h->acct.vpc_base);
+  } else {
+    if (hipMalloc((void **)&h->acct.d_hist, MPC_SIZE_BINS * sizeof(u64)) != hipSuccess) {
+      h->acct.d_hist = nullptr;
+      return set_err(h, MPC_E_NOMEM, "hipMalloc(size histogram) failed");
+    }
+    HIPCHK(h, hipMemset(h->acct.d_hist, 0, MPC_SIZE_BINS * sizeof(u64)));
+    HIPCHK(h, hipDeviceSynchronize());   // (the kernels run on non-blocking streams)
+    h->stage.account[0] = 1;
+  }
+  h->acct.on = true;
+  return MPC_OK;
+}
+
+int mpc_size_hist_get(mpc_handle *h, uint64_t *bins, size_t n)
+{
+  if (!h) return MPC_E_INVAL;
+  if (!h->acct.on) return set_err(h, MPC_E_INVAL, "size accounting is not switched on for this handle (mpc_size_hist_enable)");
+  if (!bins || n != MPC_SIZE_BINS) return set_err(h, MPC_E_INVAL, "a size histogram has MPC_SIZE_BINS (4096) bins");
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = sync_all(h);
+  if (rc != MPC_OK) return rc;
+  HIPCHK(h, hipDeviceSynchronize());   // callers may have used their own streams
+  rc = pattern_status(h);
+  if (rc != MPC_OK) return rc;
+  if (h->algorithm != Algo::VPC) {
+    HIPCHK(h, hipMemcpy(bins, h->acct.d_hist, MPC_SIZE_BINS * sizeof(u64), hipMemcpyDeviceToHost));
+    return MPC_OK;
+  }
+  std::vector<u64> raw(h->raw_len), now;
+  HIPCHK(h, hipMemcpy(raw.data(), h->d_raw, h->raw_len * sizeof(u64), hipMemcpyDeviceToHost));
+  vpc_size_hist(h, raw, now);
+  for (size_t b = 0; b < MPC_SIZE_BINS; b++) bins[b] = now[b] - h->acct.vpc_base[b];
+  return MPC_OK;
+}
+
+int mpc_group_best_enable(mpc_group *g)
+{
+  if (!g) return MPC_E_INVAL;
+  if (g->best.on) return MPC_OK;
+  std::vector<int> set;
+  for (int i = 0; i < (int)g->m.size(); i++)
+    if (g->m[(size_t)i]->algorithm != Algo::Pattern) set.push_back(i);
+  if (set.size() < 2)
+    return group_err(g, MPC_E_INVAL, "best-of needs at least two members that take part, this group has " + std::to_string(set.size()) +
+                                         " (a Pattern member is an analyser and does not)");
+  if (set.size() > MPC_SIZES_MAX)
+    return group_err(g, MPC_E_INVAL, "best-of takes at most " + std::to_string(MPC_SIZES_MAX) + " members, this group has " + std::to_string(set.size()));
+  HIPCHK(g, hipSetDevice(g->stage.device));
+  if (hipMalloc((void **)&g->best.d_acc, MPC_SIZES_BEST_LEN * sizeof(u64)) != hipSuccess) {
+    g->best.d_acc = nullptr;
+    return group_err(g, MPC_E_NOMEM, "hipMalloc(best-of accumulators) failed");
+  }
+  HIPCHK(g, hipMemset(g->best.d_acc, 0, MPC_SIZES_BEST_LEN * sizeof(u64)));
+  HIPCHK(g, hipDeviceSynchronize());   // (the kernels run on non-blocking streams)
+  g->best.set = std::move(set);
+  g->best.on = true;
+  return MPC_OK;
+}
+
+int mpc_group_best_get(mpc_group *g, uint64_t *bins, size_t n, uint64_t *wins, size_t n_members, uint64_t *best_bits, uint64_t *lines)
+{
+  if (!g) return MPC_E_INVAL;
+  if (!g->best.on) return group_err(g, MPC_E_INVAL, "best-of is not switched on for this group (mpc_group_best_enable)");
+  if ((bins && n != MPC_SIZE_BINS) || (wins && n_members != g->m.size()))
+    return group_err(g, MPC_E_INVAL, "best-of: bins has MPC_SIZE_BINS (4096) entries, wins one per group member");
+  int rc = mpc_group_sync(g);
+  if (rc != MPC_OK) return rc;
+  std::vector<u64> acc(MPC_SIZES_BEST_LEN);
+  HIPCHK(g, hipMemcpy(acc.data(), g->best.d_acc, acc.size() * sizeof(u64), hipMemcpyDeviceToHost));
+  u64 total = 0;
+  for (size_t b = 0; b < MPC_SIZE_BINS; b++) total += acc[b];
+  if (bins) std::memcpy(bins, acc.data(), MPC_SIZE_BINS * sizeof(u64));
+  if (wins) {
+    std::fill(wins, wins + n_members, 0);
+    for (size_t k = 0; k < g->best.set.size(); k++) wins[g->best.set[k]] = acc[MPC_SIZES_WINS + k];
+  }
+  if (best_bits) *best_bits = acc[MPC_SIZES_BITS];
+  if (lines) *lines = total;
+  return MPC_OK;
+}
+
+int mpc_group_best_reset(mpc_group *g)
+{
+  if (!g) return MPC_E_INVAL;
+  if (!g->best.on) return group_err(g, MPC_E_INVAL, "best-of is not switched on for this group (mpc_group_best_enable)");
+  const int rc = mpc_group_sync(g);
+  if (rc != MPC_OK) return rc;
+  HIPCHK(g, hipMemset(g->best.d_acc, 0, MPC_SIZES_BEST_LEN * sizeof(u64)));
+  return MPC_OK;
+}
+
+int mpc_size_sectors(const uint64_t *bins, size_t n, unsigned line_size, unsigned sector_bytes, uint64_t *classes, size_t n_classes,
+                     uint64_t *total_sectors, double *ratio)
+{
+  if (!bins || n != MPC_SIZE_BINS || sector_bytes == 0 || sector_bytes > line_size) return MPC_E_INVAL;
+  const u64 most = ((u64)line_size + sector_bytes - 1) / sector_bytes, sector_bits = 8ull * sector_bytes;
+  if (classes && n_classes != most) return MPC_E_INVAL;
+  std::vector<u64> cls(most, 0);
+  u64 lines = 0, sectors = 0;
+  for (u64 s = 0; s < MPC_SIZE_BINS; s++) {
+    const u64 c = std::min(std::max<u64>(1, (s + sector_bits - 1) / sector_bits), most);
+    cls[c - 1] += bins[s];
+    lines += bins[s];
+    sectors += bins[s] * c;
+  }
+  if (classes) std::memcpy(classes, cls.data(), most * sizeof(u64));
+  if (total_sectors) *total_sectors = sectors;
+  if (ratio) *ratio = sectors ? (double)(lines * most) / (double)sectors : 0.0;
   return MPC_OK;
 }
 

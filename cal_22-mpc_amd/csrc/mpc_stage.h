@@ -5,7 +5,9 @@
 // filled (from the caller's buffer, a .npy file or a .log file) and copied while chunk i is being evaluated; per-line
 // results come back through pinned buffers that exist per member and slot once a call has asked for that member's
 // output.  Calls of up to kMiniLines lines skip the slots: one pinned, device-visible buffer that the kernels read the
-// lines from and write the results to.
+// lines from and write the results to.  A member whose sizes are accounted on the device (Stager::account, mpc_sizes.h)
+// gets its device array of sizes whether or not the caller asked; the copy back and the pinned mirror stay tied to
+// "the caller asked".
 //
 // A handle is a group of one: the only difference between the two is "one output pointer" against "one output pointer
 // per member", so every function here takes arrays of `members` pointers.  What a stager feeds is told by a Sink:
@@ -71,6 +73,8 @@ struct Stager {
   bool slots_ready = false;
   std::vector<uint16_t *> ask_sizes;   // the launch in the making: per member the device buffer, null where the caller
   std::vector<int8_t *> ask_sel;       // did not ask (kept here so that no call allocates)
+  std::vector<char> account;           // per member: its sizes are wanted on the device whether or not the caller asked (size
+                                       // accounting, mpc_sizes.h); all 0 unless the owner switched accounting on
 };
 
 inline void init(Stager &st, int device, int L, size_t members)
@@ -85,6 +89,7 @@ inline void init(Stager &st, int device, int L, size_t members)
   }
   st.ask_sizes.assign(members, nullptr);
   st.ask_sel.assign(members, nullptr);
+  st.account.assign(members, 0);
 }
 
 // Creates what a staged call needs and is still missing.  When that is differs on purpose: a handle has nothing before
@@ -103,13 +108,12 @@ inline int ensure(Stager &st, const Sink &k)
   return MPC_OK;
 }
 
-// the per-line output buffers of member i in a slot, when a call asks for them for the first time
+// the per-line output buffers of member i in a slot, when a call asks for them for the first time.  The device array of
+// sizes also exists for a member whose sizes are accounted; its pinned mirror only once the caller asked.
 inline int ensure_outputs(Stager &st, const Sink &k, Slot &s, size_t i, bool sizes, bool sel)
 {
-  if (sizes && !s.d_sizes[i]) {
-    HIPCHK(k, hipMalloc((void **)&s.d_sizes[i], st.stage_lines * sizeof(uint16_t)));
-    HIPCHK(k, hipHostMalloc((void **)&s.h_sizes[i], st.stage_lines * sizeof(uint16_t), hipHostMallocDefault));
-  }
+  if ((sizes || st.account[i]) && !s.d_sizes[i]) HIPCHK(k, hipMalloc((void **)&s.d_sizes[i], st.stage_lines * sizeof(uint16_t)));
+  if (sizes && !s.h_sizes[i]) HIPCHK(k, hipHostMalloc((void **)&s.h_sizes[i], st.stage_lines * sizeof(uint16_t), hipHostMallocDefault));
   if (sel && !s.d_sel[i]) {
     HIPCHK(k, hipMalloc((void **)&s.d_sel[i], st.stage_lines));
     HIPCHK(k, hipHostMalloc((void **)&s.h_sel[i], st.stage_lines, hipHostMallocDefault));
@@ -139,7 +143,7 @@ inline int submit(Stager &st, const Sink &k, Slot &s, u64 lines, uint16_t *const
     s.user_sel[i] = (sel && sel[i]) ? sel[i] + first : nullptr;
     const int rc = ensure_outputs(st, k, s, i, s.user_sizes[i] != nullptr, s.user_sel[i] != nullptr);
     if (rc != MPC_OK) return rc;
-    st.ask_sizes[i] = s.user_sizes[i] ? s.d_sizes[i] : nullptr;
+    st.ask_sizes[i] = (s.user_sizes[i] || st.account[i]) ? s.d_sizes[i] : nullptr;
     st.ask_sel[i] = s.user_sel[i] ? s.d_sel[i] : nullptr;
   }
   HIPCHK(k, hipMemcpyAsync(s.d_in, s.h_in, lines * (u64)st.L, hipMemcpyHostToDevice, s.stream));
@@ -203,7 +207,7 @@ inline int in_place(Stager &st, const Sink &k, hipStream_t s, const uint8_t *lin
   uint16_t *out_sizes = reinterpret_cast<uint16_t *>(st.mini + kMiniLines * (size_t)st.L);
   int8_t *out_sel = reinterpret_cast<int8_t *>(out_sizes + nm * kMiniLines);
   for (size_t i = 0; i < nm; i++) {
-    st.ask_sizes[i] = (sizes && sizes[i]) ? out_sizes + i * kMiniLines : nullptr;
+    st.ask_sizes[i] = ((sizes && sizes[i]) || st.account[i]) ? out_sizes + i * kMiniLines : nullptr;
     st.ask_sel[i] = (sel && sel[i]) ? out_sel + i * kMiniLines : nullptr;
   }
   std::memcpy(st.mini, lines, (size_t)(n * (u64)st.L));
@@ -211,7 +215,7 @@ inline int in_place(Stager &st, const Sink &k, hipStream_t s, const uint8_t *lin
   if (rc != MPC_OK) { (void)hipStreamSynchronize(s); return rc; }   // (what was enqueued before the failure reads st.mini)
   HIPCHK(k, hipStreamSynchronize(s));
   for (size_t i = 0; i < nm; i++) {
-    if (st.ask_sizes[i]) std::memcpy(sizes[i], st.ask_sizes[i], (size_t)n * sizeof(uint16_t));
+    if (sizes && sizes[i]) std::memcpy(sizes[i], st.ask_sizes[i], (size_t)n * sizeof(uint16_t));
     if (st.ask_sel[i]) std::memcpy(sel[i], st.ask_sel[i], (size_t)n);
   }
   return k.status(k.ctx);

@@ -42,6 +42,34 @@ void CompressorSet::CompressBatch(const uint8_t *lines, unsigned long long n)
   if (rc != MPC_OK) fail("CompressorSet::CompressBatch", rc, mpc_group_last_error(m_Group));
 }
 
+void CompressorSet::EnableBest()
+{
+  Prepare();
+  int rc = mpc_group_best_enable(m_Group);
+  if (rc != MPC_OK) fail("CompressorSet::EnableBest", rc, mpc_group_last_error(m_Group));
+}
+
+BestReport CompressorSet::GetBest(unsigned sectorBytes)
+{
+  Prepare();
+  BestReport best(GetLineSize());
+  best.Sizes.SectorBytes = sectorBytes;
+  best.Sizes.Bins.assign(MPC_SIZE_BINS, 0);
+  best.Wins.assign(m_Members.size(), 0);
+  uint64_t bits = 0, lines = 0;
+  int rc = mpc_group_best_get(m_Group, best.Sizes.Bins.data(), best.Sizes.Bins.size(), best.Wins.data(), best.Wins.size(), &bits, &lines);
+  if (rc != MPC_OK) fail("CompressorSet::GetBest", rc, mpc_group_last_error(m_Group));
+  best.BestBits = bits;
+  best.Lines = lines;
+  size_t takingPart = 0;
+  for (Compressor *c : m_Members) {
+    mpc_info info;
+    takingPart += mpc_get_info(c->DeviceHandle(), &info) == MPC_OK && info.algorithm != 5;      // (5: Pattern)
+  }
+  while ((1ull << best.TagBits) < takingPart) best.TagBits++;
+  return best;
+}
+
 unsigned long long CompressorSet::CompressFile(const std::string &tracePath)
 {
   Prepare();

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "Compressor.h"
+#include "SizeReport.h"
 
 struct mpc_group;
 
@@ -37,6 +38,10 @@ public:
   // returns the number of lines evaluated
   unsigned long long CompressFile(const std::string &tracePath);
   CompResult *GetResult(size_t i) { return m_Members[i]->GetResult(); }
+  // ADDITIVE: account, from now on, the per-line smallest size over the members (mpc_group_best_enable: every member
+  // but Pattern ones, ties to the first minimal member); refused with a message when fewer than two take part
+  void EnableBest();
+  BestReport GetBest(unsigned sectorBytes = ACCESS_GRAN);
 
 private:
   void Prepare();      // members' buffered lines first

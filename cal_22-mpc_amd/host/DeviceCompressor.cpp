@@ -62,6 +62,23 @@ unsigned long long DeviceCompressor::CompressFile(const std::string &tracePath)
   return done;
 }
 
+void DeviceCompressor::EnableSizeHistogram()
+{
+  FlushLines();
+  int rc = mpc_size_hist_enable(m_Handle);
+  if (rc != MPC_OK) Fail(m_Tag + "::EnableSizeHistogram", rc);
+}
+
+SizeReport DeviceCompressor::GetSizeHistogram(unsigned sectorBytes)
+{
+  FlushLines();
+  SizeReport report(m_LineSize, sectorBytes);
+  report.Bins.assign(MPC_SIZE_BINS, 0);
+  int rc = mpc_size_hist_get(m_Handle, report.Bins.data(), report.Bins.size());
+  if (rc != MPC_OK) Fail(m_Tag + "::GetSizeHistogram", rc);
+  return report;
+}
+
 CompResult *DeviceCompressor::GetResult()
 {
   FlushLines();

@@ -1,5 +1,5 @@
 // DeviceCompressor.h -- ADDITIVE, no counterpart in the reference: what the six GPU evaluators (VPC, BDI, FPC, BPC,
-// SC2, Pattern) share over one libmpc_hip handle (include/mpc_hip.h).  A derived class keeps its constructor (the
+// SC2, Pattern) share over one libmpc_hip handle (include/mpc_hip.h), size accounting (SizeReport.h) included.  A derived class keeps its constructor (the
 // create call, its result object, its name), LoadResult() and whatever the reference's class of that name has of its own.
 #ifndef MPC_HOST_DEVICECOMPRESSOR_H
 #define MPC_HOST_DEVICECOMPRESSOR_H
@@ -7,6 +7,7 @@
 #include <string>
 
 #include "Compressor.h"
+#include "SizeReport.h"
 
 namespace comp
 {
@@ -27,6 +28,10 @@ public:
   virtual unsigned GetLineSize() { return m_LineSize; }
   // (a handle that has been handed out counts as fed: whoever holds it may have sent lines through it)
   virtual mpc_handle *DeviceHandle() { FlushLines(); m_Fed = true; return m_Handle; }
+  // ADDITIVE: count, from now on, how many lines compress to how many bits (mpc_size_hist_enable); off by default
+  void EnableSizeHistogram();
+  // ... that histogram (mpc_size_hist_get), buffered lines evaluated first; a failure (not enabled) exits like every other
+  SizeReport GetSizeHistogram(unsigned sectorBytes = ACCESS_GRAN);
 
 protected:
   // tag: the short name in front of this class's messages ("BDI", "VPC", ...)

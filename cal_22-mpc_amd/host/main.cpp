@@ -8,6 +8,9 @@
 // and reported as not part of this build.
 // ADDITIVE: -a takes a comma-separated list (-a VPC,BDI,FPC,BPC): every algorithm of the list is evaluated in ONE pass
 // over the trace (comp::CompressorSet) and writes exactly the files a run with its name alone writes.
+// ADDITIVE: --size-histogram / --sector BYTES also write OUTDIR/<stem>_results_sizes.csv (comp::SizeReport: the
+// distribution of the per-line sizes and the sectors they occupy) and, for a list, the per-line best of the list as
+// BEST_results_sizes.csv and a "BEST comp.ratio:" line.  Without them nothing changes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,8 +27,9 @@
 
 #define REQ_SIZE 32   // line size asked of the APSim loader (reference main.cpp:23)
 
+struct Args;
 static int runList(const std::vector<std::string> &names, const std::string &tracePath, const std::string &configPath,
-                   const std::string &outputDirPath);
+                   const std::string &outputDirPath, const Args &a);
 
 static const char *kHelp =
     "Usage:\n"
@@ -38,6 +42,11 @@ static const char *kHelp =
     "                       .log, .npy\n"
     "  -c, --config arg     Config file path (.json).\n"
     "  -o, --output arg     Output directory path\n"
+    "      --size-histogram Also write <stem>_results_sizes.csv: lines per compressed\n"
+    "                       size and per number of sectors; for a list also the\n"
+    "                       per-line best of the list (BEST_results_sizes.csv)\n"
+    "      --sector arg     Sector size in bytes for that file. Default=32\n"
+    "                       (implies --size-histogram)\n"
     "  -h, --help           Print usage\n";
 
 struct Args {
@@ -45,6 +54,8 @@ struct Args {
   bool has_algorithm = false, has_input = false, has_config = false, has_output = false, help = false;
   bool per_line = false;   // ADDITIVE --per-line: the reference's loop (GetCacheline -> CompressLine per line) instead of batches
   unsigned long long line_buffer = 0;   // ADDITIVE --line-buffer N: that loop with Compressor::SetLineBuffering(N)
+  bool size_histogram = false;          // ADDITIVE --size-histogram: <stem>_results_sizes.csv (SizeReport.h)
+  unsigned sector = ACCESS_GRAN;        // ADDITIVE --sector BYTES: the sector size of that file; implies --size-histogram
 };
 
 static bool take_value(int argc, char **argv, int &i, const std::string &arg, const char *shortf, const char *longf,
@@ -82,7 +93,7 @@ static bool refusedAsNotBuilt(const std::string &name)
 }
 
 // compressor by name (reference main.cpp:85-127); nullptr for a name this build does not evaluate
-static comp::Compressor *makeEvaluator(const std::string &name, const std::string &configPath, unsigned lineSize)
+static comp::DeviceCompressor *makeEvaluator(const std::string &name, const std::string &configPath, unsigned lineSize)
 {
   if (name == "VPC") return new comp::VPC(configPath);
   if (name == "BDI") return new comp::BDI(lineSize);
@@ -100,6 +111,20 @@ static trace::Loader *openTrace(const std::string &tracePath, trace::MemReq_t **
     abort();
   }
   return loader;
+}
+
+// --sector against the trace: a sector is at most a line
+static void requireSector(const Args &a, unsigned traceLineSize)
+{
+  if (!a.size_histogram || a.sector <= traceLineSize) return;
+  printf("--sector %u: a sector cannot be larger than the trace's %u-byte lines.\n", a.sector, traceLineSize);
+  exit(1);
+}
+
+static void writeSizes(comp::SizeReport report, const std::string &workloadName, const std::string &outputDirPath,
+                       const std::string &saveFileName)
+{
+  report.Print(workloadName, outputDirPath + "/" + saveFileName + "_results_sizes.csv");
 }
 
 static void requireLineSize(unsigned traceLineSize, unsigned evaluatorLineSize)
@@ -169,6 +194,23 @@ int main(int argc, char **argv)
       a.line_buffer = strtoull(argv[++i], nullptr, 10);
       continue;
     }
+    if (arg == "--size-histogram") { a.size_histogram = true; continue; }
+    if (arg == "--sector" || arg.compare(0, 9, "--sector=") == 0) {
+      if (arg == "--sector" && i + 1 >= argc) {
+        std::cout << "Option 'sector' is missing an argument" << std::endl;
+        exit(1);
+      }
+      const std::string value = arg == "--sector" ? argv[++i] : arg.substr(9);
+      char *end = nullptr;
+      const unsigned long long bytes = strtoull(value.c_str(), &end, 10);
+      if (value.empty() || value[0] < '0' || value[0] > '9' || *end != 0 || bytes == 0 || bytes > 0xffffffffull) {
+        std::cout << "--sector takes a number of bytes from 1 to the trace's line size, not \"" << value << "\"." << std::endl;
+        return 1;
+      }
+      a.sector = (unsigned)bytes;
+      a.size_histogram = true;
+      continue;
+    }
     if (take_value(argc, argv, i, arg, "-a", "algorithm", a.algorithm, a.has_algorithm)) continue;
     if (take_value(argc, argv, i, arg, "-i", "input", a.input, a.has_input)) continue;
     if (take_value(argc, argv, i, arg, "-c", "config", a.config, a.has_config)) continue;
@@ -206,12 +248,13 @@ int main(int argc, char **argv)
     return 0;
   }
   const std::string tracePath = a.input, configPath = a.config, outputDirPath = a.has_output ? a.output : "";
-  if (!list.empty()) return runList(list, tracePath, configPath, outputDirPath);
+  if (!list.empty()) return runList(list, tracePath, configPath, outputDirPath, a);
 
   trace::MemReq_t *memReq = nullptr;
   trace::Loader *loader = openTrace(tracePath, &memReq);
+  requireSector(a, loader->GetCachelineSize());
 
-  comp::Compressor *compressor = makeEvaluator(algorithm, configPath, loader->GetCachelineSize());
+  comp::DeviceCompressor *compressor = makeEvaluator(algorithm, configPath, loader->GetCachelineSize());
   if (!compressor) {
     if (refusedAsNotBuilt(algorithm)) return 1;
     std::cerr << "Invalid name of algorithm." << std::endl;
@@ -223,6 +266,7 @@ int main(int argc, char **argv)
   // loop itself or the loader hands out single lines only.
   if (a.line_buffer) compressor->SetLineBuffering(a.line_buffer);
   requireLineSize(loader->GetCachelineSize(), compressor->GetLineSize());
+  if (a.size_histogram) compressor->EnableSizeHistogram();
   if (!a.per_line && (loader->SupportsBatch() || !loader->GetStreamablePath().empty()))
     compressBatches(compressor, loader);
   else
@@ -233,6 +277,7 @@ int main(int argc, char **argv)
   if (!workloadNameOf(tracePath, workloadName)) return 1;
   std::cout << "comp.ratio: " << mpctext::num(compStat->CompRatio) << std::endl;
   writeResults(compStat, workloadName, outputDirPath, saveFileName);
+  if (a.size_histogram) writeSizes(compressor->GetSizeHistogram(a.sector), workloadName, outputDirPath, saveFileName);
 
   delete memReq;      // (the reference leaks its request object)
   delete loader;
@@ -241,9 +286,10 @@ int main(int argc, char **argv)
 }
 
 // -a with a list: one pass over the trace for all of them, then each algorithm's own result files and one
-// "<name> comp.ratio: <ratio>" line each, in list order.
+// "<name> comp.ratio: <ratio>" line each, in list order.  With --size-histogram: each algorithm's sizes file, then the
+// per-line best of the list, "BEST comp.ratio: <original bits / (best bits + lines x tag bits)>" and BEST_results_sizes.csv.
 static int runList(const std::vector<std::string> &names, const std::string &tracePath, const std::string &configPath,
-                   const std::string &outputDirPath)
+                   const std::string &outputDirPath, const Args &a)
 {
   std::string workloadName;
   if (!workloadNameOf(tracePath, workloadName)) return 1;
@@ -251,19 +297,30 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
   trace::MemReq_t *memReq = nullptr;
   trace::Loader *loader = openTrace(tracePath, &memReq);
   const unsigned lineSize = loader->GetCachelineSize();
+  requireSector(a, lineSize);
+  std::vector<comp::DeviceCompressor *> evaluators;
   std::vector<comp::Compressor *> members;
   for (const std::string &n : names) {
-    members.push_back(makeEvaluator(n, configPath, lineSize));      // (main() has checked the names)
+    evaluators.push_back(makeEvaluator(n, configPath, lineSize));      // (main() has checked the names)
+    members.push_back(evaluators.back());
     requireLineSize(lineSize, members.back()->GetLineSize());
+    if (a.size_histogram) evaluators.back()->EnableSizeHistogram();
   }
   {
     comp::CompressorSet set(members);
+    if (a.size_histogram) set.EnableBest();
     compressBatches(&set, loader);
     for (size_t i = 0; i < names.size(); i++) {
       comp::CompResult *compStat = set.GetResult(i);
       const std::string saveFileName = (names[i] == "VPC") ? parseConfig(configPath) : names[i];
       std::cout << names[i] << " comp.ratio: " << mpctext::num(compStat->CompRatio) << std::endl;
       writeResults(compStat, workloadName, outputDirPath, saveFileName);
+      if (a.size_histogram) writeSizes(evaluators[i]->GetSizeHistogram(a.sector), workloadName, outputDirPath, saveFileName);
+    }
+    if (a.size_histogram) {
+      const comp::BestReport best = set.GetBest(a.sector);
+      std::cout << "BEST comp.ratio: " << mpctext::num(best.CompRatio()) << std::endl;
+      writeSizes(best.Sizes, workloadName, outputDirPath, "BEST");
     }
   }
   delete memReq;

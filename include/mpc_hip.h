@@ -286,6 +286,17 @@ int mpc_group_compress_gpgpusim_log(mpc_group *g, const char *log_path, uint64_t
 /* Waits for the group's slots and for the whole device (mpc_sync). */
 int mpc_group_sync(mpc_group *g);
 
+/* ---- size accounting: per-evaluator histograms of the per-line sizes, the per-line best-of of a group, sectors ----
+ * Additive and off by default; declared in a header of its own, next to this one, which needs the two handle types
+ * above.  MPC_ABI_VERSION, the statistics vectors, the raw layouts and mpc_info are unchanged by it.                */
+#ifdef __cplusplus
+}
+#endif
+#include "mpc_hip_sizes.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+
 /* ---- measurement helpers (bench.py; not part of the evaluator) -----------
  * Synthetic device-resident traces of SURVEY.md 8d, generated on the GPU:
  * kind 0 zeros, 1 random u32, 2 fp32 sine, 3 mixed int/fp, 4 pointer qwords.

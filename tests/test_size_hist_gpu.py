@@ -502,3 +502,230 @@ def test_cli_size_files(mpc, configs, baselines, traces, tmp_path):
     refused.mkdir()
     r = subprocess.run([cli, "-a", "BDI", "--sector", "128", "-i", npy, "-o", str(refused)], cwd=bindir, capture_output=True, text=True, timeout=600)
     assert r.returncode == 1 and "--sector 128" in r.stdout and os.listdir(refused) == []
+
+
+# ---- 9. the accounting pass at its full width --------------------------------------------------------------------------
+# MPC_SIZES_MAX = 8 arrays a launch; with eight histograms and the best-of one a workgroup keeps nine LDS histograms
+# (144 KiB, beyond the 64 KiB a kernel gets by default).
+def make_spec(mpc, spec, L):
+    """"BDI" / "FPC" / "BPC" / "PATTERN", or ("SC2", S)."""
+    if isinstance(spec, tuple):
+        return mpc.SC2(L, spec[1])
+    return getattr(mpc, {"PATTERN": "Pattern"}.get(spec, spec))(L)
+
+
+def spec_sizes(oracle, spec, L, lines):
+    if isinstance(spec, tuple):
+        return sc2_ref.SC2Ref(L, spec[1]).feed(lines)[0].astype(np.int64)
+    return oracle_sizes(oracle, None, spec, L, lines)
+
+
+def open_group(mpc, specs, L, best):
+    members = [make_spec(mpc, s, L) for s in specs]
+    for ev in members:
+        ev.enable_size_histogram()
+    group = mpc.EvaluatorSet(members)
+    if best:
+        group.enable_best()
+    return group, members
+
+
+def close_group(group, members):
+    group.close()
+    for ev in members:
+        ev.close()
+
+
+def check_wide_group(group, members, specs, want, best_expected, tag):
+    for i, (spec, ev) in enumerate(zip(specs, members)):
+        same_hist(f"{tag}: member {i} {spec}", ev.size_histogram(), bincount(want[i]))
+    if best_expected is None:
+        return None
+    best, winner, part = best_expected
+    got = group.best()
+    same_hist(f"{tag}: best-of", got["bins"], bincount(best))
+    want_wins = np.zeros(len(specs), np.uint64)
+    for k, i in enumerate(part):
+        want_wins[i] = int((winner == k).sum())
+    assert got["wins"].tolist() == want_wins.tolist(), tag
+    assert got["best_bits"] == int(best.sum()) and got["lines"] == len(best), tag
+    return got
+
+
+EIGHT = ["BDI", "FPC", "BPC", ("SC2", 1500), "BDI", "FPC", "BPC", ("SC2", 700)]
+
+
+def best_of(want, specs):
+    part = [i for i, s in enumerate(specs) if s != "PATTERN"]
+    M = np.stack([want[i] for i in part])
+    return M.min(axis=0), M.argmin(axis=0), part          # argmin: the first minimal member
+
+
+def test_eight_members_with_best_of(mpc, oracle):
+    """Eight arrays and nine LDS histograms in one launch.  Members 4-6 are copies of members 0-2: they tie on every line
+    and the first minimal member wins, so they win nothing."""
+    import torch
+    L = 64
+    lines = group_lines(oracle, L)
+    n = len(lines)
+    want = [spec_sizes(oracle, s, L, lines) for s in EIGHT]
+    expected = best_of(want, EIGHT)
+    assert len(expected[2]) == 8 and len(set(expected[1].tolist())) >= 3          # several members win somewhere
+    # host path: an in-place call, then a staged one
+    group, members = open_group(mpc, EIGHT, L, best=True)
+    group.compress_lines(lines[:300], want_sizes=False, want_selected=False)
+    group.compress_lines(lines[300:], want_sizes=False, want_selected=False)
+    got = check_wide_group(group, members, EIGHT, want, expected, "host")
+    assert got["wins"][4:7].tolist() == [0, 0, 0] and int(got["wins"].sum()) == n
+    assert got["tag_bits"] == 3
+    close_group(group, members)
+    # device path: fresh members (SC2 counts its lines), the caller's sizes arrays for every other member
+    group, members = open_group(mpc, EIGHT, L, best=True)
+    d_lines = torch.from_numpy(lines).to("cuda:0")
+    d_sizes = [torch.zeros(n, dtype=torch.int16, device="cuda:0") if i % 2 == 0 else None for i in range(len(EIGHT))]
+    group.compress_device(d_lines.data_ptr(), n, [t.data_ptr() if t is not None else 0 for t in d_sizes],
+                          stream=torch.cuda.current_stream().cuda_stream)
+    got = check_wide_group(group, members, EIGHT, want, expected, "device")
+    assert got["wins"][4:7].tolist() == [0, 0, 0] and got["tag_bits"] == 3
+    for i, t in enumerate(d_sizes):
+        if t is not None:
+            assert (t.cpu().numpy().view(np.uint16) == want[i]).all(), i
+    close_group(group, members)
+
+
+def test_nine_members_take_two_launches_and_no_best_of(mpc, oracle):
+    """More members than one launch takes: best-of is refused, and without it the nine histograms come from two
+    launches of the pass (eight arrays, then one)."""
+    import torch
+    L = 64
+    specs = EIGHT + [("SC2", 300)]
+    lines = group_lines(oracle, L)
+    n = len(lines)
+    want = [spec_sizes(oracle, s, L, lines) for s in specs]
+    group, members = open_group(mpc, specs, L, best=False)
+    with pytest.raises(mpc.MpcError) as e:
+        group.enable_best()
+    assert e.value.code == MPC_E_INVAL and "at most 8" in str(e.value)
+    with pytest.raises(mpc.MpcError) as e:
+        group.best()
+    assert e.value.code == MPC_E_INVAL
+    group.compress_lines(lines[:300], want_sizes=False, want_selected=False)
+    group.compress_lines(lines[300:], want_sizes=False, want_selected=False)
+    check_wide_group(group, members, specs, want, None, "host")
+    close_group(group, members)
+    group, members = open_group(mpc, specs, L, best=False)
+    d_lines = torch.from_numpy(lines).to("cuda:0")
+    group.compress_device(d_lines.data_ptr(), n, stream=torch.cuda.current_stream().cuda_stream)
+    check_wide_group(group, members, specs, want, None, "device")
+    close_group(group, members)
+
+
+def test_eight_members_and_a_pattern_member(mpc, oracle):
+    """A Pattern member does not take part: best-of over the other eight is accepted, Pattern wins nothing, and its
+    histogram comes from a launch of its own."""
+    L = 64
+    specs = EIGHT[:3] + ["PATTERN"] + EIGHT[3:]
+    lines = group_lines(oracle, L)
+    want = [spec_sizes(oracle, s, L, lines) for s in specs]
+    expected = best_of(want, specs)
+    assert expected[2] == [0, 1, 2, 4, 5, 6, 7, 8]
+    group, members = open_group(mpc, specs, L, best=True)
+    group.compress_lines(lines[:300], want_sizes=False, want_selected=False)
+    group.compress_lines(lines[300:], want_sizes=False, want_selected=False)
+    got = check_wide_group(group, members, specs, want, expected, "host")
+    assert int(got["wins"][3]) == 0 and got["wins"][5:8].tolist() == [0, 0, 0] and got["tag_bits"] == 3
+    close_group(group, members)
+
+
+# ---- 10. the pass alone, on synthetic sizes ----------------------------------------------------------------------------
+# mpc_launch_sizes and mpc_sizes_wg_per_cu (csrc/mpc_sizes.hip) are extern "C" and exported by libmpc_hip.so: called through
+# ctypes on torch-owned arrays, against numpy.
+SIZES_MAX = 8
+BEST_LEN = BINS + SIZES_MAX + 1
+SPECIAL_SIZES = np.array([0, 1, 4094, 4095, 4096, 0x7FFF, 0x8000, 0xFFFF], dtype=np.uint16)
+
+
+def sizes_abi(mpc):
+    import ctypes as C
+
+    class MpcSizesArgs(C.Structure):          # csrc/mpc_sizes.h
+        _fields_ = [("sizes", C.c_void_p * SIZES_MAX), ("hist", C.c_void_p * SIZES_MAX), ("best", C.c_void_p), ("m", C.c_int)]
+    lib = mpc.lib()
+    lib.mpc_launch_sizes.argtypes = [C.POINTER(MpcSizesArgs), C.c_uint64, C.c_int, C.c_void_p]
+    lib.mpc_launch_sizes.restype = C.c_int
+    lib.mpc_sizes_wg_per_cu.argtypes = [C.POINTER(MpcSizesArgs)]
+    lib.mpc_sizes_wg_per_cu.restype = C.c_int
+    return lib, MpcSizesArgs
+
+
+def synthetic_sizes(rng, n, kind):
+    """kind 0: the special sizes and random ones, line by line.  kind 1: per 512 lines (what a wave takes per loop
+    step: 64 lanes x 8 lines) one, two, three and 64 distinct values across the lanes -- the two aggregation rounds and
+    the lane-by-lane remainder of wave_hist_add."""
+    palette = np.concatenate([SPECIAL_SIZES, rng.integers(0, 1 << 16, 56).astype(np.uint16)])
+    if kind == 0:
+        draw = palette[rng.integers(0, len(palette), n)]
+        return np.where(rng.random(n) < 0.5, draw, rng.integers(0, 2300, n).astype(np.uint16)).astype(np.uint16)
+    i = np.arange(n)
+    lane, segment = (i // 8) % 64, i // 512
+    distinct = np.array([1, 2, 3, 64])[segment % 4]
+    return rng.permutation(palette)[lane % distinct].astype(np.uint16)
+
+
+def test_the_pass_alone_on_synthetic_sizes(mpc):
+    import ctypes as C
+    import torch
+    lib, MpcSizesArgs = sizes_abi(mpc)
+    rng = np.random.default_rng(4096)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    case = 0
+    for m in range(1, SIZES_MAX + 1):
+        for n in (1, 7, 8, 9, 511, 512, 513, 2051):
+            for one_workgroup in (True, False):
+                case += 1
+                with_best = m >= 2 and case % 4 != 0
+                no_hist = [(i + case) % 3 == 0 for i in range(m)]
+                shifted = case % m if case % 2 else -1        # this member's array starts one element in: 2-byte loads for all
+                host = [synthetic_sizes(rng, n, (i + case) % 2) for i in range(m)]
+                dev = [torch.from_numpy(np.concatenate([np.full(8, 0x1111, np.uint16), a, np.full(8, 0x2222, np.uint16)]).view(np.int16)).to("cuda:0")
+                       for a in host]
+                d_hist = [None if no_hist[i] else torch.zeros(BINS, dtype=torch.int64, device="cuda:0") for i in range(m)]
+                d_best = torch.zeros(BEST_LEN, dtype=torch.int64, device="cuda:0") if with_best else None
+                A = MpcSizesArgs()
+                A.m = m
+                for i in range(m):
+                    A.sizes[i] = dev[i].data_ptr() + 2 * (8 + (1 if i == shifted else 0))
+                    A.hist[i] = None if no_hist[i] else d_hist[i].data_ptr()
+                A.best = d_best.data_ptr() if with_best else None
+                n_hist = sum(not x for x in no_hist) + (1 if with_best else 0)
+                per_cu = lib.mpc_sizes_wg_per_cu(C.byref(A))          # (pinned to its documented formula: a regression pin, not a second opinion)
+                assert per_cu == (0 if n_hist == 0 else min(8, (160 * 1024) // (n_hist * BINS * 4 + 128))), (m, n_hist, per_cu)
+                grid = 1 if one_workgroup else max(1, per_cu * cus)
+                torch.cuda.synchronize()
+                assert lib.mpc_launch_sizes(C.byref(A), n, grid, None) == 0, (m, n, grid)
+                torch.cuda.synchronize()
+                tag = f"m={m} n={n} grid={grid} best={with_best} no_hist={no_hist} shifted={shifted}"
+                # the member whose array is shifted reads elements 1 .. n of its data (the last one is the 0x2222 behind it)
+                seen = [np.concatenate([a[1:], [0x2222]]).astype(np.uint16) if i == shifted else a for i, a in enumerate(host)]
+                for i in range(m):
+                    if not no_hist[i]:
+                        same_hist(f"{tag}: member {i}", d_hist[i].cpu().numpy().view(np.uint64),
+                                  bincount(np.minimum(seen[i].astype(np.int64), BINS - 1)))
+                if with_best:
+                    M = np.stack([a.astype(np.int64) for a in seen])
+                    best, winner = M.min(axis=0), M.argmin(axis=0)
+                    got = d_best.cpu().numpy().view(np.uint64)
+                    same_hist(f"{tag}: best-of", got[:BINS].copy(), bincount(np.minimum(best, BINS - 1)))
+                    assert got[BINS:BINS + SIZES_MAX].tolist() == np.bincount(winner, minlength=SIZES_MAX).tolist(), tag
+                    assert int(got[BINS + SIZES_MAX]) == int(best.sum()), tag          # the unclipped sizes
+    # refused: no array, more than eight, a best-of over one member
+    A = MpcSizesArgs()
+    for m in (0, SIZES_MAX + 1):
+        A.m = m
+        assert lib.mpc_launch_sizes(C.byref(A), 8, 1, None) != 0
+    A.m = 1
+    scratch = torch.zeros(BEST_LEN, dtype=torch.int64, device="cuda:0")
+    A.sizes[0], A.best = scratch.data_ptr(), scratch.data_ptr()
+    assert lib.mpc_launch_sizes(C.byref(A), 8, 1, None) != 0
+    torch.cuda.synchronize()
+    assert not scratch.any()

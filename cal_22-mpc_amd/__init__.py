@@ -25,6 +25,8 @@ LIB_PATH = os.environ.get("MPC_HIP_LIB") or os.path.join(HERE, "libmpc_hip.so") 
 
 MPC_SIZE_BINS = 4096          # bins of a size histogram (include/mpc_hip_sizes.h)
 MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2, MPC_PATH_PATTERN = 1, 2, 3, 4, 5, 6, 7
+MPC_PATH_CPACK = 8
+MPC_CPACK_DICT_CARRIED, MPC_CPACK_DICT_PER_LINE = 0, 1     # mpc_create_cpack's dictionary_scope
 SYNTH_KINDS = {"zeros": 0, "random_u32": 1, "sine_f32": 2, "mixed": 3, "pointers_u64": 4}
 
 
@@ -83,6 +85,7 @@ def lib() -> C.CDLL:
             "mpc_sc2_table": ([H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
             "mpc_create_pattern": ([C.c_uint, C.c_int, C.POINTER(H)], C.c_int),
             "mpc_pattern_distinct_lines": ([H, C.POINTER(C.c_uint64)], C.c_int),
+            "mpc_create_cpack": ([C.c_uint, C.c_int, C.c_int, C.POINTER(H)], C.c_int),
             "mpc_destroy": ([H], None),
             "mpc_get_info": ([H, C.POINTER(Info)], C.c_int),
             "mpc_last_error": ([H], C.c_char_p),
@@ -141,7 +144,7 @@ EXPORTED_SYMBOLS = [
     "mpc_synth_fill", "mpc_read_bandwidth_probe",
     "mpc_group_create", "mpc_group_destroy", "mpc_group_last_error", "mpc_group_form", "mpc_group_compress_batch",
     "mpc_group_compress_batch_device", "mpc_group_compress_npy", "mpc_group_compress_gpgpusim_log", "mpc_group_sync",
-    "mpc_create_pattern", "mpc_pattern_distinct_lines",
+    "mpc_create_pattern", "mpc_pattern_distinct_lines", "mpc_create_cpack",
 ]
 # The SC2 entry points of include/mpc_hip.h.  Kept apart from EXPORTED_SYMBOLS, which lists the names of the
 # header's lowercase-letter form (mpc_[a-z_]+) only; every one of both lists is exported by libmpc_hip.so.
@@ -208,7 +211,7 @@ def _totals(v, ratio=_ratio_or_zero) -> Dict:
 
 
 class _Evaluator:
-    """Common part of the six evaluators: creates and owns one ``mpc_handle``."""
+    """Common part of the seven evaluators: creates and owns one ``mpc_handle``."""
 
     def __init__(self, create: str, *args):
         """``create``: name of the library's create function; ``args``: its arguments in front of the handle."""
@@ -451,6 +454,28 @@ class Pattern(_Evaluator):
         return int(n.value)
 
 
+CPACK_DICTIONARY = {"carried": MPC_CPACK_DICT_CARRIED, "line": MPC_CPACK_DICT_PER_LINE}
+
+
+class CPACK(_Evaluator):
+    """C-Pack (reference ``CPACK.cpp``) with a PER-LINE dictionary: the numbers of a fresh ``comp::CPACK(lineSize)`` per
+    line, NOT those of the reference's ``-a CPACK`` run, whose one object carries its dictionary from line to line.
+    ``dictionary="line"`` is the only scope the library evaluates; ``"carried"`` (and anything else) raises ``MpcError``
+    with the library's message.  Per-line ``selected`` is always 0; a size may exceed 8 x line_size."""
+
+    PATTERNS = ("ZZZZ", "ZZZX", "MMMM", "MMMX", "MMXX", "XXXX")      # CPACKPattern order; 2, 12, 6, 16, 24, 34 bits
+
+    def __init__(self, line_size: int, dictionary: str = "line", device: int = -1):
+        scope = CPACK_DICTIONARY.get(dictionary, -1) if isinstance(dictionary, str) else int(dictionary)
+        super().__init__("mpc_create_cpack", line_size, scope, device)
+        self.dictionary = "line"
+
+    def result(self) -> Dict:
+        """``CPACKResult`` (reference ``CPACK.h:28-96``): the totals, ``total_words`` and the six pattern counts."""
+        v = self.stats_vector()
+        return {"name": "C-Pack", **_totals(v), "total_words": int(v[3]), "counts": [int(x) for x in v[4:10]]}
+
+
 class EvaluatorSet:
     """A group of evaluators of one line size on one device that are fed together (``mpc_group``): the trace is
     staged once per chunk and every member sees every line as if it had been called alone.  The members keep their
@@ -461,7 +486,7 @@ class EvaluatorSet:
         self.members = list(evaluators)
         self._g = C.c_void_p()
         if any(not isinstance(e, _Evaluator) or not e._h for e in self.members):
-            raise ValueError("EvaluatorSet takes open VPC / BDI / FPC / BPC / SC2 / Pattern evaluators")
+            raise ValueError("EvaluatorSet takes open VPC / BDI / FPC / BPC / SC2 / Pattern / CPACK evaluators")
         arr = (C.c_void_p * max(1, len(self.members)))(*[e._h.value for e in self.members])
         rc = lib().mpc_group_create(arr, len(self.members), C.byref(self._g))
         if rc != 0:

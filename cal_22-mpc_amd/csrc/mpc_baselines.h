@@ -7,6 +7,7 @@
 //   bdi_check, bdi_screen, bdi_line, BdiLane      BDI: one line; a lane's run of results and its wave's queue
 //   fpc_line, FpcAcc                      FPC: one line; a lane's totals
 //   bpc_line, BpcAcc                      BPC: one line; a lane's pattern counts
+//   cpack_line, CpackAcc                  C-Pack with a per-line dictionary: one line; a lane's totals
 //
 // Device code only; gfx950.
 #pragma once
@@ -703,5 +704,106 @@ struct BpcAcc {
       flush(s_counts);
       since_flush = 0;
     }
+  }
+};
+
+// ---------------------------------------------------------------------------
+// C-Pack with a PER-LINE dictionary (reference CPACK.cpp:7-101 with a fresh comp::CPACK per line; the reference's own
+// driver carries the dictionary from line to line, which is not evaluated here: DESIGN.md 8).  The dictionary is a
+// FIFO of 16 words, all zero when the line starts.  Per 32-bit word b0 b1 b2 b3 (memory order; b0 = the low byte):
+//   b0 = b1 = b2 = 0                       ZZZZ 2 bits if b3 = 0, else ZZZX 12; no dictionary access
+//   the FIRST entry from the front with the same (b0, b1) decides: b2 differs MMXX 24, b3 differs MMMX 16, equal MMMM 6;
+//     a hit changes nothing
+//   no such entry                          XXXX 34; the word is pushed at the back and the front entry leaves
+// One lane per line, the line in registers, and no dictionary: with the key of a word = its (b0, b1) and C = the misses
+// before it in the line,
+//   - pushed entries that are still in the FIFO have pairwise different keys (a word is pushed only when no entry has
+//     its key), so at most one entry can match: the LATEST earlier miss with the word's key, if it is still there;
+//   - the entry pushed as miss number p (from 0) leaves with miss number p + 16: it is there at a word iff C - p <= 16;
+//   - the zero entries are at the front while C < 16: a word with key 0 that is not ZZZ* then gets MMXX (its b2 is not
+//     0), and nothing with key 0 has been pushed;
+//   - up to 16 words (64 bytes) C <= 15 throughout: nothing is ever evicted, and a word with a non-zero key is decided by
+//     the FIRST earlier word with its key (that one missed) -- pairwise compares of the words, no serial dependence.
+// The size is linear in nested counts, as FPC's: with a = ZZZ* words, b = ZZZZ, c = hits, d = hits whose b2 is equal,
+// e = hits whose b2 and b3 are equal:  34 NW - 22 a - 10 b - 10 c - 8 d - 10 e.  It is not capped (16 misses: 544 bits).
+// ---------------------------------------------------------------------------
+struct CpackCounts { u32 a, b, c, d, e; };
+
+// one word: zzz = its (b0, b1, b2) are 0; hit and, for a hit, x = (b2, b3) of the word XOR those of the deciding entry
+__device__ __forceinline__ void cpack_count(u32 v, bool zzz, bool hit, u32 x, CpackCounts &n)
+{
+  n.a += zzz ? 1u : 0u;
+  n.b += v == 0u ? 1u : 0u;
+  n.c += hit ? 1u : 0u;
+  n.d += (hit && (x & 0xffu) == 0u) ? 1u : 0u;
+  n.e += (hit && x == 0u) ? 1u : 0u;
+}
+
+// one line: its counts into n (zeroed by the caller), its size in bits returned
+template <int NW>
+__device__ __forceinline__ u32 cpack_line(const u32 (&w)[NW], CpackCounts &n)
+{
+  if constexpr (NW <= 16) {
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+      const u32 key = w[i] & 0xffffu;
+      u32 m = ~w[i];                                   // (no earlier word with this key: the XOR below has a key part)
+#pragma unroll
+      for (int j = i - 1; j >= 0; j--) m = (w[j] & 0xffffu) == key ? w[j] : m;      // ends at the first such word
+      const u32 y = m ^ w[i];
+      const bool zzz = (w[i] & 0xffffffu) == 0u;
+      const bool zero_entry = key == 0u && !zzz;       // decided by a zero entry: MMXX
+      const bool hit = !zzz && (key == 0u || (y & 0xffffu) == 0u);
+      cpack_count(w[i], zzz, hit, zero_entry ? 1u : (y >> 16), n);
+    }
+  } else {
+    // the misses so far as (key | none) and ((b2, b3) | miss number << 16); C = their number
+    u32 dk[NW], pay[NW];
+    u32 C = 0;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+      const u32 key = w[i] & 0xffffu, hi = w[i] >> 16;
+      u32 m = 0xffff0000u;                             // (no miss with this key: a miss number that is never "still there")
+#pragma unroll
+      for (int j = 0; j < i; j++) m = dk[j] == key ? pay[j] : m;                     // ends at the latest such miss
+      const bool zzz = (w[i] & 0xffffffu) == 0u;
+      const bool zero_entry = key == 0u && !zzz && C < 16u;
+      const bool there = C - (m >> 16) <= 16u;         // (unsigned: no miss found gives a huge difference)
+      const bool hit = !zzz && (zero_entry || there);
+      cpack_count(w[i], zzz, hit, zero_entry ? 1u : ((m & 0xffffu) ^ hi), n);
+      const bool miss = !zzz && !hit;
+      dk[i] = miss ? key : 0xffffffffu;
+      pay[i] = hi | (C << 16);
+      C += miss ? 1u : 0u;
+    }
+  }
+  return 34u * NW - 22u * n.a - 10u * n.b - 10u * n.c - 8u * n.d - 10u * n.e;
+}
+// C-Pack's totals of one lane: the nested counts, words, bits
+struct CpackAcc {
+  CpackCounts tot = {0, 0, 0, 0, 0};
+  u32 words = 0;
+  u64 bits = 0;
+
+  // per-lane totals -> the workgroup's pattern counts (CPACKPattern order: ZZZZ ZZZX MMMM MMMX MMXX XXXX) and bits
+  __device__ __forceinline__ void flush(u64 *s_counts)
+  {
+    const CpackCounts &t = tot;
+    const u32 c[6] = {t.b, t.a - t.b, t.e, t.d - t.e, t.c - t.d, words - t.a - t.c};
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+      if (c[k]) atomicAdd(&s_counts[k], (u64)c[k]);
+    if (bits) atomicAdd(&s_counts[6], bits);
+    tot = CpackCounts{0, 0, 0, 0, 0};
+    words = 0;
+    bits = 0;
+  }
+  // one line of nw words: its counts n and its size
+  __device__ __forceinline__ void add(const CpackCounts &n, u32 size, u32 nw, u64 *s_counts)
+  {
+    tot.a += n.a; tot.b += n.b; tot.c += n.c; tot.d += n.d; tot.e += n.e;
+    words += nw;
+    bits += size;
+    if (words >= (1u << 30)) flush(s_counts);      // far from overflow of the 32-bit totals
   }
 };

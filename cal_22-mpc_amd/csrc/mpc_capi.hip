@@ -45,7 +45,7 @@ namespace {
 thread_local std::string g_create_error;
 
 // The ABI's algorithm numbers (mpc_info.algorithm) and, per algorithm, the facts that do not depend on a handle.
-enum class Algo { VPC, BDI, FPC, BPC, SC2, Pattern };
+enum class Algo { VPC, BDI, FPC, BPC, SC2, Pattern, CPack };
 
 struct AlgoFacts {
   const char *name;                        // in a group's form and error texts
@@ -65,6 +65,8 @@ constexpr AlgoFacts kAlgo[] = {
   {"SC2", "SC2", MPC_SC2_RAW_LEN, 6, 2, MPC_PATH_SC2, 4, 4, MPC_MAX_LINE},
   // 8-, 4- and 2-byte values (Pattern.cpp:26-58): a multiple of 8, or checkPattern reads past the line
   {"PATTERN", "Pattern", MPC_PATTERN_RAW_LEN, 534, 10, MPC_PATH_PATTERN, 8, 8, MPC_MAX_LINE},
+  // C-Pack with a per-line dictionary: 32-bit words (CPACK.cpp:14)
+  {"CPACK", "C-Pack", MPC_CPACK_RAW_LEN, 10, 6, MPC_PATH_CPACK, 4, 4, MPC_MAX_LINE},
 };
 constexpr const AlgoFacts &facts(Algo a) { return kAlgo[(int)a]; }
 const char *algorithm_name(Algo a) { return facts(a).name; }
@@ -348,6 +350,7 @@ int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t 
   switch (h->algorithm) {
   case Algo::SC2: return launch_sc2(h, d_lines, n, d_sizes, d_sel, s);
   case Algo::Pattern: return launch_pattern(h, d_lines, n, d_sizes, d_sel, s);
+  case Algo::CPack: e = mpc_launch_cpack(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
   case Algo::BPC: e = mpc_launch_bpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
   case Algo::FPC: e = mpc_launch_fpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
   case Algo::BDI: e = mpc_launch_bdi(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
@@ -542,6 +545,18 @@ void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<
     vec[3] += h->sc2.warm;
     vec[4] += h->sc2.symbols.size();
     vec[5] += raw[1];
+    return;
+  }
+  case Algo::CPack: {
+    u64 words = 0;
+    for (int i = 0; i < 6; i++) {
+      vec[4 + i] += raw[i];
+      words += raw[i];
+    }
+    vec[0] += words / (u64)(h->L / 4);
+    vec[1] += words * 32ull;
+    vec[2] += raw[6];
+    vec[3] += words;
     return;
   }
   case Algo::BPC: {
@@ -853,6 +868,18 @@ int mpc_create_bdi(unsigned line_size, int device, mpc_handle **out) { return cr
 int mpc_create_fpc(unsigned line_size, int device, mpc_handle **out) { return create_fixed(Algo::FPC, line_size, device, out); }
 int mpc_create_bpc(unsigned line_size, int device, mpc_handle **out) { return create_fixed(Algo::BPC, line_size, device, out); }
 
+int mpc_create_cpack(unsigned line_size, int dictionary_scope, int device, mpc_handle **out)
+{
+  if (!out) return MPC_E_INVAL;
+  *out = nullptr;
+  if (dictionary_scope == MPC_CPACK_DICT_CARRIED)
+    return set_err(nullptr, MPC_E_INVAL, "C-Pack: the reference's dictionary carried from line to line (MPC_CPACK_DICT_CARRIED) is not offered: "
+                                         "it is sequential state and does not shard (DESIGN.md 8); MPC_CPACK_DICT_PER_LINE starts every line from a fresh dictionary");
+  if (dictionary_scope != MPC_CPACK_DICT_PER_LINE)
+    return set_err(nullptr, MPC_E_INVAL, "C-Pack: dictionary_scope " + std::to_string(dictionary_scope) + " is not one of MPC_CPACK_DICT_CARRIED (0), MPC_CPACK_DICT_PER_LINE (1)");
+  return create_fixed(Algo::CPack, line_size, device, out);
+}
+
 int mpc_create_pattern(unsigned line_size, int device, mpc_handle **out)
 {
   int rc = create_fixed(Algo::Pattern, line_size, device, out);
@@ -1032,6 +1059,7 @@ const char *mpc_kernel_form(const mpc_handle *h)
   if (!h) return "";
   if (h->algorithm == Algo::SC2) return h->sc2.built ? "table sizing" : "warm-up counting";
   if (h->algorithm == Algo::Pattern) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled, then the set passes" : "run-time loop, then the set passes";
+  if (h->algorithm == Algo::CPack) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled" : "run-time loop";
   if (h->algorithm != Algo::VPC) return "unrolled";
   if (h->route.kernel == VpcKernel::AtCreation && h->jit.from_cache) return "unrolled, compiled at creation (from the cache)";
   static const char *const form[] = {"unrolled", "unrolled, general layout", "unrolled, compiled at creation", "run-time loop", "generic"};

@@ -100,6 +100,8 @@ static inline uint64_t mpc_vpc_raw_len(int K, int bins) { return 2ull * (uint64_
 #define MPC_FPC_RAW_LEN 9
 /*   BPC: [0,7) Counts (BPCPattern order)  [7] TotalWords  [8] compressed_bits  */
 #define MPC_BPC_RAW_LEN 9
+/*   C-Pack, per-line dictionary: [0,6) Counts (CPACKPattern order)  [6] compressed_bits */
+#define MPC_CPACK_RAW_LEN 7
 
 /* The stateless baselines evaluated by one launch (baselines_kernel, mpc_baselines.hip): per member its optional per-line
  * outputs and its raw statistics.  raw == NULL: the algorithm is not a member of the launch.                      */

@@ -16,6 +16,7 @@
 //   BPC       first word <= 33, 33 planes of <= 32 bits   1089 at any L <= 128; 217 bits at L = 8, more than 8 L: bins are NOT sized by 8 L
 //   SC2       33 bits per word                            2112 at L = 256
 //   Pattern   smallest scan + 4, at most 8 L + 4          2052 at L = 256
+//   C-Pack    34 bits per word (2 prefix + 32)            2176 at L = 256; more than 8 L, like BPC
 //
 // All accumulators are plain uint64 sums (device-scope atomic adds), so shards and ranks add.
 #pragma once

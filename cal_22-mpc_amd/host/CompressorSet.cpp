@@ -16,7 +16,7 @@ CompressorSet::CompressorSet(const std::vector<Compressor *> &members) : m_Membe
   for (size_t i = 0; i < m_Members.size(); i++) {
     mpc_handle *h = m_Members[i] ? m_Members[i]->DeviceHandle() : nullptr;
     if (!h) {
-      printf("CompressorSet: member %zu%s%s is not a GPU evaluator (VPC, BDI, FPC, BPC, SC2, Pattern): it cannot be fed in a set.\n", i,
+      printf("CompressorSet: member %zu%s%s is not a GPU evaluator (VPC, BDI, FPC, BPC, SC2, Pattern, CPACK): it cannot be fed in a set.\n", i,
              m_Members[i] ? " " : "", m_Members[i] ? m_Members[i]->GetCompressorName().c_str() : "");
       exit(1);
     }

@@ -1,5 +1,5 @@
-// DeviceCompressor.h -- ADDITIVE, no counterpart in the reference: what the six GPU evaluators (VPC, BDI, FPC, BPC,
-// SC2, Pattern) share over one libmpc_hip handle (include/mpc_hip.h), size accounting (SizeReport.h) included.  A derived class keeps its constructor (the
+// DeviceCompressor.h -- ADDITIVE, no counterpart in the reference: what the seven GPU evaluators (VPC, BDI, FPC, BPC,
+// SC2, Pattern, CPACK) share over one libmpc_hip handle (include/mpc_hip.h), size accounting (SizeReport.h) included.  A derived class keeps its constructor (the
 // create call, its result object, its name), LoadResult() and whatever the reference's class of that name has of its own.
 #ifndef MPC_HOST_DEVICECOMPRESSOR_H
 #define MPC_HOST_DEVICECOMPRESSOR_H

@@ -48,13 +48,14 @@ typedef struct mpc_handle mpc_handle;
 #define MPC_PATH_BPC          5
 #define MPC_PATH_SC2          6
 #define MPC_PATH_PATTERN      7
+#define MPC_PATH_CPACK        8  /* C-Pack with a per-line dictionary */
 
 typedef struct {
   int32_t abi_version;
-  int32_t algorithm;        /* 0 = VPC, 1 = BDI, 2 = FPC, 3 = BPC, 4 = SC2, 5 = Pattern */
+  int32_t algorithm;        /* 0 = VPC, 1 = BDI, 2 = FPC, 3 = BPC, 4 = SC2, 5 = Pattern, 6 = C-Pack (per-line dictionary) */
   int32_t line_size;        /* bytes per line (L) */
   int32_t num_modules;      /* VPC: M; BDI: 0 */
-  int32_t num_clusters;     /* VPC: M+1 (cluster -1 .. M-1); BDI: 9 states; FPC: 8 prefixes; BPC: 7 patterns; SC2: 2 (warm-up, table); Pattern: 10 states */
+  int32_t num_clusters;     /* VPC: M+1 (cluster -1 .. M-1); BDI: 9 states; FPC: 8 prefixes; BPC: 7 patterns; SC2: 2 (warm-up, table); Pattern: 10 states; C-Pack: 6 patterns */
   int32_t hist_bins;        /* VPC: bins per cluster in the stats vector */
   int32_t kernel_path;      /* MPC_PATH_* */
   int32_t device;           /* HIP device ordinal the handle is bound to */
@@ -129,6 +130,22 @@ int mpc_sc2_table(mpc_handle *h, uint32_t *symbols, uint16_t *lengths, size_t ca
 int mpc_create_pattern(unsigned line_size, int device, mpc_handle **out);
 /* Lines in the handle's set since creation (waits like mpc_sync; not cleared by mpc_stats_reset). */
 int mpc_pattern_distinct_lines(mpc_handle *h, uint64_t *n);
+/* C-Pack (reference CPACK.cpp:7-101) with a PER-LINE dictionary: what `new comp::CPACK(lineSize)` constructed afresh for
+ * every line reports.  NOT the numbers of the reference's `-a CPACK` run: its driver keeps one object, so the 16-entry
+ * FIFO dictionary is carried from line to line (CPACK.h:107-113, CPACK.cpp:86-93); that is sequential state, does not
+ * shard, and is not offered.  A cache decompresses lines independently, and C-Pack as published starts
+ * each line from a fresh dictionary: that is what is evaluated here.
+ * Per line: the dictionary is a FIFO of 16 four-byte entries, all zero.  For each 4-byte word b0 b1 b2 b3 in memory
+ * order: b0 = b1 = b2 = 0 is ZZZZ (2 bits) when b3 = 0 and ZZZX (12) otherwise, without a dictionary access; else the
+ * first entry from the front (the oldest) with the same b0, b1 decides alone -- b2 differs MMXX (24), b3 differs MMMX
+ * (16), all equal MMMM (6) -- and a hit changes nothing; without such an entry the word is XXXX (34), is pushed at the
+ * back and the front entry leaves.  Per-line output: the sum of the word sizes in bits (not capped: 16 misses in a
+ * 64-byte line are 544 bits); `selected` is 0.
+ * dictionary_scope: MPC_CPACK_DICT_PER_LINE; MPC_CPACK_DICT_CARRIED and every other value return MPC_E_INVAL with a
+ * message.  line_size: a multiple of 4 from 4 to 256.  Both are checked before any device is touched.                */
+#define MPC_CPACK_DICT_CARRIED  0
+#define MPC_CPACK_DICT_PER_LINE 1
+int mpc_create_cpack(unsigned line_size, int dictionary_scope, int device, mpc_handle **out);
 void mpc_destroy(mpc_handle *h);
 
 int mpc_get_info(const mpc_handle *h, mpc_info *info);
@@ -190,6 +207,8 @@ int mpc_sync(mpc_handle *h);
  * SC2 layout: [0] lines [1] original_bits [2] compressed_bits [3] warm-up lines [4] table symbols
  *             [5] words found in the table.  mpc_stats_reset clears the statistics only: the table and the
  *             handle's line counter (which line is line S) stay.
+ * C-Pack layout: [0] lines [1] original_bits [2] compressed_bits [3] TotalWords (the sum of the counts) [4..9] Counts in
+ *             CPACKPattern order ZZZZ ZZZX MMMM MMMX MMXX XXXX (CPACK.h:18-26), of 2 12 6 16 24 34 bits.
  * Pattern layout: [0] lines [1] 0 [2] 0 (CompResult::Update is never called: OriginalSize and CompressedSize stay 0)
  *             [3] sum of the returned sizes [4] Z [5] R [6] T [7] U [8] Total, all in bytes [9..14] ImplicitCounts
  *             [15..20] ExplicitCounts [21] lines that joined the set [22..277] SymbolCounts [278..533]
@@ -204,7 +223,7 @@ int mpc_stats_set(mpc_handle *h, const uint64_t *vec, size_t n);   /* = (after a
 /* Device-side exchange (multi-GPU without a host round trip).  The handle's device
  * accumulators ("raw" statistics: VPC [sum_r(K)] [sum_r2(K)] [histogram(K x B)], BDI
  * [Counts(9)] [compressed_bits], FPC [Counts(8)] [compressed_bits], BPC [Counts(7)] [TotalWords] [compressed_bits], SC2
- * [compressed_bits] [words_in_table], Pattern: the 531 sums of csrc/mpc_pattern.h) are plain uint64 sums, so ranks may all-reduce them
+ * [compressed_bits] [words_in_table], Pattern: the 531 sums of csrc/mpc_pattern.h, C-Pack [Counts(6)] [compressed_bits]) are plain uint64 sums, so ranks may all-reduce them
  * directly: mpc_stats_copy_raw_device enqueues an asynchronous device-to-device copy of
  * the raw_len words into d_dst on hip_stream (after everything already enqueued there),
  * and mpc_stats_from_raw turns such an array -- on the host, e.g. after the all-reduce --
@@ -256,8 +275,8 @@ int mpc_gpgpusim_log_line_size(const char *log_path, uint32_t *line_size);
  * on the slot's stream, in member order.  Each member sees every line exactly as if it had been called alone and keeps
  * its own statistics: mpc_stats_get and everything else that takes the member's handle work as before.  BDI, FPC and
  * BPC members of 32-, 64- or 128-byte lines, when at least two of them are in the group, share one kernel that loads a
- * line once and evaluates all of them on it; every other member launches its own kernel (a Pattern member its own kernels: the
- * analysis and the set passes) (mpc_group_form).
+ * line once and evaluates all of them on it; every other member launches its own kernel (a C-Pack member too; a Pattern
+ * member its own kernels: the analysis and the set passes) (mpc_group_form).
  * The group BORROWS the handles: destroy the group before its members.  A member stays usable on its own between group
  * calls.  One group is used from one thread at a time.                                                             */
 typedef struct mpc_group mpc_group;

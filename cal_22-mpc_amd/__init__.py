@@ -25,6 +25,7 @@ LIB_PATH = os.environ.get("MPC_HIP_LIB") or os.path.join(HERE, "libmpc_hip.so") 
 
 MPC_SIZE_BINS = 4096          # bins of a size histogram (include/mpc_hip_sizes.h)
 MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2, MPC_PATH_PATTERN = 1, 2, 3, 4, 5, 6, 7
+MPC_PATH_PATTERN_EVICTING = 9
 MPC_PATH_CPACK = 8
 MPC_CPACK_DICT_CARRIED, MPC_CPACK_DICT_PER_LINE = 0, 1     # mpc_create_cpack's dictionary_scope
 SYNTH_KINDS = {"zeros": 0, "random_u32": 1, "sine_f32": 2, "mixed": 3, "pointers_u64": 4}
@@ -84,6 +85,7 @@ def lib() -> C.CDLL:
             "mpc_sc2_code_lengths": ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
             "mpc_sc2_table": ([H, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
             "mpc_create_pattern": ([C.c_uint, C.c_int, C.POINTER(H)], C.c_int),
+            "mpc_create_pattern_evicting": ([C.c_uint, C.c_uint64, C.c_int, C.POINTER(H)], C.c_int),
             "mpc_pattern_distinct_lines": ([H, C.POINTER(C.c_uint64)], C.c_int),
             "mpc_create_cpack": ([C.c_uint, C.c_int, C.c_int, C.POINTER(H)], C.c_int),
             "mpc_destroy": ([H], None),
@@ -144,7 +146,7 @@ EXPORTED_SYMBOLS = [
     "mpc_synth_fill", "mpc_read_bandwidth_probe",
     "mpc_group_create", "mpc_group_destroy", "mpc_group_last_error", "mpc_group_form", "mpc_group_compress_batch",
     "mpc_group_compress_batch_device", "mpc_group_compress_npy", "mpc_group_compress_gpgpusim_log", "mpc_group_sync",
-    "mpc_create_pattern", "mpc_pattern_distinct_lines", "mpc_create_cpack",
+    "mpc_create_pattern", "mpc_pattern_distinct_lines", "mpc_create_cpack", "mpc_create_pattern_evicting",
 ]
 # The SC2 entry points of include/mpc_hip.h.  Kept apart from EXPORTED_SYMBOLS, which lists the names of the
 # header's lowercase-letter form (mpc_[a-z_]+) only; every one of both lists is exported by libmpc_hip.so.
@@ -437,18 +439,34 @@ def pattern_result_from_vector(v: np.ndarray) -> Dict:
 class Pattern(_Evaluator):
     """``comp::Pattern(lineSize)`` (reference ``Pattern.h:228-252``): zero / repeated / already-seen / base-delta bytes and
     the byte entropy of a trace.  Per-line ``selected`` is the ``PatternState`` (0..5, 9 = NotDefined).  The set of
-    lines seen lives on the device and holds up to 2**24 - 1 distinct lines (the reference evicts beyond that; this
-    raises ``MpcError`` instead).  One object per trace and per GPU."""
+    lines seen lives on the device.  One object per trace and per GPU.
 
-    def __init__(self, line_size: int, device: int = 0):
-        super().__init__("mpc_create_pattern", line_size, device)
+    ``on_full="refuse"`` (the default): the set holds up to 2**24 - 1 distinct lines; the reference evicts beyond that,
+    this raises ``MpcError`` instead.  ``on_full="evict"``: the reference's eviction (a FIFO over insertions, see
+    ``mpc_create_pattern_evicting`` in ``include/mpc_hip.h``) with ``capacity`` lines, ``None`` for the reference's
+    2**24 - 1; it takes any trace, and beyond the capacity its numbers depend on the order of the lines.  Below the
+    capacity both give the same numbers."""
+
+    def __init__(self, line_size: int, device: int = 0, on_full: str = "refuse", capacity: Optional[int] = None):
+        if on_full not in ("refuse", "evict"):
+            raise ValueError(f"on_full is 'refuse' or 'evict', not {on_full!r}")
+        if on_full == "refuse" and capacity is not None:
+            raise ValueError("capacity is the evicting set's: on_full='evict'")
+        self.on_full = on_full
+        if on_full == "evict":
+            if capacity is not None and (int(capacity) != capacity or capacity < 1):
+                raise ValueError("capacity is None or an integer from 1 to 2**24 - 1")
+            super().__init__("mpc_create_pattern_evicting", line_size, 0 if capacity is None else int(capacity), device)
+        else:
+            super().__init__("mpc_create_pattern", line_size, device)
 
     def result(self) -> Dict:
         """The counts of ``PatternResult`` and both entropies (the reference computes them in ``Print``)."""
         return pattern_result_from_vector(self.stats_vector())
 
     def distinct_lines(self) -> int:
-        """Lines in the set since creation (``reset()`` keeps the set)."""
+        """Lines that joined the set since creation: the distinct lines, or with ``on_full="evict"`` the insertions
+        (``reset()`` keeps the set)."""
         n = C.c_uint64()
         self._check(lib().mpc_pattern_distinct_lines(self._h, C.byref(n)))
         return int(n.value)

@@ -49,6 +49,7 @@ def lib_units(csrc: str = CSRC):
               (os.path.join(csrc, "mpc_baselines.hip"), "baselines.o", []),      # the group's shared kernel
               (os.path.join(csrc, "mpc_sc2.hip"), "sc2.o", []),
               (os.path.join(csrc, "mpc_pattern.hip"), "pattern.o", []),
+              (os.path.join(csrc, "mpc_pattern_evict.hip"), "pattern_evict.o", []),   # the Pattern analyser's evicting set
               (os.path.join(csrc, "mpc_cpack.hip"), "cpack.o", []),              # C-Pack with a per-line dictionary
               (os.path.join(csrc, "mpc_sizes.hip"), "sizes.o", []),              # size histograms and best-of
               (os.path.join(csrc, "mpc_capi.hip"), "capi.o", [])]

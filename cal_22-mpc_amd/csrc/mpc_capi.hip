@@ -115,6 +115,8 @@ struct mpc_handle {
     hipEvent_t done = nullptr;
     bool recorded = false;
     bool over = false;           // a line beyond the capacity arrived: the handle takes no more lines
+    bool evicting = false;       // mpc_create_pattern_evicting: `evict` is the set, `set` is unused
+    MpcEvictSet evict{};
   } pat;
   std::vector<Stager *> fed_by;  // every stager that feeds this handle: its own, then those of the groups it is a member of (sc2_build)
   // size accounting (mpc_sizes.h): nothing of it exists before mpc_size_hist_enable
@@ -488,7 +490,14 @@ int launch_pattern(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes,
     if (e != hipSuccess) return failed(e);
   }
   if (h->pat.recorded) HIPCHK(h, hipStreamWaitEvent(s, h->pat.done, 0));
-  for (u64 at = 0; at < n; at += MPC_PATTERN_CHUNK) {
+  // the evicting set: launches of at most min(capacity, MPC_PATTERN_CHUNK) lines, in trace order
+  for (u64 at = 0; h->pat.evicting && at < n; at += h->pat.evict.launch_max) {
+    const u64 take = std::min<u64>(n - at, h->pat.evict.launch_max);
+    const hipError_t e = mpc_launch_pattern_evict(base + at * (u64)h->L, (uint32_t)take, h->L, &h->pat.evict, h->d_raw, grid_for(h, take, 256, 8),
+                                                  grid_for(h, (u64)h->pat.evict.slot_mask + 1, 256, 8), s);
+    if (e != hipSuccess) return failed(e);
+  }
+  for (u64 at = 0; !h->pat.evicting && at < n; at += MPC_PATTERN_CHUNK) {
     const u64 take = std::min<u64>(n - at, MPC_PATTERN_CHUNK);
     HIPCHK(h, hipMemsetAsync(h->pat.set.ctl + MPC_PSET_PENDING_A, 0, 2 * sizeof(u64), s));
     const hipError_t e = mpc_launch_pattern_set(base + at * (u64)h->L, (uint32_t)take, h->L, &h->pat.set, h->d_raw, grid_for(h, take, 256, 8), s);
@@ -503,6 +512,11 @@ int launch_pattern(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes,
 int pattern_status(mpc_handle *h)
 {
   if (h->algorithm != Algo::Pattern) return MPC_OK;
+  if (h->pat.evicting) {       // nothing to run into: the flag says that a probe went round a whole table, which its sizing excludes
+    u64 flag = 0;
+    HIPCHK(h, hipMemcpy(&flag, h->pat.evict.ctl + MPC_ESET_OVERFLOW, sizeof(flag), hipMemcpyDeviceToHost));
+    return flag ? set_err(h, MPC_E_HIP, "Pattern: the evicting set's table is full (internal error)") : MPC_OK;
+  }
   if (!h->pat.over) {
     u64 ctl[2] = {0, 0};
     HIPCHK(h, hipMemcpy(ctl, h->pat.set.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
@@ -911,6 +925,66 @@ int mpc_create_pattern(unsigned line_size, int device, mpc_handle **out)
   return MPC_OK;
 }
 
+int mpc_create_pattern_evicting(unsigned line_size, uint64_t capacity, int device, mpc_handle **out)
+{
+  if (!out) return MPC_E_INVAL;
+  *out = nullptr;
+  // (the refusals before a device is touched: the line size, then the capacity)
+  int rc = check_line_size(Algo::Pattern, line_size);
+  if (rc != MPC_OK) return rc;
+  if (capacity > MPC_PATTERN_CAPACITY)
+    return set_err(nullptr, MPC_E_INVAL, "Pattern: a capacity of " + std::to_string(capacity) + " lines is more than the reference's 16777215 (2^24 - 1); 0 stands for that");
+  rc = create_fixed(Algo::Pattern, line_size, device, out);
+  if (rc != MPC_OK) return rc;
+  mpc_handle *h = *out;
+  h->pat.evicting = true;
+  MpcEvictSet &S = h->pat.evict;
+  S.capacity = capacity ? capacity : MPC_PATTERN_CAPACITY;
+  S.launch_max = (uint32_t)std::min<u64>(S.capacity, MPC_PATTERN_CHUNK);
+  // the newer table holds at most C lines brought along and C - 1 + launch_max insertions (mpc_pattern.h)
+  u64 slots = 8;
+  while (2 * slots < 3 * (2 * S.capacity + S.launch_max)) slots <<= 1;
+  S.slot_mask = (uint32_t)(slots - 1);
+  S.tag_mask = ~0ull;
+#if MPC_TESTING
+  if (const char *e = getenv("MPC_TEST_PATTERN_TAG_BITS")) {      // as mpc_create_pattern
+    const long bits = atol(e);
+    if (bits >= 1 && bits < 64) S.tag_mask = (1ull << bits) - 1ull;
+  }
+#endif
+  const size_t m = S.launch_max, blocks = (m + 255) / 256;
+  bool ok = true;
+  auto take = [&](auto **p, size_t bytes, int fill) {      // fill < 0: left as it comes
+    ok = ok && hipMalloc((void **)p, bytes) == hipSuccess && (fill < 0 || hipMemset(*p, fill, bytes) == hipSuccess);
+  };
+  for (MpcEvictTable &T : S.tab) {
+    take(&T.tags, slots * sizeof(u64), 0);
+    take(&T.stamps, slots * sizeof(u64), 0xff);
+    take(&T.first, slots * sizeof(u64), 0xff);        // (above every key a launch writes)
+    take(&T.store, slots * (size_t)line_size, -1);
+  }
+  take(&S.ctl, MPC_ESET_WORDS * sizeof(u64), 0);
+  take(&S.pend_a, m * sizeof(uint2), 0);
+  take(&S.pend_b, m * sizeof(uint2), 0);
+  take(&S.ent, m * sizeof(uint32_t), 0);
+  take(&S.gone_before, m * sizeof(uint32_t), 0);
+  take(&S.risk_before, m * sizeof(uint32_t), 0);
+  take(&S.risk, m * sizeof(uint32_t), 0);
+  take(&S.risk_missed, (m + 1) * sizeof(uint32_t), 0);
+  take(&S.kind, m, 0);
+  take(&S.block_sums, blocks * sizeof(uint2), 0);
+  if (!ok) {
+    g_create_error = "hipMalloc of the evicting Pattern line set (" + std::to_string(2 * slots * (3 * sizeof(u64) + line_size)) + " bytes) failed";
+    return create_failed(MPC_E_NOMEM, out);
+  }
+  if (hipDeviceSynchronize() != hipSuccess ||          // (the kernels run on non-blocking streams)
+      hipEventCreateWithFlags(&h->pat.done, hipEventDisableTiming) != hipSuccess) {
+    g_create_error = "initialising the evicting Pattern line set failed";
+    return create_failed(MPC_E_NODEVICE, out);
+  }
+  return MPC_OK;
+}
+
 int mpc_pattern_distinct_lines(mpc_handle *h, uint64_t *n)
 {
   if (!h || !n || h->algorithm != Algo::Pattern) return MPC_E_INVAL;
@@ -921,7 +995,7 @@ int mpc_pattern_distinct_lines(mpc_handle *h, uint64_t *n)
   rc = pattern_status(h);
   if (rc != MPC_OK) return rc;
   u64 v = 0;
-  HIPCHK(h, hipMemcpy(&v, h->pat.set.ctl + MPC_PSET_DISTINCT, sizeof(v), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(&v, h->pat.evicting ? h->pat.evict.ctl + MPC_ESET_INSERTIONS : h->pat.set.ctl + MPC_PSET_DISTINCT, sizeof(v), hipMemcpyDeviceToHost));
   *n = v;
   return MPC_OK;
 }
@@ -1004,6 +1078,15 @@ void mpc_destroy(mpc_handle *h)
   if (h->pat.set.ctl) (void)hipFree(h->pat.set.ctl);
   if (h->pat.set.pend_a) (void)hipFree(h->pat.set.pend_a);
   if (h->pat.set.pend_b) (void)hipFree(h->pat.set.pend_b);
+  {
+    const MpcEvictSet &E = h->pat.evict;
+    for (const MpcEvictTable &T : E.tab)
+      for (void *p : {(void *)T.tags, (void *)T.stamps, (void *)T.first, (void *)T.store})
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)E.ctl, (void *)E.pend_a, (void *)E.pend_b, (void *)E.ent, (void *)E.gone_before, (void *)E.risk_before, (void *)E.risk,
+                    (void *)E.risk_missed, (void *)E.kind, (void *)E.block_sums})
+      if (p) (void)hipFree(p);
+  }
   if (h->pat.done) (void)hipEventDestroy(h->pat.done);
   if (h->acct.d_hist) (void)hipFree(h->acct.d_hist);
   if (h->acct.d_scratch) (void)hipFree(h->acct.d_scratch);
@@ -1021,7 +1104,7 @@ int mpc_get_info(const mpc_handle *h, mpc_info *info)
   info->num_modules = vpc ? h->cfg.M : 0;
   info->num_clusters = vpc ? h->cfg.M + 1 : facts(h->algorithm).clusters;
   info->hist_bins = vpc ? h->cfg.hist_bins : 0;
-  info->kernel_path = vpc && h->route.kernel == VpcKernel::Generic ? MPC_PATH_VPC_GENERIC : facts(h->algorithm).path;
+  info->kernel_path = vpc && h->route.kernel == VpcKernel::Generic ? MPC_PATH_VPC_GENERIC : h->pat.evicting ? MPC_PATH_PATTERN_EVICTING : facts(h->algorithm).path;
   info->device = h->device;
   info->stats_len = h->stats_len;
   return MPC_OK;
@@ -1058,6 +1141,8 @@ const char *mpc_kernel_form(const mpc_handle *h)
 {
   if (!h) return "";
   if (h->algorithm == Algo::SC2) return h->sc2.built ? "table sizing" : "warm-up counting";
+  if (h->algorithm == Algo::Pattern && h->pat.evicting)
+    return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled, then the evicting set passes" : "run-time loop, then the evicting set passes";
   if (h->algorithm == Algo::Pattern) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled, then the set passes" : "run-time loop, then the set passes";
   if (h->algorithm == Algo::CPack) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled" : "run-time loop";
   if (h->algorithm != Algo::VPC) return "unrolled";

@@ -2,7 +2,7 @@
 //
 // The launchers have C linkage, so a declaration that drifted from its definition would still link and then misbehave.
 // This header is therefore included by the callers (mpc_capi.hip, mpc_jit.h) AND by the units that define the
-// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_cpack.hip, mpc_sizes.hip, the host section of mpc_vpc_lane.hip):
+// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_sizes.hip, the host section of mpc_vpc_lane.hip):
 // the compiler sees declaration and definition together and refuses a mismatch.  Host code only -- the run-time
 // compiled source of mpc_jit.h (-DMPC_LANE_JIT) never sees it, and it is not one of the files that key the code
 // object cache.
@@ -17,6 +17,7 @@ struct MpcVpcParams;
 struct MpcBaselinesArgs;
 struct MpcSc2Table;
 struct MpcPatternSet;
+struct MpcEvictSet;
 struct MpcSizesArgs;
 
 extern "C" {
@@ -68,6 +69,10 @@ hipError_t mpc_launch_pattern(const void *d_lines, unsigned long long n_lines, i
                               unsigned long long *d_stats, int grid, hipStream_t stream);
 hipError_t mpc_launch_pattern_set(const void *d_lines, uint32_t n_lines, int L, const MpcPatternSet *S, unsigned long long *d_stats,
                                   int compare_grid, hipStream_t stream);
+
+// mpc_pattern_evict.hip
+hipError_t mpc_launch_pattern_evict(const void *d_lines, uint32_t n_lines, int L, const MpcEvictSet *S, unsigned long long *d_stats,
+                                    int compare_grid, int clear_grid, hipStream_t stream);
 
 // mpc_cpack.hip
 hipError_t mpc_launch_cpack(const void *d_lines, unsigned long long n_lines, int L, uint16_t *d_sizes, int8_t *d_sel, unsigned long long *d_stats,

@@ -68,6 +68,18 @@ Pattern::Pattern(unsigned lineSize) : DeviceCompressor("Pattern", lineSize)
   m_Stat->CompressorName = "Pattern Checker";
 }
 
+Pattern::Pattern(unsigned lineSize, PatternOnFull onFull, unsigned long long capacity) : DeviceCompressor("Pattern", lineSize)
+{
+  if (onFull == PatternOnFull::Evict) {
+    CheckCreated(mpc_create_pattern_evicting(lineSize, capacity, -1, &m_Handle));
+  } else {
+    if (capacity != 0 || onFull != PatternOnFull::Refuse) fail("Pattern: a capacity belongs to PatternOnFull::Evict, and there is no third mode", MPC_E_INVAL, "");
+    CheckCreated(mpc_create_pattern(lineSize, -1, &m_Handle));
+  }
+  m_Stat = new PatternResult(lineSize);
+  m_Stat->CompressorName = "Pattern Checker";
+}
+
 unsigned long long Pattern::DistinctLines()
 {
   FlushLines();

@@ -2,7 +2,8 @@
 // zero / repeated / already-seen / base-delta bytes and the byte entropy of a trace; evaluation on the MI355X via
 // libmpc_hip.so (mpc_create_pattern).  The counts come from the device, the two entropies are computed here from the
 // count maps, as the reference's Print does.  The reference's public m_DataCache member (its LRU of lines) has no
-// counterpart: the set of lines lives in device memory (DistinctLines() is its size).
+// counterpart: the set of lines lives in device memory (DistinctLines() is its size).  ADDITIVE: PatternOnFull::Evict
+// models the reference's eviction beyond 2^24 - 1 lines (mpc_create_pattern_evicting); the default refuses such a trace.
 #ifndef MPC_HOST_PATTERN_H
 #define MPC_HOST_PATTERN_H
 
@@ -36,11 +37,18 @@ struct PatternResult : public CompResult {
   uint64_t Total;
 };
 
+// What the set of lines does when the 2^24-th distinct line arrives: stop with an error (the default), or evict as the
+// reference's cache does -- a FIFO over insertions (include/mpc_hip.h: mpc_create_pattern_evicting).
+enum class PatternOnFull { Refuse = 0, Evict = 1 };
+
 class Pattern : public DeviceCompressor
 {
 public:
   Pattern(unsigned lineSize);
-  // lines in the set (at most 2^24 - 1: the reference evicts beyond that, this evaluator stops with an error)
+  // ADDITIVE.  capacity (Evict only): 0 for the reference's 2^24 - 1, or 1 .. 2^24 - 1 lines
+  Pattern(unsigned lineSize, PatternOnFull onFull, unsigned long long capacity = 0);
+  // lines that joined the set.  Refuse: its distinct lines (at most 2^24 - 1: the reference evicts beyond that, this evaluator
+  // stops with an error).  Evict: its insertions (a line that was evicted and comes back is inserted again)
   unsigned long long DistinctLines();
 
 protected:

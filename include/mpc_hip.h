@@ -49,6 +49,7 @@ typedef struct mpc_handle mpc_handle;
 #define MPC_PATH_SC2          6
 #define MPC_PATH_PATTERN      7
 #define MPC_PATH_CPACK        8  /* C-Pack with a per-line dictionary */
+#define MPC_PATH_PATTERN_EVICTING 9  /* mpc_create_pattern_evicting: the analysis kernel of MPC_PATH_PATTERN, then the evicting set's passes */
 
 typedef struct {
   int32_t abi_version;
@@ -123,12 +124,27 @@ int mpc_sc2_table(mpc_handle *h, uint32_t *symbols, uint16_t *lengths, size_t ca
  * line_size: a multiple of 8 from 8 to 256 (the reference reads past the line otherwise); checked before any device is
  * touched.  The set lives in device memory, sized at creation: (8 + line_size) x 2^25 bytes (2.25 GiB for 64-byte
  * lines) plus 64 MiB of work lists.
- * LIMIT the reference does not have: its LRU starts evicting when the 2^24-th distinct line arrives, and eviction is
- * not modelled.  A handle takes 2^24 - 1 distinct lines.  The call that brings one more fails with MPC_E_INVAL (a call
+ * LIMIT the reference does not have: its LRU starts evicting when the 2^24-th distinct line arrives, and this handle
+ * does not model eviction (mpc_create_pattern_evicting does).  A handle takes 2^24 - 1 distinct lines.  The call that brings one more fails with MPC_E_INVAL (a call
  * that does not wait for its lines, mpc_compress_batch_device, reports it at the next mpc_sync / mpc_stats_get); from
  * then on the handle refuses lines and mpc_stats_get returns the same error.  A new trace needs a new handle.        */
 int mpc_create_pattern(unsigned line_size, int device, mpc_handle **out);
-/* Lines in the handle's set since creation (waits like mpc_sync; not cleared by mpc_stats_reset). */
+/* The same analyser with the reference's eviction (opt-in; mpc_create_pattern is unchanged and keeps refusing).  The
+ * reference's cache is only ever asked exist() and, on a miss, put() (Pattern.cpp:109-116; LRU.h), so a hit reorders nothing
+ * and it is a FIFO over insertions: a line existed before iff an equal line was inserted earlier and the stamp s of its
+ * latest insertion (the number of insertions before it) satisfies s >= I - capacity, I the insertions so far: it is one
+ * of the last `capacity` insertions.  A line that did not exist is inserted.  Beyond the capacity the
+ * result depends on the order of the lines: a handle's calls are evaluated in the order they are made, on whichever streams.
+ * capacity: 0 stands for the reference's 2^24 - 1; 1 .. 2^24 - 1 sizes the set for that capacity (small capacities
+ * allocate little); anything larger is refused, like a bad line_size, before a device is touched.
+ * Memory: two tables of S slots, S the smallest power of two >= 1.5 x (2 capacity + min(capacity, 2^22)), of
+ * (24 + line_size) bytes per slot, plus 37 bytes per line of a launch: 2 x 2^26 x (24 + line_size) bytes at the
+ * reference's capacity (4 GiB for 8-byte lines, 11 GiB for 64-byte lines).  It does not grow with the trace.
+ * Statistics: the Pattern layout, [21] = insertions (every miss inserts), T = L x ([0] - [21]).  Below the capacity every
+ * number equals mpc_create_pattern's.  mpc_get_info reports MPC_PATH_PATTERN_EVICTING.                              */
+int mpc_create_pattern_evicting(unsigned line_size, uint64_t capacity, int device, mpc_handle **out);
+/* Lines that joined the handle's set since creation: its distinct lines, or for an evicting handle its insertions (a line
+ * that was evicted and comes back is inserted again).  Waits like mpc_sync; not cleared by mpc_stats_reset. */
 int mpc_pattern_distinct_lines(mpc_handle *h, uint64_t *n);
 /* C-Pack (reference CPACK.cpp:7-101) with a PER-LINE dictionary: what `new comp::CPACK(lineSize)` constructed afresh for
  * every line reports.  NOT the numbers of the reference's `-a CPACK` run: its driver keeps one object, so the 16-entry
@@ -211,7 +227,7 @@ int mpc_sync(mpc_handle *h);
  *             CPACKPattern order ZZZZ ZZZX MMMM MMMX MMXX XXXX (CPACK.h:18-26), of 2 12 6 16 24 34 bits.
  * Pattern layout: [0] lines [1] 0 [2] 0 (CompResult::Update is never called: OriginalSize and CompressedSize stay 0)
  *             [3] sum of the returned sizes [4] Z [5] R [6] T [7] U [8] Total, all in bytes [9..14] ImplicitCounts
- *             [15..20] ExplicitCounts [21] lines that joined the set [22..277] SymbolCounts [278..533]
+ *             [15..20] ExplicitCounts [21] lines that joined the set (an evicting handle: insertions) [22..277] SymbolCounts [278..533]
  *             SymbolCountsExceptAllZerosAllWordSame.  T = L x ([0] - [21]).  mpc_stats_reset clears the statistics,
  *             [21] included, and keeps the set: lines seen before the reset still count as seen.
  */

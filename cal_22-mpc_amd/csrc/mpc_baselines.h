@@ -411,11 +411,15 @@ __device__ __forceinline__ void bdi_line(const u32 (&w)[NW], bool active, bool r
 }
 
 constexpr u32 kBdiQueue = 384;      // deferred lines per wave (LDS)
+// A launch of more lines than this defers nothing: a queue entry is a 32-bit line index.  The test library draws the
+// limit at 2^20 - 1 lines, so that a launch of a few MiB runs bdi_line's inline scans (tests/test_launch_splits_gpu.py).
+constexpr u64 kBdiDeferMaxLines = MPC_TESTING ? 0xfffffull : 0xffffffffull;
 
 // BDI's state of one lane beyond the line at hand: the run of equal results it has not counted yet, and its wave's
 // queue of deferred lines.  sizes / sel: the handle's per-line outputs (or null); counts: the workgroup's raw
-// statistics (LDS); queue: kBdiQueue entries of LDS per wave; routes: the test library's route counters, a feature of
-// a single handle's kernel (null in the group's; the product build has no such code: MPC_TESTING is 0).
+// statistics (LDS); queue: kBdiQueue entries of LDS per wave; routes: the test library's route counters, which sit
+// behind the handle's raw statistics for bdi_kernel and for the group's BDI member alike (never read in the product
+// build, which has no such code: MPC_TESTING is 0).
 struct BdiLane {
   uint16_t *sizes;
   int8_t *sel;

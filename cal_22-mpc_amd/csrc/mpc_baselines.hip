@@ -36,8 +36,9 @@ baselines_kernel(const uint4 *__restrict__ lines, u64 n_lines, MpcBaselinesArgs 
   __syncthreads();
   const u32 lane = threadIdx.x & 63u;
   const u32 wave = uni(threadIdx.x >> 6);
-  BdiLane bdi = {A.bdi.sizes, A.bdi.sel, s_bdi, s_queue[DEFER ? wave : 0u], nullptr};
-  const bool can_defer = n_lines <= 0xffffffffull;      // queue entries are 32-bit line indices
+  // (test library: the BDI member's route counters sit behind its raw statistics, as for bdi_kernel)
+  BdiLane bdi = {A.bdi.sizes, A.bdi.sel, s_bdi, s_queue[DEFER ? wave : 0u], (MPC_TESTING && BDI) ? A.bdi.raw + MPC_BDI_RAW_LEN : nullptr};
+  const bool can_defer = n_lines <= kBdiDeferMaxLines;      // queue entries are 32-bit line indices
   FpcAcc fpc;
   BpcAcc bpc;
   // every member on one line held in w (every lane stays in: bdi_line votes across the wave)

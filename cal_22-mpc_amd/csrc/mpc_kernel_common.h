@@ -4,6 +4,7 @@
 #ifndef __HIPCC_RTC__      /* (hiprtc, mpc_jit.h: the runtime's declarations and the fixed-width types are built in) */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #endif
 
 #include "mpc_device.h"
@@ -42,6 +43,41 @@ __device__ __forceinline__ void route_add(u64 *routes, int which, u32 v)
   (void)routes; (void)which; (void)v;
 #endif
 }
+
+// How many lines (or per-line sizes) a launcher hands one kernel launch before it cuts the batch: product_value, the
+// limit that keeps the kernel's 32-bit quantities in range.  Test library only: the MPC_TEST_LAUNCH_LINES environment
+// variable (a positive multiple of 64, read once per process) takes its place, so that a batch of a few MiB takes the
+// cuts that the product takes at 2^30 lines and 2^31 sizes (tests/test_launch_splits_gpu.py).
+#ifndef __HIPCC_RTC__
+static inline u64 mpc_launch_cap(u64 product_value)
+{
+#if MPC_TESTING
+  static const u64 test_cap = []() {
+    const char *e = getenv("MPC_TEST_LAUNCH_LINES");
+    const u64 v = e ? strtoull(e, nullptr, 10) : 0ull;
+    return (v > 0 && v % 64u == 0) ? v : 0ull;
+  }();
+  if (test_cap) return test_cap;
+#endif
+  return product_value;
+}
+// Test library only: the launches that the launchers which cut a batch have made in this process, one per piece
+// (mpc_test_launches() reads it), so that a test of a cut can say that the cut was taken.  The counter is one object for
+// all units of the library (an inline function's static).  Nothing in the product.
+#if MPC_TESTING
+inline u64 &mpc_test_launch_counter()
+{
+  static u64 n = 0;
+  return n;
+}
+#endif
+static inline void mpc_count_launch()
+{
+#if MPC_TESTING
+  __atomic_fetch_add(&mpc_test_launch_counter(), 1ull, __ATOMIC_RELAXED);
+#endif
+}
+#endif
 
 #define H80 0x80808080u
 #define L7F 0x7f7f7f7fu

@@ -215,7 +215,7 @@ bdi_kernel(const uint4 *__restrict__ lines, u64 n_lines, uint16_t *__restrict__ 
   const u32 lane = threadIdx.x & 63u;
   const u32 wave = uni(threadIdx.x >> 6);
   BdiLane bdi = {sizes_out, sel_out, s_counts, s_queue[wave], gstats + MPC_BDI_RAW_LEN};      // (route counters behind the statistics)
-  const bool can_defer = n_lines <= 0xffffffffull;      // queue entries are 32-bit line indices
+  const bool can_defer = n_lines <= kBdiDeferMaxLines;      // queue entries are 32-bit line indices
   ring_feed<NW>(lines, n_lines, s_ring, lane, wave, bdi.qn, [&](const u32 (&w)[NW], u64 line, bool active) __attribute__((always_inline)) {
     bdi.group<NW, (NW <= 16)>(lines, lane, w, line, active, can_defer);     // (128-byte lines: deferral measured slower)
   });

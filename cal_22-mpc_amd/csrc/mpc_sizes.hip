@@ -185,11 +185,12 @@ extern "C" hipError_t mpc_launch_sizes(const MpcSizesArgs *A, u64 n_lines, int g
   if (n_hist == 0 || n_lines == 0) return hipSuccess;
   int vec = 1;
   for (int i = 0; i < A->m; i++) vec &= (reinterpret_cast<uintptr_t>(A->sizes[i]) & 15u) == 0 ? 1 : 0;
-  constexpr u64 kMaxLines = 1ull << 31;     // per launch: a uint32 LDS bin cannot wrap (and a piece's first line keeps the alignment)
+  const u64 kMaxLines = mpc_launch_cap(1ull << 31);     // per launch: a uint32 LDS bin cannot wrap (and a piece's first line keeps the alignment)
   for (u64 at = 0; at < n_lines; at += kMaxLines) {
     const u64 take = n_lines - at < kMaxLines ? n_lines - at : kMaxLines;
     MpcSizesArgs P = *A;
     for (int i = 0; i < A->m; i++) P.sizes[i] = A->sizes[i] + at;
+    mpc_count_launch();
     const u64 chunks = (take + 7) / 8;
     const u64 need = (chunks + kSizesThreads - 1) / kSizesThreads;
     const int g = (int)(need < (u64)(grid < 1 ? 1 : grid) ? need : (u64)(grid < 1 ? 1 : grid));
@@ -208,3 +209,10 @@ extern "C" hipError_t mpc_launch_sizes(const MpcSizesArgs *A, u64 n_lines, int g
   }
   return hipSuccess;
 }
+
+#if MPC_TESTING
+// test library only (not part of include/mpc_hip.h): the kernel launches that mpc_launch_vpc_lane,
+// mpc_launch_vpc_lane_jit and mpc_launch_sizes have made in this process, one per piece of a batch
+// (mpc_kernel_common.h: mpc_count_launch)
+extern "C" unsigned long long mpc_test_launches(void) { return __atomic_load_n(&mpc_test_launch_counter(), __ATOMIC_RELAXED); }
+#endif

@@ -1709,13 +1709,14 @@ extern "C" hipError_t mpc_launch_vpc_lane_jit(hipFunction_t fn_stats, hipFunctio
   unsigned ring_cfg = 0;
   int wpb = 0;
   if (mpc_vpc_lane_ring_plan(P, &ring_cfg, &wpb) == 0) return hipErrorInvalidConfiguration;
-  const u64 max_lines = 1ull << 30;     // 32-bit line indices inside the kernel
+  const u64 max_lines = mpc_launch_cap(1ull << 30);     // 32-bit line indices inside the kernel
   hipFunction_t fn = (d_sizes || d_sel) ? fn_lines : fn_stats;
   for (u64 done = 0; done < n_lines; done += max_lines) {
     const u64 take = (n_lines - done) < max_lines ? (n_lines - done) : max_lines;
     const uint4 *l = static_cast<const uint4 *>(d_lines) + done * (u64)(P->L / 16);
     u32 n32 = (u32)take;
     u64 first_line = done;
+    mpc_count_launch();
     const u64 want = (take / 64u + (u64)wpb - 1u) / (u64)wpb;
     const u64 cap = (u64)grid / (wpb > 8 ? 16u : 8u);
     int wgrid = (int)(want < cap ? want : cap);
@@ -1762,7 +1763,7 @@ extern "C" hipError_t MPC_LAUNCH_NAME(const void *d_lines, u64 n_lines, const Mp
                                       int8_t *d_sel, u64 *d_stats, int grid, hipStream_t stream)
 {
   if (!lane_has_line_size(P->L)) return hipErrorInvalidValue;
-  const u64 max_lines = 1ull << 30;     // 32-bit line indices inside the kernel
+  const u64 max_lines = mpc_launch_cap(1ull << 30);     // 32-bit line indices inside the kernel
   // a sequence whose rings do not fit the LDS beside its histogram runs the run-time module loop
   const int wpb = lane_wpb_of(P->L);
   const bool rings_fit = lane_lds_plan(P, wpb, P->L <= 64).stages != 0;
@@ -1771,7 +1772,8 @@ extern "C" hipError_t MPC_LAUNCH_NAME(const void *d_lines, u64 n_lines, const Mp
     const uint4 *l = static_cast<const uint4 *>(d_lines) + done * (u64)(P->L / 16);
     hipError_t e = hipErrorInvalidValue;
     bool launched = false;
-#define X(...)                                                                                                     \
+    mpc_count_launch();
+#define X(...)                                                                                                    \
     if (!launched && rings_fit && lane_seq_matches<__VA_ARGS__>(P)) {                                              \
       e = lane_launch<__VA_ARGS__>(l, (u32)take, done, P, d_sizes, d_sel, d_stats, grid, stream);                  \
       launched = true;                                                                                             \

@@ -8,6 +8,10 @@ import pytest
 
 from conftest import pkg
 
+# fresh processes bound to the test library (shared with test_launch_splits_gpu.py; test_device_footprint_gpu.py takes
+# _run_with_test_library from here)
+from testlib_child import ROUTE_NAMES, ROUTES_PRELUDE, _run_with_test_library  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 
@@ -1093,45 +1097,6 @@ def test_bench_plain_run_dumps_last_step_statistics(oracle, configs, traces, tmp
     o = oracle.VpcOracle(configs.probe_config(64))
     o.compress(traces.random_u32(n, 64))
     assert (got == o.stats_vector().astype(np.float64)).all()
-
-
-ROUTE_NAMES = ["vpc_deferred", "vpc_drains", "vpc_paired_blocks", "vpc_plain_blocks", "vpc_to_paired", "vpc_to_plain",
-               "vpc_tail_groups", "bdi_deferred", "bdi_drains"]        # MPC_RT_* of csrc/mpc_kernel_common.h
-
-ROUTES_PRELUDE = r"""
-import ctypes, importlib, json, sys
-import numpy as np
-sys.path.insert(0, %r)
-mpc = importlib.import_module("cal_22-mpc_amd"); C = importlib.import_module("cal_22-mpc_amd.configs"); T = importlib.import_module("cal_22-mpc_amd.traces")
-from oracle import oracle as O
-assert mpc.LIB_PATH.endswith("libmpc_hip_test.so"), mpc.LIB_PATH
-def routes(ev):
-    # test library only: how often the kernels' alternative routes ran since the statistics were last reset
-    f = mpc.lib().mpc_test_routes
-    f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int
-    out = (ctypes.c_uint64 * 16)()
-    assert f(ev._h, out, 16) == 0
-    return dict(zip(%r, [int(x) for x in out]))
-"""
-
-
-def _run_with_test_library(code: str, grid_cap: int, timeout: int = 900):
-    """A fresh process bound to libmpc_hip_test.so (the product library has neither route counters nor the grid
-    cap), MPC_TEST_GRID set; returns the JSON object the code printed behind 'ROUTES '."""
-    import json
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    test_lib = os.path.join(root, "cal_22-mpc_amd", "libmpc_hip_test.so")
-    assert os.path.exists(test_lib), "libmpc_hip_test.so is missing: python cal_22-mpc_amd/build.py"
-    env = dict(os.environ, MPC_TEST_GRID=str(grid_cap), MPC_HIP_LIB=test_lib)
-    r = subprocess.run([sys.executable, "-c", (ROUTES_PRELUDE % (root, ROUTE_NAMES)) + code], capture_output=True, text=True,
-                       timeout=timeout, env=env, cwd=root)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    line = [l for l in r.stdout.split("\n") if l.startswith("ROUTES ")]
-    assert line, r.stdout[-2000:]
-    return json.loads(line[-1][7:])
 
 
 def test_deferred_line_queues_fill_and_drain_inside_the_loop(oracle, configs, traces, tmp_path):

@@ -183,6 +183,17 @@ def test_rejected_arguments(mpc):
     assert e.value.code == -22
 
 
+@pytest.mark.parametrize("L", [32, 64, 128])
+def test_sample_beyond_2_28_words_is_refused(mpc, L):
+    """A warm-up count and a slot index are 32 bits wide: S * W <= 2^28 keeps both in range.  One line more than that is
+    refused before anything is allocated, and so is a line count whose product with W wraps a 64-bit word."""
+    W = L // 4
+    for S in ((1 << 28) // W + 1, (1 << 28) + 1, (1 << 64) // W):
+        with pytest.raises(mpc.MpcError) as e:
+            mpc.SC2(L, S, device=0)
+        assert e.value.code == -22 and "2^28 words" in str(e.value), (L, S, str(e.value))
+
+
 def test_cpp_mirror_runs_the_reference_loop(mpc, traces, tmp_path):
     host = os.path.join(ROOT, "cal_22-mpc_amd", "host")
     libdir = os.path.join(ROOT, "cal_22-mpc_amd")

@@ -27,6 +27,7 @@ MPC_SIZE_BINS = 4096          # bins of a size histogram (include/mpc_hip_sizes.
 MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2, MPC_PATH_PATTERN = 1, 2, 3, 4, 5, 6, 7
 MPC_PATH_PATTERN_EVICTING = 9
 MPC_PATH_CPACK = 8
+MPC_PATH_CPACK_BLOCKS = 10
 MPC_CPACK_DICT_CARRIED, MPC_CPACK_DICT_PER_LINE = 0, 1     # mpc_create_cpack's dictionary_scope
 SYNTH_KINDS = {"zeros": 0, "random_u32": 1, "sine_f32": 2, "mixed": 3, "pointers_u64": 4}
 
@@ -88,6 +89,9 @@ def lib() -> C.CDLL:
             "mpc_create_pattern_evicting": ([C.c_uint, C.c_uint64, C.c_int, C.POINTER(H)], C.c_int),
             "mpc_pattern_distinct_lines": ([H, C.POINTER(C.c_uint64)], C.c_int),
             "mpc_create_cpack": ([C.c_uint, C.c_int, C.c_int, C.POINTER(H)], C.c_int),
+            "mpc_create_cpack_blocks": ([C.c_uint, C.c_uint64, C.c_int, C.POINTER(H)], C.c_int),
+            "mpc_cpack_blocks_restart": ([H], C.c_int),
+            "mpc_cpack_block_lines": ([H, C.POINTER(C.c_uint64)], C.c_int),
             "mpc_destroy": ([H], None),
             "mpc_get_info": ([H, C.POINTER(Info)], C.c_int),
             "mpc_last_error": ([H], C.c_char_p),
@@ -147,6 +151,7 @@ EXPORTED_SYMBOLS = [
     "mpc_group_create", "mpc_group_destroy", "mpc_group_last_error", "mpc_group_form", "mpc_group_compress_batch",
     "mpc_group_compress_batch_device", "mpc_group_compress_npy", "mpc_group_compress_gpgpusim_log", "mpc_group_sync",
     "mpc_create_pattern", "mpc_pattern_distinct_lines", "mpc_create_cpack", "mpc_create_pattern_evicting",
+    "mpc_create_cpack_blocks", "mpc_cpack_blocks_restart", "mpc_cpack_block_lines",
 ]
 # The SC2 entry points of include/mpc_hip.h.  Kept apart from EXPORTED_SYMBOLS, which lists the names of the
 # header's lowercase-letter form (mpc_[a-z_]+) only; every one of both lists is exported by libmpc_hip.so.
@@ -479,14 +484,47 @@ class CPACK(_Evaluator):
     """C-Pack (reference ``CPACK.cpp``) with a PER-LINE dictionary: the numbers of a fresh ``comp::CPACK(lineSize)`` per
     line, NOT those of the reference's ``-a CPACK`` run, whose one object carries its dictionary from line to line.
     ``dictionary="line"`` is the only scope the library evaluates; ``"carried"`` (and anything else) raises ``MpcError``
-    with the library's message.  Per-line ``selected`` is always 0; a size may exceed 8 x line_size."""
+    with the library's message.  Per-line ``selected`` is always 0; a size may exceed 8 x line_size.
+
+    ``dictionary="block", block_lines=N`` (``mpc_create_cpack_blocks``): one dictionary per block of N lines, what a fresh
+    ``comp::CPACK(lineSize)`` every N lines reports.  The object numbers its lines from 0 in the order of its calls (all
+    ingestion paths, until ``restart()``), block b is lines [b N, (b + 1) N).  The result depends on where blocks begin
+    (shards start at multiples of N: ``sharded.shard_range(..., align=N)``), a block is one lane's sequential work, and N
+    beyond the trace is the reference's ``-a CPACK`` run on a single lane: exact and slow."""
 
     PATTERNS = ("ZZZZ", "ZZZX", "MMMM", "MMMX", "MMXX", "XXXX")      # CPACKPattern order; 2, 12, 6, 16, 24, 34 bits
 
-    def __init__(self, line_size: int, dictionary: str = "line", device: int = -1):
+    def __init__(self, line_size: int, dictionary: str = "line", device: int = -1, *, block_lines: Optional[int] = None):
+        if dictionary == "block":
+            if block_lines is None:
+                raise ValueError("C-Pack: dictionary='block' needs block_lines (1 .. 2**32 - 1)")
+            if int(block_lines) != block_lines or not 0 <= block_lines < 1 << 64:
+                raise ValueError("C-Pack: block_lines is an integer from 1 to 2**32 - 1")
+            super().__init__("mpc_create_cpack_blocks", line_size, int(block_lines), device)
+            self.dictionary = "block"
+            n = C.c_uint64()
+            self._check(lib().mpc_cpack_block_lines(self._h, C.byref(n)))
+            self._block_lines = int(n.value)
+            return
+        if block_lines is not None:
+            raise ValueError("C-Pack: block_lines belongs to dictionary='block'")
         scope = CPACK_DICTIONARY.get(dictionary, -1) if isinstance(dictionary, str) else int(dictionary)
         super().__init__("mpc_create_cpack", line_size, scope, device)
         self.dictionary = "line"
+        self._block_lines = None
+
+    @property
+    def block_lines(self) -> Optional[int]:
+        """Lines per dictionary block; ``None`` for the per-line dictionary."""
+        return self._block_lines
+
+    @property
+    def kernel_form(self) -> str:
+        return (lib().mpc_kernel_form(self._h) or b"").decode()
+
+    def restart(self) -> None:
+        """The next line starts a block (``mpc_cpack_blocks_restart``): before a second trace.  The statistics stay."""
+        self._check(lib().mpc_cpack_blocks_restart(self._h))
 
     def result(self) -> Dict:
         """``CPACKResult`` (reference ``CPACK.h:28-96``): the totals, ``total_words`` and the six pattern counts."""

@@ -118,6 +118,18 @@ struct mpc_handle {
     bool evicting = false;       // mpc_create_pattern_evicting: `evict` is the set, `set` is unused
     MpcEvictSet evict{};
   } pat;
+  // C-Pack with a dictionary per block of N lines (mpc_create_cpack_blocks; N == 0: the per-line handle of mpc_create_cpack).
+  // A launch may end inside a block: the open block's dictionary stays on the device, and every launch that reads or
+  // writes it waits, on its own stream, for the event the one before it recorded -- whichever stream that was.
+  struct {
+    u64 N = 0;                   // lines per block
+    u64 pos = 0;                 // lines of the open block already evaluated (lines seen modulo N); not reset by mpc_stats_reset
+    uint32_t *d_state = nullptr; // [2][MPC_CPACK_STATE_WORDS]: a launch reads half `cur` and writes the other
+    int cur = 0;
+    hipEvent_t done = nullptr;
+    bool recorded = false;
+    std::string form;            // mpc_kernel_form
+  } cpk;
   std::vector<Stager *> fed_by;  // every stager that feeds this handle: its own, then those of the groups it is a member of (sc2_build)
   // size accounting (mpc_sizes.h): nothing of it exists before mpc_size_hist_enable
   struct {
@@ -344,6 +356,7 @@ int grid_for(const mpc_handle *h, u64 work_items, int block, int per_cu)
 
 int launch_sc2(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
 int launch_pattern(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
+int launch_cpack_blocks(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
 
 int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s)
 {
@@ -352,7 +365,9 @@ int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t 
   switch (h->algorithm) {
   case Algo::SC2: return launch_sc2(h, d_lines, n, d_sizes, d_sel, s);
   case Algo::Pattern: return launch_pattern(h, d_lines, n, d_sizes, d_sel, s);
-  case Algo::CPack: e = mpc_launch_cpack(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
+  case Algo::CPack:
+    if (h->cpk.N) return launch_cpack_blocks(h, d_lines, n, d_sizes, d_sel, s);
+    e = mpc_launch_cpack(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
   case Algo::BPC: e = mpc_launch_bpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
   case Algo::FPC: e = mpc_launch_fpc(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
   case Algo::BDI: e = mpc_launch_bdi(d_lines, n, h->L, d_sizes, d_sel, h->d_raw, grid_for(h, n, 256, kWgPerCu), s); break;
@@ -471,6 +486,27 @@ int launch_sc2(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int
   if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   h->sc2.seen += rest;
   h->sc2.lines += rest;
+  return MPC_OK;
+}
+
+// C-Pack in blocks: one launch; the host keeps where in a block the next line falls.  Only a launch that begins or ends
+// inside a block touches the dictionary kept on the device, and only those are chained.
+int launch_cpack_blocks(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s)
+{
+  auto &K = h->cpk;
+  const bool loads = K.pos != 0, stores = (K.pos + n) % K.N != 0;
+  if ((loads || stores) && K.recorded) HIPCHK(h, hipStreamWaitEvent(s, K.done, 0));
+  const u64 n_blocks = (K.pos + n + K.N - 1) / K.N;
+  const hipError_t e = mpc_launch_cpack_blocks(d_lines, n, h->L, K.N, K.pos, d_sizes, d_sel, h->d_raw, K.d_state + K.cur * MPC_CPACK_STATE_WORDS,
+                                               K.d_state + (K.cur ^ 1) * MPC_CPACK_STATE_WORDS,
+                                               grid_for(h, n_blocks, MPC_CPACK_BLOCK_THREADS, kWgPerCu), s);
+  if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  if (loads || stores) {
+    HIPCHK(h, hipEventRecord(K.done, s));
+    K.recorded = true;
+  }
+  if (stores) K.cur ^= 1;
+  K.pos = (K.pos + n) % K.N;
   return MPC_OK;
 }
 
@@ -667,6 +703,7 @@ void group_route(mpc_group *g)
       part += ": one kernel";
     } else {
       part = std::string(algorithm_name(h->algorithm)) + ": " + (h->algorithm == Algo::VPC ? mpc_kernel_form(h) : h->algorithm == Algo::Pattern ? "own kernels" : "own kernel");
+      if (h->cpk.N) part += ", dictionary per block of " + std::to_string(h->cpk.N) + " lines";
     }
     form += (form.empty() ? "" : "; ") + part;
   }
@@ -894,6 +931,49 @@ int mpc_create_cpack(unsigned line_size, int dictionary_scope, int device, mpc_h
   return create_fixed(Algo::CPack, line_size, device, out);
 }
 
+int mpc_create_cpack_blocks(unsigned line_size, uint64_t block_lines, int device, mpc_handle **out)
+{
+  if (!out) return MPC_E_INVAL;
+  *out = nullptr;
+  // (the refusals before a device is touched: the line size, then the block length)
+  int rc = check_line_size(Algo::CPack, line_size);
+  if (rc != MPC_OK) return rc;
+  if (block_lines < 1 || block_lines > 0xffffffffull)
+    return set_err(nullptr, MPC_E_INVAL, "C-Pack: block_lines " + std::to_string(block_lines) + " is not in 1..4294967295 (2^32 - 1) lines; a block "
+                                         "longer than the trace is the dictionary carried over all of it");
+  rc = create_fixed(Algo::CPack, line_size, device, out);
+  if (rc != MPC_OK) return rc;
+  mpc_handle *h = *out;
+  h->cpk.N = block_lines;
+  h->cpk.form = "one lane per block of " + std::to_string(block_lines) + (block_lines == 1 ? " line" : " lines");
+  if (hipMalloc((void **)&h->cpk.d_state, 2 * MPC_CPACK_STATE_WORDS * sizeof(uint32_t)) != hipSuccess) {
+    h->cpk.d_state = nullptr;
+    g_create_error = "C-Pack: hipMalloc of the open block's dictionary failed";
+    return create_failed(MPC_E_NOMEM, out);
+  }
+  if (hipMemset(h->cpk.d_state, 0, 2 * MPC_CPACK_STATE_WORDS * sizeof(uint32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipEventCreateWithFlags(&h->cpk.done, hipEventDisableTiming) != hipSuccess) {
+    g_create_error = "C-Pack: initialising the open block's dictionary failed";
+    return create_failed(MPC_E_NODEVICE, out);
+  }
+  return MPC_OK;
+}
+
+int mpc_cpack_blocks_restart(mpc_handle *h)
+{
+  if (!h) return MPC_E_INVAL;
+  if (h->algorithm != Algo::CPack || !h->cpk.N) return set_err(h, MPC_E_INVAL, "C-Pack: not a handle of mpc_create_cpack_blocks");
+  h->cpk.pos = 0;      // (the dictionary on the device is only read by a launch that begins inside a block)
+  return MPC_OK;
+}
+
+int mpc_cpack_block_lines(const mpc_handle *h, uint64_t *n)
+{
+  if (!h || !n || h->algorithm != Algo::CPack || !h->cpk.N) return MPC_E_INVAL;
+  *n = h->cpk.N;
+  return MPC_OK;
+}
+
 int mpc_create_pattern(unsigned line_size, int device, mpc_handle **out)
 {
   int rc = create_fixed(Algo::Pattern, line_size, device, out);
@@ -1088,6 +1168,8 @@ void mpc_destroy(mpc_handle *h)
       if (p) (void)hipFree(p);
   }
   if (h->pat.done) (void)hipEventDestroy(h->pat.done);
+  if (h->cpk.d_state) (void)hipFree(h->cpk.d_state);
+  if (h->cpk.done) (void)hipEventDestroy(h->cpk.done);
   if (h->acct.d_hist) (void)hipFree(h->acct.d_hist);
   if (h->acct.d_scratch) (void)hipFree(h->acct.d_scratch);
   if (h->acct.scratch_done) (void)hipEventDestroy(h->acct.scratch_done);
@@ -1104,7 +1186,8 @@ int mpc_get_info(const mpc_handle *h, mpc_info *info)
   info->num_modules = vpc ? h->cfg.M : 0;
   info->num_clusters = vpc ? h->cfg.M + 1 : facts(h->algorithm).clusters;
   info->hist_bins = vpc ? h->cfg.hist_bins : 0;
-  info->kernel_path = vpc && h->route.kernel == VpcKernel::Generic ? MPC_PATH_VPC_GENERIC : h->pat.evicting ? MPC_PATH_PATTERN_EVICTING : facts(h->algorithm).path;
+  info->kernel_path = vpc && h->route.kernel == VpcKernel::Generic ? MPC_PATH_VPC_GENERIC : h->pat.evicting ? MPC_PATH_PATTERN_EVICTING
+                      : h->cpk.N ? MPC_PATH_CPACK_BLOCKS : facts(h->algorithm).path;
   info->device = h->device;
   info->stats_len = h->stats_len;
   return MPC_OK;
@@ -1144,6 +1227,7 @@ const char *mpc_kernel_form(const mpc_handle *h)
   if (h->algorithm == Algo::Pattern && h->pat.evicting)
     return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled, then the evicting set passes" : "run-time loop, then the evicting set passes";
   if (h->algorithm == Algo::Pattern) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled, then the set passes" : "run-time loop, then the set passes";
+  if (h->algorithm == Algo::CPack && h->cpk.N) return h->cpk.form.c_str();
   if (h->algorithm == Algo::CPack) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled" : "run-time loop";
   if (h->algorithm != Algo::VPC) return "unrolled";
   if (h->route.kernel == VpcKernel::AtCreation && h->jit.from_cache) return "unrolled, compiled at creation (from the cache)";
@@ -1430,7 +1514,7 @@ int mpc_stats_reset(mpc_handle *h)
   if (h->acct.d_hist) HIPCHK(h, hipMemset(h->acct.d_hist, 0, MPC_SIZE_BINS * sizeof(u64)));
   if (h->acct.on) h->acct.vpc_base.assign(h->acct.vpc_base.size(), 0);
   h->extra.assign(h->stats_len, 0);
-  h->sc2.lines = h->sc2.warm = 0;     // SC2: the table and the line counter stay
+  h->sc2.lines = h->sc2.warm = 0;     // SC2: the table and the line counter stay (C-Pack in blocks: the open block and the position in it)
   return MPC_OK;
 }
 

@@ -2,7 +2,7 @@
 //
 // The launchers have C linkage, so a declaration that drifted from its definition would still link and then misbehave.
 // This header is therefore included by the callers (mpc_capi.hip, mpc_jit.h) AND by the units that define the
-// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_sizes.hip, the host section of mpc_vpc_lane.hip):
+// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_sizes.hip, the host section of mpc_vpc_lane.hip):
 // the compiler sees declaration and definition together and refuses a mismatch.  Host code only -- the run-time
 // compiled source of mpc_jit.h (-DMPC_LANE_JIT) never sees it, and it is not one of the files that key the code
 // object cache.
@@ -77,6 +77,16 @@ hipError_t mpc_launch_pattern_evict(const void *d_lines, uint32_t n_lines, int L
 // mpc_cpack.hip
 hipError_t mpc_launch_cpack(const void *d_lines, unsigned long long n_lines, int L, uint16_t *d_sizes, int8_t *d_sel, unsigned long long *d_stats,
                             int grid, hipStream_t stream);
+
+// mpc_cpack_blocks.hip: n_lines lines that begin `pos` lines into a block of block_lines lines (pos < block_lines).  The open
+// block's dictionary (MPC_CPACK_STATE_WORDS words) is read from d_state when pos > 0 and written to d_state_out, another array, when
+// the launch ends inside a block: launches of one handle must not overlap.  One lane
+// per block: the grid is sized for ceil((pos + n_lines) / block_lines) work items of MPC_CPACK_BLOCK_THREADS lanes a workgroup.
+#define MPC_CPACK_BLOCK_THREADS 64
+#define MPC_CPACK_STATE_WORDS 32      /* 16 entries in ring order, the front, padding */
+hipError_t mpc_launch_cpack_blocks(const void *d_lines, unsigned long long n_lines, int L, unsigned long long block_lines, unsigned long long pos,
+                                   uint16_t *d_sizes, int8_t *d_sel, unsigned long long *d_stats, const uint32_t *d_state, uint32_t *d_state_out,
+                                   int grid, hipStream_t stream);
 
 // mpc_sizes.hip
 int mpc_sizes_wg_per_cu(const MpcSizesArgs *A);

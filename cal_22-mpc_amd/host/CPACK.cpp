@@ -39,4 +39,20 @@ CPACK::CPACK(unsigned lineSize, CPACKDictionary scope) : DeviceCompressor("CPACK
   m_Stat->CompressorName = "C-Pack";
 }
 
+CPACK::CPACK(unsigned lineSize, CPACKDictionary scope, uint64_t blockLines) : DeviceCompressor("CPACK", lineSize), m_BlockLines(blockLines)
+{
+  if (scope != CPACKDictionary::PerBlock)
+    fail("CPACK: cannot create the evaluator", MPC_E_INVAL, "C-Pack: a block length goes with CPACKDictionary::PerBlock only");
+  CheckCreated(mpc_create_cpack_blocks(lineSize, blockLines, -1, &m_Handle));
+  m_Stat = new CPACKResult(lineSize);
+  m_Stat->CompressorName = "C-Pack";
+}
+
+void CPACK::Restart()
+{
+  FlushLines();
+  int rc = mpc_cpack_blocks_restart(m_Handle);
+  if (rc != MPC_OK) Fail("CPACK::Restart", rc);
+}
+
 }  // namespace comp

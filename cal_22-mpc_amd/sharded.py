@@ -14,9 +14,14 @@ from typing import Tuple
 import numpy as np
 
 
-def shard_range(n_lines: int, rank: int, world: int) -> Tuple[int, int]:
-    """Contiguous shard [begin, end) of rank `rank`: GPU g gets [g*N/G, (g+1)*N/G)."""
-    return (rank * n_lines) // world, ((rank + 1) * n_lines) // world
+def shard_range(n_lines: int, rank: int, world: int, align: int = 1) -> Tuple[int, int]:
+    """Contiguous shard [begin, end) of rank `rank`: GPU g gets [g*N/G, (g+1)*N/G).  ``align`` > 1: every shard starts at
+    a multiple of ``align`` lines (the block length of ``CPACK(..., dictionary="block")``, whose result depends on where
+    blocks begin): the cuts are rounded down to one, the last shard still ends at ``n_lines``; a shard may be empty."""
+    if align < 1:
+        raise ValueError("align is at least 1")
+    cut = lambda r: n_lines if r >= world else ((r * n_lines) // world) // align * align      # noqa: E731
+    return cut(rank), cut(rank + 1)
 
 
 def all_reduce_stats(vec: np.ndarray, device=None) -> np.ndarray:

@@ -49,11 +49,12 @@ typedef struct mpc_handle mpc_handle;
 #define MPC_PATH_SC2          6
 #define MPC_PATH_PATTERN      7
 #define MPC_PATH_CPACK        8  /* C-Pack with a per-line dictionary */
+#define MPC_PATH_CPACK_BLOCKS 10  /* mpc_create_cpack_blocks: C-Pack with a dictionary shared by blocks of N lines, one lane per block */
 #define MPC_PATH_PATTERN_EVICTING 9  /* mpc_create_pattern_evicting: the analysis kernel of MPC_PATH_PATTERN, then the evicting set's passes */
 
 typedef struct {
   int32_t abi_version;
-  int32_t algorithm;        /* 0 = VPC, 1 = BDI, 2 = FPC, 3 = BPC, 4 = SC2, 5 = Pattern, 6 = C-Pack (per-line dictionary) */
+  int32_t algorithm;        /* 0 = VPC, 1 = BDI, 2 = FPC, 3 = BPC, 4 = SC2, 5 = Pattern, 6 = C-Pack (per-line dictionary, or per block of lines: kernel_path) */
   int32_t line_size;        /* bytes per line (L) */
   int32_t num_modules;      /* VPC: M; BDI: 0 */
   int32_t num_clusters;     /* VPC: M+1 (cluster -1 .. M-1); BDI: 9 states; FPC: 8 prefixes; BPC: 7 patterns; SC2: 2 (warm-up, table); Pattern: 10 states; C-Pack: 6 patterns */
@@ -162,6 +163,33 @@ int mpc_pattern_distinct_lines(mpc_handle *h, uint64_t *n);
 #define MPC_CPACK_DICT_CARRIED  0
 #define MPC_CPACK_DICT_PER_LINE 1
 int mpc_create_cpack(unsigned line_size, int dictionary_scope, int device, mpc_handle **out);
+/* C-Pack with a dictionary shared by BLOCKS of block_lines lines: what one reference comp::CPACK object reports when a
+ * fresh one is constructed every block_lines lines.  The handle numbers the lines it is given 0, 1, 2, ... in the order
+ * of its calls, from creation or the last mpc_cpack_blocks_restart, across calls and across ingestion paths.  Block b is
+ * lines [b N, (b + 1) N), N = block_lines; the last block of a trace may be short.  At the first word of line b N the
+ * dictionary is 16 zero words; within the block it is carried from word to word and from line to line exactly as
+ * CPACK::CompressLine does on one object (the word rules are those above).  Per-line output: that line's size in bits
+ * (not capped); `selected` is 0.  Statistics: the C-Pack layout.  N = 1 gives the numbers of mpc_create_cpack.
+ * What a caller must know:
+ *  - The result depends on where blocks begin.  Shards of a trace must start at multiples of N (a rank's first line is
+ *    line 0 of its handle), or the shards' numbers are those of another blocking.
+ *  - A block is one lane's sequential work: the cost of a line grows with N, and a trace of fewer than some ten thousand
+ *    blocks does not fill the device.
+ *  - N beyond the length of the trace is the reference's `-a CPACK` run, one dictionary carried over all of it, evaluated
+ *    by a single lane.  It is exact and slow.
+ * A call, a staged chunk or a launch may end inside a block: the open block's dictionary stays in device memory and the
+ * next lines continue it, whichever call, ingestion path or group brings them; the launches of one handle are chained
+ * and never overlap.  mpc_stats_reset clears the statistics and leaves the open block and the position in it (as it
+ * leaves SC2's line counter).
+ * line_size: a multiple of 4 from 4 to 256.  block_lines: 1 .. 2^32 - 1.  Both are checked before any device is touched
+ * (MPC_E_INVAL, a message that starts with "C-Pack" and names the limit).  mpc_get_info reports algorithm 6, 6 clusters
+ * and MPC_PATH_CPACK_BLOCKS; mpc_kernel_form and mpc_group_form name the block length.                                  */
+int mpc_create_cpack_blocks(unsigned line_size, uint64_t block_lines, int device, mpc_handle **out);
+/* The next line the handle is given starts a block (and is line 0 again): for a handle that is fed a second trace.  The
+ * statistics stay.  MPC_E_INVAL for every handle that mpc_create_cpack_blocks did not make.                             */
+int mpc_cpack_blocks_restart(mpc_handle *h);
+/* The block length the handle was created with.  MPC_E_INVAL for every other handle.                                   */
+int mpc_cpack_block_lines(const mpc_handle *h, uint64_t *n);
 void mpc_destroy(mpc_handle *h);
 
 int mpc_get_info(const mpc_handle *h, mpc_info *info);

@@ -11,7 +11,8 @@ stand-in for the strutil.h header are written, with the build, into a temporary 
 is removed afterwards; the output holds seeds, an input digest and the reference's outputs only.
 
 Run where the reference sources are (REF, as in oracle/Makefile):
-    REF=/path/to/reference python tests/golden/make_ref_sc2_vectors.py
+    REF=/path/to/reference python tests/golden/make_ref_sc2_vectors.py [--check]
+--check regenerates everything in memory and compares it with the committed file instead of writing it.
 """
 import json
 import os
@@ -87,10 +88,10 @@ int main(int argc, char **argv)
 """
 
 
-def main():
-    ref = os.environ.get("REF")
-    if not ref:
-        sys.exit("set REF to the root of the reference sources (as for oracle/Makefile)")
+OUT = os.path.join(HERE, "ref_sc2_vectors.json")
+
+
+def generate(ref):
     src = os.path.join(ref, "src")
     import torch
     fmt_inc = os.path.join(os.path.dirname(torch.__file__), "include")
@@ -133,10 +134,28 @@ def main():
                   f"ratio {res[0] / res[1]:.4f}")
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
-    dst = os.path.join(HERE, "ref_sc2_vectors.json")
-    with open(dst, "w") as f:
-        json.dump({"source": "reference src/compressor/SC2.cpp, compiled unmodified", "cases": out}, f, separators=(",", ":"))
-    print(dst, os.path.getsize(dst), "bytes")
+    return {"source": "reference src/compressor/SC2.cpp, compiled unmodified", "cases": out}
+
+
+def main():
+    ref = os.environ.get("REF")
+    if not ref:
+        sys.exit("set REF to the root of the reference sources (as for oracle/Makefile)")
+    doc = generate(ref)
+    if "--check" in sys.argv:
+        with open(OUT) as f:
+            old = json.load(f)
+        new = json.loads(json.dumps(doc))
+        names = [c["name"] for c in new["cases"]]
+        diff = sorted(set(names) ^ {c["name"] for c in old["cases"]})
+        diff += [c["name"] for c in new["cases"] for o in old["cases"] if o["name"] == c["name"] and o != c]
+        if diff or old["source"] != new["source"] or [c["name"] for c in old["cases"]] != names:
+            sys.exit(f"differs from {OUT}: {diff or 'order or source'}")
+        print(f"{OUT}: no difference ({len(names)} cases)")
+        return
+    with open(OUT, "w") as f:
+        json.dump(doc, f, separators=(",", ":"))
+    print(OUT, os.path.getsize(OUT), "bytes")
 
 
 if __name__ == "__main__":

@@ -154,6 +154,11 @@ def case_lines(spec: dict) -> np.ndarray:
     """The lines of one fixture case: a warm-up sample of S lines with the frequencies the case is about, then
     `post` lines drawn from the same symbols with some random words (misses) mixed in."""
     L, S, post, kind = spec["L"], spec["S"], spec["post"], spec["kind"]
+    if kind == "keys":            # chosen words (tests/sc2_keys.py): the builder makes the whole case, tail included
+        import sc2_keys
+        lines, bl, bs, _ = sc2_keys.build(spec["builder"])
+        assert (bl, bs, len(lines) - bs) == (L, S, post), spec["name"]
+        return lines
     W = L // 4
     rng = np.random.default_rng(spec["seed"])
     nw = S * W
@@ -208,6 +213,15 @@ CASES = [
     {"name": "zipf_L64", "kind": "zipf", "L": 64, "S": 400, "post": 500, "seed": 107},
     {"name": "zipf_L128", "kind": "zipf", "L": 128, "S": 300, "post": 400, "seed": 108},
     {"name": "zipf_L256", "kind": "zipf", "L": 256, "S": 200, "post": 300, "seed": 109},
+    # chosen words: the selection's early exit and first eviction, a count digit that holds exactly what is needed, a tie
+    # decided in the low symbol byte with 0 evicted and 0xFFFFFFFF kept, 0 evicted from a sample, a bucket layout that
+    # needs its second seed pair
+    {"name": "keys_distinct_1024", "kind": "keys", "builder": "distinct_1024", "L": 64, "S": 65, "post": 80},
+    {"name": "keys_distinct_1025", "kind": "keys", "builder": "distinct_1025", "L": 64, "S": 65, "post": 80},
+    {"name": "keys_top_group_1024", "kind": "keys", "builder": "top_group_1024", "L": 64, "S": 160, "post": 120},
+    {"name": "keys_tie_byte0", "kind": "keys", "builder": "tie_byte0_with_zero_and_ones", "L": 64, "S": 116, "post": 120},
+    {"name": "keys_evicted_zero", "kind": "keys", "builder": "evicted_zero", "L": 64, "S": 65, "post": 100},
+    {"name": "keys_retry_once", "kind": "keys", "builder": "retry_once", "L": 64, "S": 128, "post": 120},
 ]
 
 

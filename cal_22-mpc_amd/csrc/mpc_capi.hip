@@ -26,7 +26,8 @@
 #ifndef MPC_TESTING
 #define MPC_TESTING 0
 #endif
-constexpr size_t kRouteWords = MPC_TESTING ? 16 : 0;
+constexpr size_t kRouteWords = (MPC_TESTING || MPC_STAMPS) ? 16 : 0;
+constexpr size_t kTestWords = kRouteWords + (MPC_STAMPS ? MPC_STAMP_WORDS : 0);      // route counters, then the workgroup stamps
 
 typedef unsigned long long u64;
 
@@ -237,9 +238,9 @@ int finish_create(mpc_handle *h)
 {
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
     return set_err(nullptr, MPC_E_NODEVICE, "hipStreamCreate failed");
-  if (hipMalloc(&h->d_raw, (h->raw_len + kRouteWords) * sizeof(u64)) != hipSuccess)
+  if (hipMalloc(&h->d_raw, (h->raw_len + kTestWords) * sizeof(u64)) != hipSuccess)
     return set_err(nullptr, MPC_E_NOMEM, "hipMalloc(stats) failed");
-  if (hipMemsetAsync(h->d_raw, 0, (h->raw_len + kRouteWords) * sizeof(u64), h->stream) != hipSuccess ||
+  if (hipMemsetAsync(h->d_raw, 0, (h->raw_len + kTestWords) * sizeof(u64), h->stream) != hipSuccess ||
       hipStreamSynchronize(h->stream) != hipSuccess)
     return set_err(nullptr, MPC_E_NODEVICE, "hipMemset(stats) failed");
   h->extra.assign(h->stats_len, 0);
@@ -1510,7 +1511,7 @@ int mpc_stats_reset(mpc_handle *h)
   int rc = sync_all(h);
   if (rc != MPC_OK) return rc;
   HIPCHK(h, hipDeviceSynchronize());
-  HIPCHK(h, hipMemset(h->d_raw, 0, (h->raw_len + kRouteWords) * sizeof(u64)));
+  HIPCHK(h, hipMemset(h->d_raw, 0, (h->raw_len + kTestWords) * sizeof(u64)));
   if (h->acct.d_hist) HIPCHK(h, hipMemset(h->acct.d_hist, 0, MPC_SIZE_BINS * sizeof(u64)));
   if (h->acct.on) h->acct.vpc_base.assign(h->acct.vpc_base.size(), 0);
   h->extra.assign(h->stats_len, 0);
@@ -1731,6 +1732,18 @@ int mpc_test_routes(mpc_handle *h, uint64_t *out, size_t n)
   uint64_t tmp[kRouteWords];
   HIPCHK(h, hipMemcpy(tmp, h->d_raw + h->raw_len, sizeof(tmp), hipMemcpyDeviceToHost));
   for (size_t i = 0; i < n; i++) out[i] = i < kRouteWords ? tmp[i] : 0;
+  return MPC_OK;
+}
+#endif
+
+#if MPC_STAMPS
+// test library and -DMPC_STAMPS=1 builds: the workgroup stamps of the handle's last lane-kernel launch (mpc_device.h: MPC_STAMP_WORDS words)
+int mpc_test_stamps(mpc_handle *h, uint64_t *out, size_t n)
+{
+  if (!h || !out || n > (size_t)MPC_STAMP_WORDS) return MPC_E_INVAL;
+  if (hipSetDevice(h->device) != hipSuccess) return MPC_E_HIP;
+  HIPCHK(h, hipDeviceSynchronize());
+  HIPCHK(h, hipMemcpy(out, h->d_raw + h->raw_len + kRouteWords, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return MPC_OK;
 }
 #endif

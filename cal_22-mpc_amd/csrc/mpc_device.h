@@ -17,6 +17,25 @@ typedef unsigned long long uint64_t;
 typedef unsigned long uintptr_t;
 #endif
 
+/* Workgroup stamps.  Test library (MPC_TESTING), and development builds with -DMPC_STAMPS=1 alone -- the product's kernels plus
+   the stamps: the test library's route counters are same-address atomics, one per 128-line block, and make a 16 GiB launch
+   nine times longer, so a launch is timed with the second kind.  Behind the 16 route counter words: three words per workgroup of the last lane-kernel launch (workgroups
+   0 .. MPC_STAMP_WGS - 1 of the unrolled-sequence kernels) -- the wall clock (100 MHz) at entry, the wall clock after the
+   statistics flush, and the hardware ids of the CU it ran on (XCC_ID << 32 | HW_ID).  mpc_test_stamps() reads them;
+   tools/wg_spread.py turns them into the launch's per-CU finish spread.  "Last" is per handle and by time of store:
+   launches of one handle that overlap (the stager's two slot streams) write the same words, and what is read then is a
+   mixture -- harmless, but only a launch that ran alone can be read.  Kernels compiled at creation (mpc_jit.h) get
+   MPC_TESTING alone: they stamp in the test library, not in a -DMPC_STAMPS=1 build. */
+#ifndef MPC_STAMPS
+#if defined(MPC_TESTING) && MPC_TESTING
+#define MPC_STAMPS 1
+#else
+#define MPC_STAMPS 0
+#endif
+#endif
+#define MPC_STAMP_WGS 1024
+#define MPC_STAMP_WORDS (3 * MPC_STAMP_WGS)
+
 #define MPC_MAX_MODULES 32        /* M (AllZero + AllWordSame + prediction modules) */
 #define MPC_MAX_PRED    31        /* prediction (PredComp) modules */
 #define MPC_MAX_LINE    256       /* bytes per line, generic path */

@@ -32,8 +32,12 @@ enum {
   MPC_RT_VPC_TAIL_GROUPS,    // groups behind the last whole block (plain loads)
   MPC_RT_BDI_DEFERRED,
   MPC_RT_BDI_DRAINS,
+  MPC_RT_VPC_CERT_GROUPS,    // groups of the plain unrolled kernels that ran the certificate's fast tier
+  MPC_RT_VPC_CERT_EXACT,     // ... of which the exact tier ran too (the fast tier left a needed lane open)
+  MPC_RT_VPC_ENCODER,        // groups in which the common encoder ran
   MPC_ROUTE_COUNT = 16
 };
+// (behind them, test library only: the workgroup stamps of mpc_device.h, MPC_STAMP_WORDS words)
 // called by ONE lane of a wave
 __device__ __forceinline__ void route_add(u64 *routes, int which, u32 v)
 {

@@ -67,6 +67,9 @@
 #ifndef MPC_DRAIN_WAIT
 #define MPC_DRAIN_WAIT 1   // development-only: 0 leaves the wait for the drain copy's loads to the compiler (see the drain loop)
 #endif
+#ifndef MPC_CERT_TIERS
+#define MPC_CERT_TIERS 1   // development-only (A/B): 0 = the exact certificate on every group of the plain kernels
+#endif
 #ifndef MPC_ABLATE
 #define MPC_ABLATE 0   // development-only timing ablations (tools/ablate.sh); results are WRONG when non-zero
 #endif
@@ -783,6 +786,86 @@ __device__ __forceinline__ u32 fold_pack(const u32 (&X)[NG])
 // bits (it is neither a single one nor an adjacent pair, FPCModule.cpp:50-69); any other
 // non-zero row costs at least 7; a zero row sits in a run that costs at least 4.
 // True: the encoding cannot beat 8*L bits, the encoder need not run.
+//
+// Two tiers (lane_step).  The FOLDS are shared: Sf7 / Sb7 = per row, columns 0..6 / 9..15 non-zero.  The fast tier
+// (lane_certified_fast) takes a row for a 17-bit row only when both folds are set -- then both halves are non-zero AND
+// there is a bit outside columns 7 / 8, whatever those two columns hold, so it never counts a row the exact test would
+// not -- and closes a lane when every row has a fold set (no zero row: nnz = 2 W, no run) and 10 n17 + 14 W >= 32 W, i.e.
+// n17 >= ceil(1.8 W): 29 of the 32 rows of a 64-byte line (290 + 224 = 514 >= 512).  It needs neither the gather of
+// columns 7 and 8 nor the bound's arithmetic.  A random row fails it with probability 2 / 128, a random line (4 or more
+// failing rows of 32) with 0.0018, a group of 64 with about 0.1 -- if the rows were random: counted on the random trace,
+// 0.20 of the groups take the exact tier (the XORed residues of the winning module are not uniform), which runs on the same
+// folds.
+template <int W>
+struct LaneFolds {
+  static constexpr int NG = W / 4;
+  static constexpr int GP = NG < 4 ? NG : 4;      // column groups per packed word
+  static constexpr int NH = NG / GP;
+  u32 Sf7[NH], Sb7[NH];
+};
+template <int W>
+__device__ __forceinline__ void lane_folds(const u32 (&t)[W], LaneFolds<W> &f)
+{
+  constexpr int GP = LaneFolds<W>::GP;
+#pragma unroll
+  for (int h = 0; h < LaneFolds<W>::NH; h++) {
+    const u32 *th = &t[16 * h];
+    // columns 0..6 and 9..15 of every group folded to plane masks
+    u32 F[GP], B[GP];
+#pragma unroll
+    for (int j = 0; j < GP; j++) {
+      F[j] = th[4 * j] | (th[4 * j + 1] & 0x00ffffffu);
+      B[j] = (th[4 * j + 2] & 0xffffff00u) | th[4 * j + 3];
+    }
+    f.Sf7[h] = fold_pack<GP>(F);
+    f.Sb7[h] = fold_pack<GP>(B);
+  }
+}
+// (returns the wave mask of the closed lanes: two ballots combined on the scalar unit -- the ballot of a combined condition
+// first makes it a vector register again)
+template <int W>
+__device__ __forceinline__ u64 lane_certified_fast(const LaneFolds<W> &f)
+{
+  constexpr u32 rows = LaneFolds<W>::GP == 2 ? 0x00ff00ffu : ~0u;      // the row bits of a packed word (fold_pack)
+  u32 n17 = 0, any = rows;
+#pragma unroll
+  for (int h = 0; h < LaneFolds<W>::NH; h++) {
+    n17 += (u32)__popc(f.Sf7[h] & f.Sb7[h]);
+    any &= f.Sf7[h] | f.Sb7[h];
+  }
+  return __ballot(n17 >= (18u * W + 9u) / 10u) & __ballot(any == rows);
+}
+template <int W>
+__device__ __forceinline__ bool lane_certified_exact(const u32 (&t)[W], const LaneFolds<W> &f)
+{
+  constexpr int GP = LaneFolds<W>::GP;
+  u32 n17 = 0, nnz = 0;
+#pragma unroll
+  for (int h = 0; h < LaneFolds<W>::NH; h++) {
+    const u32 *th = &t[16 * h];
+    // columns 7 and 8 are whole bytes (byte 3 of word 1, byte 0 of word 2) and only need gathering
+    const u32 Sf7 = f.Sf7[h], Sb7 = f.Sb7[h];
+    u32 C7, C8;
+    if constexpr (GP == 2) {
+      C7 = perm(th[5], th[1], 0x0c070c03u);
+      C8 = perm(th[6], th[2], 0x0c040c00u);
+    } else {
+      C7 = perm(perm(th[13], th[9], 0x0c0c0703u), perm(th[5], th[1], 0x0c0c0703u), 0x05040100u);
+      C8 = perm(perm(th[14], th[10], 0x0c0c0400u), perm(th[6], th[2], 0x0c0c0400u), 0x05040100u);
+    }
+    const u32 Sf = Sf7 | C7, Sb = Sb7 | C8;     // front / back half non-zero
+    const u32 So = Sf7 | Sb7;                   // a bit outside columns 7 / 8
+    n17 += (u32)__popc(Sf & Sb & So);
+    nnz += (u32)__popc(Sf | Sb);
+  }
+  const u32 bound = 10u * n17 + 7u * nnz + (nnz != 2u * W ? 4u : 0u);
+  return bound >= 32u * W;
+}
+// Every other kernel: the one-tier form, as it was.  It is the same arithmetic as lane_folds + lane_certified_exact, and a
+// change of the bound has to be made in BOTH.  The second copy is deliberate: written as a call of those two (three forms
+// were tried, the folds handed over by reference, by pointer behind a constant flag, and filled in place) the kernels that
+// this function serves no longer compile to the code they had -- operands of the row count's v_bitop3 swap at every line
+// size, and three of the 32-byte general-layout kernels spill two more SGPRs (25 -> 27, 25 -> 27, 21 -> 23).
 template <int W>
 __device__ __forceinline__ bool lane_certified(const u32 (&t)[W])
 {
@@ -968,6 +1051,7 @@ struct LaneEnv {
   int8_t *sel_out;
   u32 *defer_q;      // this wave's queue of deferred lines (LDS, defer_cap entries)
   u32 defer_cap;
+  u64 *routes;       // (test library only: the route counters)
 };
 
 // sum and sum of squares of the bytes of W words (two chains each: the reductions are
@@ -1127,7 +1211,28 @@ __device__ __forceinline__ void lane_step(const uint4 (&v)[W / 4], u32 line0, u3
     // straight away (rs.enc_hot, wave-uniform).
     u64 open_mask = need_mask;
     const bool byte_major = (NPT == 0 && P.byte_major) || (MPC_JIT_BM && NPT > 0);    // (run-time loop: no certificate for that order)
-    if (!rs.enc_hot && !byte_major) open_mask &= ~__ballot(lane_certified<W>(t));
+    if constexpr (MPC_CERT_TIERS && W == 16 && NPT > 0 && !GEN && !MPC_JIT_BM) {
+      // Plain layout, 64-byte lines: the fast tier first; the exact one only where it left a needed lane open (one scalar
+      // compare).  Which tiers ran changes no result: both are sufficient tests for the same decision -- the encoder need
+      // not run -- and a lane they leave open is decided by the encoder itself.  (At 32 and 128 bytes the fast tier wants 15
+      // of 16 and 58 of 64 rows and closes too few groups: 0.81 and 0.80 of them went on to the exact tier, random 32-byte
+      // lines +1.2 %.  Going straight to the exact tier after a group whose fast tier left a lane open: slower on every
+      // trace.  profiles/sched_ab.txt, variants c and c2.)
+      if (!rs.enc_hot) {
+        LaneFolds<W> folds;
+        lane_folds<W>(t, folds);
+        open_mask &= ~lane_certified_fast<W>(folds);
+        if (MPC_TESTING && E.lane == 0) route_add(E.routes, MPC_RT_VPC_CERT_GROUPS, 1u);
+        // (laid out as the unlikely branch: as a likely one it sat in the way of the groups that skip the certificate, and the
+        // sine and the mixed trace, which run it on 3 % of their groups, were 0.6 % slower -- profiles/sched_ab.txt)
+        if (__builtin_expect(open_mask != 0, 0)) {
+          open_mask &= ~__ballot(lane_certified_exact<W>(t, folds));
+          if (MPC_TESTING && E.lane == 0) route_add(E.routes, MPC_RT_VPC_CERT_EXACT, 1u);
+        }
+      }
+    } else {
+      if (!rs.enc_hot && !byte_major) open_mask &= ~__ballot(lane_certified<W>(t));
+    }
     if (MPC_JIT_BM && NPT > 0 && !rs.enc_hot) open_mask &= ~__ballot(lane_certified_bm<W>(t));
     if constexpr (MPC_ABLATE & 16) {                  // timing ablation: the certificate stays, the compressible path is cut off
       if (open_mask) E.st.hist[0] = 1u;               // (keeps the certificate alive; results are wrong)
@@ -1136,6 +1241,7 @@ __device__ __forceinline__ void lane_step(const uint4 (&v)[W / 4], u32 line0, u3
     u32 enc = uncomp;
     u64 keep_mask = 0;
     if (open_mask) {
+      if (MPC_TESTING && E.lane == 0) route_add(E.routes, MPC_RT_VPC_ENCODER, 1u);
       if (byte_major) enc = lane_encode_bm<W>(t);
       else enc = lane_encode<W>(t);
       if (!no_pred) keep_mask = __ballot(enc < uncomp) & open_mask;             // VPC.cpp:397-407
@@ -1343,7 +1449,16 @@ __device__ __forceinline__ void vpc_lane_body(unsigned char *smem, const uint4 *
   u32 iter = 0;
   const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   u64 *routes = gstats + (2 * E.K + E.K * E.bins);         // (test library only: route counters behind the raw statistics)
-  (void)routes;
+  E.routes = MPC_TESTING ? routes : nullptr;
+#if MPC_STAMPS
+  // (test library and -DMPC_STAMPS=1 builds only) workgroup stamps: wall clock at entry and the CU's hardware ids -- HW_ID is hardware register 4,
+  // XCC_ID register 20, all 32 bits each; plain vector stores of one lane
+  u64 *stamp = routes + MPC_ROUTE_COUNT + 3u * blockIdx.x;
+  if (sizeof...(KINDS) > 0 && threadIdx.x == 0 && blockIdx.x < (u32)MPC_STAMP_WGS) {
+    stamp[0] = wall_clock64();
+    stamp[2] = ((u64)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (u64)__builtin_amdgcn_s_getreg((31 << 11) | 4);
+  }
+#endif
   bool alt = false;    // wave-uniform: the prefilters saw lines of two kinds alternate (paired groups)
   uint4 va[NQ];
   u32 qn = 0;          // deferred lines waiting in the wave's queue (wave-uniform)
@@ -1510,6 +1625,9 @@ __device__ __forceinline__ void vpc_lane_body(unsigned char *smem, const uint4 *
   }
   lane_run_flush(rs, E.st, E.K, E.bins);
   stats_flush(E.st, E.K, E.bins, gstats, (int)(E.lane + 64u * wave), 64 * (int)WPB);
+#if MPC_STAMPS
+  if (sizeof...(KINDS) > 0 && E.lane + 64u * wave == 0u && blockIdx.x < (u32)MPC_STAMP_WGS) stamp[1] = wall_clock64();
+#endif
 }
 
 #define MPC_LANE_BOUNDS(W, NPT)                                                                                     \

@@ -28,6 +28,7 @@ MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BP
 MPC_PATH_PATTERN_EVICTING = 9
 MPC_PATH_CPACK = 8
 MPC_PATH_CPACK_BLOCKS = 10
+MPC_PATH_FIT_PAIRS, MPC_PATH_FIT_RESIDUES = 11, 12
 MPC_CPACK_DICT_CARRIED, MPC_CPACK_DICT_PER_LINE = 0, 1     # mpc_create_cpack's dictionary_scope
 SYNTH_KINDS = {"zeros": 0, "random_u32": 1, "sine_f32": 2, "mixed": 3, "pointers_u64": 4}
 
@@ -92,6 +93,9 @@ def lib() -> C.CDLL:
             "mpc_create_cpack_blocks": ([C.c_uint, C.c_uint64, C.c_int, C.POINTER(H)], C.c_int),
             "mpc_cpack_blocks_restart": ([H], C.c_int),
             "mpc_cpack_block_lines": ([H, C.POINTER(C.c_uint64)], C.c_int),
+            "mpc_create_fit_pairs": ([C.c_uint, C.c_int, C.POINTER(H)], C.c_int),
+            "mpc_create_fit_residues": ([C.c_uint, C.c_void_p, C.c_int, C.POINTER(H)], C.c_int),
+            "mpc_fit_base_table": ([H, C.c_void_p, C.c_size_t], C.c_int),
             "mpc_destroy": ([H], None),
             "mpc_get_info": ([H, C.POINTER(Info)], C.c_int),
             "mpc_last_error": ([H], C.c_char_p),
@@ -152,6 +156,7 @@ EXPORTED_SYMBOLS = [
     "mpc_group_compress_batch_device", "mpc_group_compress_npy", "mpc_group_compress_gpgpusim_log", "mpc_group_sync",
     "mpc_create_pattern", "mpc_pattern_distinct_lines", "mpc_create_cpack", "mpc_create_pattern_evicting",
     "mpc_create_cpack_blocks", "mpc_cpack_blocks_restart", "mpc_cpack_block_lines",
+    "mpc_create_fit_pairs", "mpc_create_fit_residues", "mpc_fit_base_table",
 ]
 # The SC2 entry points of include/mpc_hip.h.  Kept apart from EXPORTED_SYMBOLS, which lists the names of the
 # header's lowercase-letter form (mpc_[a-z_]+) only; every one of both lists is exported by libmpc_hip.so.
@@ -218,7 +223,7 @@ def _totals(v, ratio=_ratio_or_zero) -> Dict:
 
 
 class _Evaluator:
-    """Common part of the seven evaluators: creates and owns one ``mpc_handle``."""
+    """Common part of the seven evaluators and the two Fit analyses: creates and owns one ``mpc_handle``."""
 
     def __init__(self, create: str, *args):
         """``create``: name of the library's create function; ``args``: its arguments in front of the handle."""
@@ -530,6 +535,56 @@ class CPACK(_Evaluator):
         """``CPACKResult`` (reference ``CPACK.h:28-96``): the totals, ``total_words`` and the six pattern counts."""
         v = self.stats_vector()
         return {"name": "C-Pack", **_totals(v), "total_words": int(v[3]), "counts": [int(x) for x in v[4:10]]}
+
+
+class _Fit(_Evaluator):
+    """Common part of the two Fit analyses: no per-line result."""
+
+    def compress_lines(self, lines: np.ndarray, want_sizes: bool = False, want_selected: bool = False):
+        """Host buffer [n, L] uint8; the counts accumulate in the handle.  Returns ``(None, None)``: an analysis has no
+        per-line result (asking for one raises ``MpcError``, the library's refusal)."""
+        return super().compress_lines(lines, want_sizes, want_selected)
+
+    @property
+    def kernel_form(self) -> str:
+        return (lib().mpc_kernel_form(self._h) or b"").decode()
+
+    def lines(self) -> int:
+        return int(self.stats_vector()[0])
+
+
+class FitPairs(_Fit):
+    """``mpc_create_fit_pairs``: for every byte pair (i, j) of the lines fed, how many lines have a residue
+    ``(line[i] - line[j]) & 255`` of bit length k (0 for a zero residue, else 1..8).  ``fit.fit_base_table`` picks the
+    BaseIndexTable of a DiffBase module from it.  line_size: 32, 64 or 128."""
+
+    def __init__(self, line_size: int, device: int = -1):
+        super().__init__("mpc_create_fit_pairs", line_size, device)
+
+    def table(self) -> np.ndarray:
+        """``uint64[L, L, 9]``: P[i][j][k]."""
+        L = self.line_size
+        return self.stats_vector()[3:].reshape(L, L, 9).copy()
+
+
+class FitResidues(_Fit):
+    """``mpc_create_fit_residues``: for every byte i how many lines have the residue ``(line[i] - line[base_table[i]]) &
+    255 == v``.  ``fit.fit_diff_table`` picks the DiffTable from it.  ``base_table``: L entries below L, any table."""
+
+    def __init__(self, line_size: int, base_table, device: int = -1):
+        base = np.ascontiguousarray(base_table)
+        if base.ndim != 1 or base.shape[0] != line_size or not np.issubdtype(base.dtype, np.integer) or \
+                (base.size and (base.min() < 0 or base.max() > 255)):
+            raise ValueError(f"base_table: {line_size} integers from 0 to 255")
+        base = base.astype(np.uint8)
+        super().__init__("mpc_create_fit_residues", line_size, base.ctypes.data, device)
+        out = np.zeros(self.line_size, dtype=np.uint8)
+        self._check(lib().mpc_fit_base_table(self._h, out.ctypes.data, out.size))
+        self.base_table = [int(b) for b in out]
+
+    def table(self) -> np.ndarray:
+        """``uint64[L, 256]``: V[i][v]."""
+        return self.stats_vector()[3:].reshape(self.line_size, 256).copy()
 
 
 class EvaluatorSet:

@@ -52,6 +52,7 @@ def lib_units(csrc: str = CSRC):
               (os.path.join(csrc, "mpc_pattern_evict.hip"), "pattern_evict.o", []),   # the Pattern analyser's evicting set
               (os.path.join(csrc, "mpc_cpack.hip"), "cpack.o", []),              # C-Pack with a per-line dictionary
               (os.path.join(csrc, "mpc_cpack_blocks.hip"), "cpack_blocks.o", []),   # ... with one per block of N lines
+              (os.path.join(csrc, "mpc_fit.hip"), "fit.o", []),                  # byte-pair and residue statistics for fit.py
               (os.path.join(csrc, "mpc_sizes.hip"), "sizes.o", []),              # size histograms and best-of
               (os.path.join(csrc, "mpc_capi.hip"), "capi.o", [])]
     return units

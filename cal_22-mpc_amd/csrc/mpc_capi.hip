@@ -19,6 +19,7 @@
 #include "mpc_sc2.h"
 #include "mpc_pattern.h"
 #include "mpc_sizes.h"
+#include "mpc_fit.h"
 #include "mpc_launch.h"
 
 // libmpc_hip_test.so (build.py, -DMPC_TESTING=1): route counters behind the raw statistics and a cap on the launch grid,
@@ -46,7 +47,7 @@ namespace {
 thread_local std::string g_create_error;
 
 // The ABI's algorithm numbers (mpc_info.algorithm) and, per algorithm, the facts that do not depend on a handle.
-enum class Algo { VPC, BDI, FPC, BPC, SC2, Pattern, CPack };
+enum class Algo { VPC, BDI, FPC, BPC, SC2, Pattern, CPack, Fit };
 
 struct AlgoFacts {
   const char *name;                        // in a group's form and error texts
@@ -68,6 +69,8 @@ constexpr AlgoFacts kAlgo[] = {
   {"PATTERN", "Pattern", MPC_PATTERN_RAW_LEN, 534, 10, MPC_PATH_PATTERN, 8, 8, MPC_MAX_LINE},
   // C-Pack with a per-line dictionary: 32-bit words (CPACK.cpp:14)
   {"CPACK", "C-Pack", MPC_CPACK_RAW_LEN, 10, 6, MPC_PATH_CPACK, 4, 4, MPC_MAX_LINE},
+  // the two Fit analyses: lengths, clusters and path depend on the line size and the analysis (create_fit); 32, 64 or 128 bytes
+  {"FIT", "Fit", 0, 0, 9, MPC_PATH_FIT_PAIRS, 32, 32, 128},
 };
 constexpr const AlgoFacts &facts(Algo a) { return kAlgo[(int)a]; }
 const char *algorithm_name(Algo a) { return facts(a).name; }
@@ -131,6 +134,11 @@ struct mpc_handle {
     bool recorded = false;
     std::string form;            // mpc_kernel_form
   } cpk;
+  // Fit (mpc_fit.h): which of the two analyses; the residue analysis's base table (its device copy is d_gtab)
+  struct {
+    bool residues = false;
+    std::vector<uint8_t> base;
+  } fit;
   std::vector<Stager *> fed_by;  // every stager that feeds this handle: its own, then those of the groups it is a member of (sc2_build)
   // size accounting (mpc_sizes.h): nothing of it exists before mpc_size_hist_enable
   struct {
@@ -359,11 +367,20 @@ int launch_sc2(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int
 int launch_pattern(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
 int launch_cpack_blocks(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
 
+const char *const kFitNoPerLine = "Fit: an analysis has no per-line result: size_bits_out and selected_out must be NULL";
+
 int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s)
 {
   if (n == 0) return MPC_OK;
   hipError_t e;
   switch (h->algorithm) {
+  case Algo::Fit:
+    if (d_sizes || d_sel) return set_err(h, MPC_E_INVAL, kFitNoPerLine);
+    if (h->fit.residues)
+      e = mpc_launch_fit_residues(d_lines, n, h->L, h->d_gtab, h->d_raw, grid_for(h, n, 1, mpc_fit_residues_wg_per_cu(h->L)), s);
+    else      // (persistent grids: the launchers size them down to the work of a short batch)
+      e = mpc_launch_fit_pairs(d_lines, n, h->L, h->d_raw, grid_for(h, n, 1, mpc_fit_pairs_wg_per_cu(h->L)), s);
+    break;
   case Algo::SC2: return launch_sc2(h, d_lines, n, d_sizes, d_sel, s);
   case Algo::Pattern: return launch_pattern(h, d_lines, n, d_sizes, d_sel, s);
   case Algo::CPack:
@@ -566,6 +583,26 @@ int pattern_status(mpc_handle *h)
 void derive_stats(const mpc_handle *h, const std::vector<u64> &raw, std::vector<u64> &vec)
 {
   switch (h->algorithm) {
+  case Algo::Fit: {
+    const u64 L = (u64)h->L, lines = raw[0];
+    vec[0] += lines;
+    if (h->fit.residues) {
+      for (u64 i = 0; i < L; i++)
+        for (u64 v = 0; v < 256; v++) vec[3 + i * 256 + v] += raw[1 + v * L + i];
+      return;
+    }
+    for (u64 i = 0; i < L; i++)
+      for (u64 j = 0; j < L; j++) {
+        u64 others = 0;
+        for (u64 k = 1; k <= MPC_FIT_PAIR_BINS; k++) {
+          const u64 c = raw[1 + (i * MPC_FIT_PAIR_BINS + (k - 1)) * L + j];
+          vec[3 + (i * L + j) * 9 + k] += c;
+          others += c;
+        }
+        vec[3 + (i * L + j) * 9] += lines - others;      // bin 0 is what the eight counted bins leave
+      }
+    return;
+  }
   case Algo::Pattern: {
     const u64 L = (u64)h->L;
     vec[0] += raw[MPC_PAT_LINES];
@@ -890,6 +927,43 @@ int create_failed(int rc, mpc_handle **out)
   return rc;
 }
 
+// The two Fit analyses.  base == nullptr: the pair table.  The refusals come before any device is touched.
+int create_fit(unsigned line_size, const uint8_t *base, int device, mpc_handle **out)
+{
+  if (!out) return MPC_E_INVAL;
+  *out = nullptr;
+  if (line_size != 32 && line_size != 64 && line_size != 128)
+    return set_err(nullptr, MPC_E_INVAL, "Fit: line size " + std::to_string(line_size) + " is not one of 32, 64 and 128 bytes");
+  for (unsigned i = 0; base && i < line_size; i++)
+    if (base[i] >= line_size)
+      return set_err(nullptr, MPC_E_INVAL, "Fit: base_table[" + std::to_string(i) + "] = " + std::to_string(base[i]) + " is not a byte of a " +
+                                               std::to_string(line_size) + "-byte line");
+  mpc_handle *h = new (std::nothrow) mpc_handle();
+  if (!h) return MPC_E_NOMEM;
+  h->algorithm = Algo::Fit;
+  h->L = (int)line_size;
+  h->fit.residues = base != nullptr;
+  h->raw_len = base ? mpc_fit_residues_raw_len(line_size) : mpc_fit_pairs_raw_len(line_size);
+  h->stats_len = base ? mpc_fit_residues_stats_len(line_size) : mpc_fit_pairs_stats_len(line_size);
+  int rc = pick_device(device, &h->device, &h->num_cus);
+  if (rc == MPC_OK && base) {
+    h->fit.base.assign(base, base + line_size);
+    if (hipMalloc((void **)&h->d_gtab, line_size) != hipSuccess) {
+      h->d_gtab = nullptr;
+      rc = set_err(nullptr, MPC_E_NOMEM, "Fit: hipMalloc of the base table failed");
+    } else if (hipMemcpy(h->d_gtab, base, line_size, hipMemcpyHostToDevice) != hipSuccess) {
+      rc = set_err(nullptr, MPC_E_NODEVICE, "Fit: hipMemcpy of the base table failed");
+    }
+  }
+  if (rc == MPC_OK) rc = finish_create(h);
+  if (rc != MPC_OK) {
+    mpc_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return MPC_OK;
+}
+
 uint32_t *g_sine_dev[16] = {nullptr};   // per device float32 sine period for mpc_synth_fill
 
 }  // namespace
@@ -957,6 +1031,23 @@ int mpc_create_cpack_blocks(unsigned line_size, uint64_t block_lines, int device
     g_create_error = "C-Pack: initialising the open block's dictionary failed";
     return create_failed(MPC_E_NODEVICE, out);
   }
+  return MPC_OK;
+}
+
+int mpc_create_fit_pairs(unsigned line_size, int device, mpc_handle **out) { return create_fit(line_size, nullptr, device, out); }
+
+int mpc_create_fit_residues(unsigned line_size, const uint8_t *base_table, int device, mpc_handle **out)
+{
+  if (!out) return MPC_E_INVAL;
+  *out = nullptr;
+  if (!base_table) return set_err(nullptr, MPC_E_INVAL, "Fit: base_table is NULL");
+  return create_fit(line_size, base_table, device, out);
+}
+
+int mpc_fit_base_table(const mpc_handle *h, uint8_t *out, size_t n)
+{
+  if (!h || !out || h->algorithm != Algo::Fit || !h->fit.residues || n < (size_t)h->L) return MPC_E_INVAL;
+  std::memcpy(out, h->fit.base.data(), (size_t)h->L);
   return MPC_OK;
 }
 
@@ -1185,10 +1276,10 @@ int mpc_get_info(const mpc_handle *h, mpc_info *info)
   info->algorithm = (int)h->algorithm;
   info->line_size = h->L;
   info->num_modules = vpc ? h->cfg.M : 0;
-  info->num_clusters = vpc ? h->cfg.M + 1 : facts(h->algorithm).clusters;
+  info->num_clusters = vpc ? h->cfg.M + 1 : h->fit.residues ? 256 : facts(h->algorithm).clusters;
   info->hist_bins = vpc ? h->cfg.hist_bins : 0;
   info->kernel_path = vpc && h->route.kernel == VpcKernel::Generic ? MPC_PATH_VPC_GENERIC : h->pat.evicting ? MPC_PATH_PATTERN_EVICTING
-                      : h->cpk.N ? MPC_PATH_CPACK_BLOCKS : facts(h->algorithm).path;
+                      : h->cpk.N ? MPC_PATH_CPACK_BLOCKS : h->fit.residues ? MPC_PATH_FIT_RESIDUES : facts(h->algorithm).path;
   info->device = h->device;
   info->stats_len = h->stats_len;
   return MPC_OK;
@@ -1230,6 +1321,7 @@ const char *mpc_kernel_form(const mpc_handle *h)
   if (h->algorithm == Algo::Pattern) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled, then the set passes" : "run-time loop, then the set passes";
   if (h->algorithm == Algo::CPack && h->cpk.N) return h->cpk.form.c_str();
   if (h->algorithm == Algo::CPack) return (h->L == 32 || h->L == 64 || h->L == 128) ? "unrolled" : "run-time loop";
+  if (h->algorithm == Algo::Fit) return h->fit.residues ? "one lane per byte" : "one lane per byte pair";
   if (h->algorithm != Algo::VPC) return "unrolled";
   if (h->route.kernel == VpcKernel::AtCreation && h->jit.from_cache) return "unrolled, compiled at creation (from the cache)";
   static const char *const form[] = {"unrolled", "unrolled, general layout", "unrolled, compiled at creation", "run-time loop", "generic"};
@@ -1246,6 +1338,7 @@ int mpc_compress_batch_device(mpc_handle *h, const void *d_lines, uint64_t n, ui
 {
   if (!h || (!d_lines && n)) return MPC_E_INVAL;
   if (((uintptr_t)d_lines) & 15u) return set_err(h, MPC_E_INVAL, "device line buffer must be 16-byte aligned");
+  if (h->algorithm == Algo::Fit && (d_sizes || d_sel)) return set_err(h, MPC_E_INVAL, kFitNoPerLine);
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)hip_stream;
   if (!accounts(h) || d_sizes) return launch_accounted(h, d_lines, n, d_sizes, d_sel, s);
@@ -1278,6 +1371,7 @@ int mpc_sync(mpc_handle *h)
 int mpc_compress_batch(mpc_handle *h, const uint8_t *lines, uint64_t n, uint16_t *sizes, int8_t *sel)
 {
   if (!h || (!lines && n)) return MPC_E_INVAL;
+  if (h->algorithm == Algo::Fit && (sizes || sel)) return set_err(h, MPC_E_INVAL, kFitNoPerLine);
   if (n == 0) return MPC_OK;
   return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, &sizes, &sel);   // (a group of one)
 }
@@ -1335,6 +1429,8 @@ int mpc_group_create(mpc_handle *const *members, size_t n, mpc_group **out)
     for (size_t j = 0; j < i; j++)
       if (members[j] == members[i])
         return group_err(nullptr, MPC_E_INVAL, "member " + std::to_string(i) + " repeats member " + std::to_string(j) + " (a handle is fed once)");
+    if (members[i]->algorithm == Algo::Fit)
+      return group_err(nullptr, MPC_E_INVAL, "Fit: member " + std::to_string(i) + " is an analysis handle, which a group does not take");
     if (members[i]->L != members[0]->L)
       return group_err(nullptr, MPC_E_INVAL, "members of different line sizes: member " + std::to_string(i) + " has " + std::to_string(members[i]->L) +
                                                  "-byte lines, member 0 " + std::to_string(members[0]->L));
@@ -1533,6 +1629,7 @@ int mpc_size_hist_enable(mpc_handle *h)
 {
   if (!h) return MPC_E_INVAL;
   if (h->acct.on) return MPC_OK;
+  if (h->algorithm == Algo::Fit) return set_err(h, MPC_E_INVAL, "Fit: an analysis has no per-line sizes to account");
   HIPCHK(h, hipSetDevice(h->device));
   if (h->algorithm == Algo::VPC) {
     // nothing to allocate: remember the statistics' histogram of the lines before this point

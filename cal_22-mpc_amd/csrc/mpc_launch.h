@@ -2,7 +2,7 @@
 //
 // The launchers have C linkage, so a declaration that drifted from its definition would still link and then misbehave.
 // This header is therefore included by the callers (mpc_capi.hip, mpc_jit.h) AND by the units that define the
-// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_sizes.hip, the host section of mpc_vpc_lane.hip):
+// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_fit.hip, mpc_sizes.hip, the host section of mpc_vpc_lane.hip):
 // the compiler sees declaration and definition together and refuses a mismatch.  Host code only -- the run-time
 // compiled source of mpc_jit.h (-DMPC_LANE_JIT) never sees it, and it is not one of the files that key the code
 // object cache.
@@ -86,6 +86,14 @@ hipError_t mpc_launch_cpack(const void *d_lines, unsigned long long n_lines, int
 #define MPC_CPACK_STATE_WORDS 32      /* 16 entries in ring order, the front, padding */
 hipError_t mpc_launch_cpack_blocks(const void *d_lines, unsigned long long n_lines, int L, unsigned long long block_lines, unsigned long long pos,
                                    uint16_t *d_sizes, int8_t *d_sel, unsigned long long *d_stats, const uint32_t *d_state, uint32_t *d_state_out,
+                                   int grid, hipStream_t stream);
+
+// mpc_fit.hip: the two Fit analyses (layouts: mpc_fit.h).  `grid` bounds the workgroups of a launch: num_cus x the
+// *_wg_per_cu of the line size.  d_base: the residue analysis's base table, L bytes on the device, every entry < L.
+int mpc_fit_pairs_wg_per_cu(int L);
+hipError_t mpc_launch_fit_pairs(const void *d_lines, unsigned long long n_lines, int L, unsigned long long *d_stats, int grid, hipStream_t stream);
+int mpc_fit_residues_wg_per_cu(int L);
+hipError_t mpc_launch_fit_residues(const void *d_lines, unsigned long long n_lines, int L, const uint8_t *d_base, unsigned long long *d_stats,
                                    int grid, hipStream_t stream);
 
 // mpc_sizes.hip

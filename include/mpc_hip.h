@@ -50,14 +50,16 @@ typedef struct mpc_handle mpc_handle;
 #define MPC_PATH_PATTERN      7
 #define MPC_PATH_CPACK        8  /* C-Pack with a per-line dictionary */
 #define MPC_PATH_CPACK_BLOCKS 10  /* mpc_create_cpack_blocks: C-Pack with a dictionary shared by blocks of N lines, one lane per block */
+#define MPC_PATH_FIT_PAIRS    11  /* mpc_create_fit_pairs: bit lengths of the byte-pair residues, one lane per pair */
+#define MPC_PATH_FIT_RESIDUES 12  /* mpc_create_fit_residues: residue histogram for a base table, one lane per byte */
 #define MPC_PATH_PATTERN_EVICTING 9  /* mpc_create_pattern_evicting: the analysis kernel of MPC_PATH_PATTERN, then the evicting set's passes */
 
 typedef struct {
   int32_t abi_version;
-  int32_t algorithm;        /* 0 = VPC, 1 = BDI, 2 = FPC, 3 = BPC, 4 = SC2, 5 = Pattern, 6 = C-Pack (per-line dictionary, or per block of lines: kernel_path) */
+  int32_t algorithm;        /* 0 = VPC, 1 = BDI, 2 = FPC, 3 = BPC, 4 = SC2, 5 = Pattern, 6 = C-Pack (per-line dictionary, or per block of lines: kernel_path), 7 = Fit (an analysis, pairs or residues: kernel_path) */
   int32_t line_size;        /* bytes per line (L) */
   int32_t num_modules;      /* VPC: M; BDI: 0 */
-  int32_t num_clusters;     /* VPC: M+1 (cluster -1 .. M-1); BDI: 9 states; FPC: 8 prefixes; BPC: 7 patterns; SC2: 2 (warm-up, table); Pattern: 10 states; C-Pack: 6 patterns */
+  int32_t num_clusters;     /* VPC: M+1 (cluster -1 .. M-1); BDI: 9 states; FPC: 8 prefixes; BPC: 7 patterns; SC2: 2 (warm-up, table); Pattern: 10 states; C-Pack: 6 patterns; Fit: 9 bit lengths (pairs) or 256 residues */
   int32_t hist_bins;        /* VPC: bins per cluster in the stats vector */
   int32_t kernel_path;      /* MPC_PATH_* */
   int32_t device;           /* HIP device ordinal the handle is bound to */
@@ -190,6 +192,20 @@ int mpc_create_cpack_blocks(unsigned line_size, uint64_t block_lines, int device
 int mpc_cpack_blocks_restart(mpc_handle *h);
 /* The block length the handle was created with.  MPC_E_INVAL for every other handle.                                   */
 int mpc_cpack_block_lines(const mpc_handle *h, uint64_t *n);
+/* Fit: the two analyses from which cal_22-mpc_amd/fit.py fits the BaseIndexTable and the DiffTable of a DiffBase module
+ * to a trace (no counterpart in the reference, which ships no configuration).  bitlen8(v) = 0 for v = 0, else the position
+ * of the highest set bit of v plus 1 (1..8); every residue is a uint8 difference mod 256 as in ResidueModule.cpp:34 (-1 is
+ * 255 and costs 8).  Ordinary handles for every ingestion and statistics call; all counters are uint64 sums over lines,
+ * so calls, shards and merged vectors add.  What an analysis does not have: a per-line result (non-NULL size_bits_out /
+ * selected_out), size accounting (mpc_size_hist_enable) and a place in a group (mpc_group_create) each return MPC_E_INVAL
+ * with a message that begins with "Fit".  line_size: 32, 64 or 128, checked before any device is touched.
+ * Pair table: P[i][j][k], i, j in [0, L), k in [0, 9) = lines with bitlen8((line[i] - line[j]) & 255) == k.             */
+int mpc_create_fit_pairs(unsigned line_size, int device, mpc_handle **out);
+/* Residue histogram for a base table: V[i][v] = lines with (line[i] - line[base_table[i]]) & 255 == v.  base_table: L
+ * entries, each < L (any table: forward references and base_table[i] == i included); copied.                          */
+int mpc_create_fit_residues(unsigned line_size, const uint8_t *base_table, int device, mpc_handle **out);
+/* The base table of an mpc_create_fit_residues handle (n >= L).  MPC_E_INVAL for every other handle.                  */
+int mpc_fit_base_table(const mpc_handle *h, uint8_t *out, size_t n);
 void mpc_destroy(mpc_handle *h);
 
 int mpc_get_info(const mpc_handle *h, mpc_info *info);
@@ -258,6 +274,8 @@ int mpc_sync(mpc_handle *h);
  *             [15..20] ExplicitCounts [21] lines that joined the set (an evicting handle: insertions) [22..277] SymbolCounts [278..533]
  *             SymbolCountsExceptAllZerosAllWordSame.  T = L x ([0] - [21]).  mpc_stats_reset clears the statistics,
  *             [21] included, and keeps the set: lines seen before the reset still count as seen.
+ * Fit pairs layout: [0] lines [1] 0 [2] 0 (an analysis, as Pattern) [3 + (i L + j) 9 + k] P[i][j][k]; length 3 + 9 L^2.
+ * Fit residues layout: [0] lines [1] 0 [2] 0 [3 + 256 i + v] V[i][v]; length 3 + 256 L.
  */
 int mpc_stats_len(const mpc_handle *h, uint64_t *len);
 int mpc_stats_get(mpc_handle *h, uint64_t *vec, size_t n);      /* syncs */
@@ -267,7 +285,8 @@ int mpc_stats_set(mpc_handle *h, const uint64_t *vec, size_t n);   /* = (after a
 /* Device-side exchange (multi-GPU without a host round trip).  The handle's device
  * accumulators ("raw" statistics: VPC [sum_r(K)] [sum_r2(K)] [histogram(K x B)], BDI
  * [Counts(9)] [compressed_bits], FPC [Counts(8)] [compressed_bits], BPC [Counts(7)] [TotalWords] [compressed_bits], SC2
- * [compressed_bits] [words_in_table], Pattern: the 531 sums of csrc/mpc_pattern.h, C-Pack [Counts(6)] [compressed_bits]) are plain uint64 sums, so ranks may all-reduce them
+ * [compressed_bits] [words_in_table], Pattern: the 531 sums of csrc/mpc_pattern.h, C-Pack [Counts(6)] [compressed_bits],
+ * Fit pairs [lines] [8 L^2 counts of bit lengths 1..8], Fit residues [lines] [256 L counts]: csrc/mpc_fit.h) are plain uint64 sums, so ranks may all-reduce them
  * directly: mpc_stats_copy_raw_device enqueues an asynchronous device-to-device copy of
  * the raw_len words into d_dst on hip_stream (after everything already enqueued there),
  * and mpc_stats_from_raw turns such an array -- on the host, e.g. after the all-reduce --

@@ -1774,7 +1774,22 @@ int mpc_config_describe(const char *json_text, char *out, size_t cap)
          "\", \"compiled\": \"" + std::string(!unrolled ? "" : r.kernel == VpcKernel::AtCreation ? "at creation" : "built in") +
          "\", \"general_layout\": \"" + std::string(unrolled && plan.params.gen_layout ? "yes" : "no") +
          "\", \"scan_order\": \"" + std::string(!fast ? "" : (plan.params.byte_major ? "byte-major" : "plane-major")) +
-         "\", \"modules\": [";
+         "\", \"needs\": [";
+    // the plan itself: the layouts a kernel compiled at creation is asked for, and per prediction module what the planned
+    // lane kernel reads and does for every byte (mpc::read_back_vpc_module; a fast plan only, whichever kernel the route picks)
+    static const char *const need_names[] = {"BM", "ANYROOT", "PLANES", "GATHER", "WSHIFT"};
+    bool first_need = true;
+    for (int b = 0; b < 5; b++)
+      if (plan.jit_needs & (1u << b)) {
+        s += std::string(first_need ? "\"" : ", \"") + need_names[b] + "\"";
+        first_need = false;
+      }
+    s += "], \"runtime_only\": " + std::to_string(plan.fast ? plan.params.runtime_only : 0) + ", \"modules\": [";
+    auto ints = [](const std::vector<int> &v) {
+      std::string a = "[";
+      for (size_t j = 0; j < v.size(); j++) a += (j ? "," : "") + std::to_string(v[j]);
+      return a + "]";
+    };
     for (int i = 0; i < cfg.M; i++) {
       const mpc::Module &m = cfg.modules[(size_t)i];
       s += (i ? ", " : "");
@@ -1782,7 +1797,16 @@ int mpc_config_describe(const char *json_text, char *out, size_t cap)
            ", \"cx\": " + (m.consecutive_xor ? "1" : "0") + ", \"table_size\": " + std::to_string(m.table_size) + ", \"shifts\": [";
       for (size_t j = 0; j < m.weight.size(); j++)
         s += (j ? "," : "") + std::to_string(m.pred_kind == mpc::PRED_WEIGHT && (int)j != m.root ? mpc::weight_shift(m.weight[j]) : 0);
-      s += "]}";
+      s += "]";
+      if (plan.fast && i >= cfg.start) {
+        mpc::VpcModuleRead rb;
+        mpc::read_back_vpc_module(plan, i - cfg.start, rb);
+        s += ", \"kernel_base\": " + ints(rb.base);
+        if (!rb.shift.empty()) s += ", \"kernel_shift\": " + ints(rb.shift);
+        if (!rb.diff.empty()) s += ", \"kernel_diff\": " + ints(rb.diff);
+        if (*rb.base_form) s += ", \"base_form\": \"" + std::string(rb.base_form) + "\"";
+      }
+      s += "}";
     }
     s += "]}";
   }

@@ -384,6 +384,9 @@ inline void build_vpc_plan(const VpcConfig &cfg, VpcPlan &plan)
     // c1 split into its low-7-bit and MSB parts (lane-per-line kernel, WeightBase residue)
     for (size_t w = 0; w < c1.size(); w++) plan.tab.push_back(c1[w] & 0x7f7f7f7fu);
     for (size_t w = 0; w < c1.size(); w++) plan.tab.push_back(c1[w] & 0x80808080u);
+    // a two-words-back table with more than two shift distances gives the periodic form up (below) -- and its bytes from word 2
+    // on, whose selectors above only name the byte inside the source word, lie outside the window: gathered
+    if (stride2 && wgen) gather = true;
     f.gather = gather ? 1 : 0;
     if (gather || wgen) stride2 = false;
     // periodic tables: words 1.. all use "the same byte of the previous word" with identical masks /
@@ -458,6 +461,108 @@ inline void build_vpc_plan(const VpcConfig &cfg, VpcPlan &plan)
   while (plan.tab.size() % 4) plan.tab.push_back(0);
   if (plan.tab.empty()) plan.tab.assign(4, 0);
   P.tab_words = (int32_t)plan.tab.size();
+}
+
+// ---------------------------------------------------------------------------
+// the plan, read back
+// ---------------------------------------------------------------------------
+
+// What mpc_jit.h writes into MPC_JIT_BASES / MPC_JIT_SHIFTS for byte i of prediction module q (the generic-path tables
+// of VpcPlan::gtab): the base byte of a gathered module (-1: none), the shift distance of a module with more than two
+// (99: the predicted byte is 0).
+inline int jit_base_entry(const VpcPlan &plan, int q, int i)
+{
+  const MpcVpcParams &P = plan.params;
+  const bool has = P.fm[q].gather && i != P.fm[q].root;
+  return has ? (int)plan.gtab[(size_t)(P.gm[q].off_base + i)] : -1;
+}
+
+inline int jit_shift_entry(const VpcPlan &plan, int q, int i)
+{
+  const MpcVpcParams &P = plan.params;
+  int v = 99;
+  if (P.fm[q].wgen && i != P.fm[q].root) {
+    v = (int)(signed char)plan.gtab[(size_t)(P.gm[q].off_shift + i)];
+    if (v >= 8 || v <= -8) v = 99;
+  }
+  return v;
+}
+
+// What the lane kernel of a fast plan does for every byte of prediction module q, decoded from the kernel's own inputs
+// (plan.tab at fm[q].tab_off, the fields of fm[q], the two functions above) the way window_base, lane_gather_base,
+// window_predict, window_residue and lane_weight_general of mpc_vpc_lane.hip use them -- never from the configuration.
+//   base[i]   the byte of the line the prediction starts from; -1: none (the constant 0); -2: a selector the planner
+//             never writes
+//   shift[i]  WeightBase: the one shift distance of the byte (left positive); 99: the predicted byte is always 0;
+//             98: both shift classes act on the byte; 97: a mask that does not keep exactly the bits the shift leaves
+//   diff[i]   DiffBase: the constant added, as uint8; -1: a constant whose halves overlap
+struct VpcModuleRead {
+  const char *base_form = "";      // "windowed" | "previous word" | "two words back" | "gathered"; "" for OneBase / ConsecutiveBase
+  std::vector<int> base, shift, diff;
+};
+
+inline void read_back_vpc_module(const VpcPlan &plan, int q, VpcModuleRead &out)
+{
+  const MpcVpcParams &P = plan.params;
+  const MpcFastModule &f = P.fm[q];
+  const int L = P.L, W = L / 4;
+  out.base.assign((size_t)L, -1);
+  out.shift.clear();
+  out.diff.clear();
+  out.base_form = "";
+  if (f.kind == MPC_FK_ONEBASE || f.kind == MPC_FK_CONSEC) return;
+  // (the gathered base and the general shifts exist only in a kernel compiled with the switch)
+  const bool gather = (plan.jit_needs & JIT_GATHER) && f.gather, wgen = (plan.jit_needs & JIT_WSHIFT) && f.wgen;
+  const int D = f.prev_word;
+  out.base_form = gather ? "gathered" : D == 2 ? "two words back" : D == 1 ? "previous word" : "windowed";
+  const uint32_t *t = plan.tab.data() + f.tab_off;
+  const bool weight = f.kind != MPC_FK_DIFF;
+  (weight ? out.shift : out.diff).assign((size_t)L, 0);
+  auto keeps = [](int s) { return (s >= 8 || s <= -8) ? 0u : s >= 0 ? ((0xffu << s) & 0xffu) : (0xffu >> -s); };
+  for (int i = 0; i < L; i++) {
+    const int w = i / 4, k = i % 4;
+    const int te = D == 2 ? (w < 2 ? w : 2 + (w & 1)) : (D == 1 ? (w ? 1 : 0) : w);      // table entry of word w
+    auto byte_of = [&](int row) { return (t[(size_t)(row * W + te)] >> (8 * k)) & 0xffu; };
+    if (gather) {
+      out.base[(size_t)i] = jit_base_entry(plan, q, i);
+    } else if (D && w >= D) {
+      out.base[(size_t)i] = i - 4 * D;
+    } else {
+      const uint32_t s = (t[(size_t)w] >> (8 * k)) & 0xffu;     // v_perm_b32: 0..3 the previous word (0 in word 0), 4..7 the own, 0x0c zero
+      out.base[(size_t)i] = s == 0x0cu ? -1 : s < 4 ? (w ? 4 * (w - 1) + (int)s : -1) : s < 8 ? 4 * w + (int)s - 4 : -2;
+    }
+    if (!weight) {
+      const uint32_t lo = byte_of(1), hi = byte_of(2);
+      out.diff[(size_t)i] = ((lo & 0x80u) || (hi & 0x7fu)) ? -1 : (int)(lo | hi);
+    } else if (wgen) {
+      out.shift[(size_t)i] = jit_shift_entry(plan, q, i);
+    } else {
+      uint32_t m1, m2;
+      int s1, s2;
+      bool bad = false;
+      if (f.kind == MPC_FK_WEIGHT) {
+        // class 1 unshifted, its mask pre-split into the low seven bits and the MSB; class 2 shifted right, MSB clear
+        const uint32_t lo = byte_of(3), hi = byte_of(4);
+        bad = (lo & 0x80u) || (hi & 0x7fu);
+        m1 = lo | hi;
+        m2 = byte_of(2);
+        s1 = 0;
+        s2 = -f.rs2;
+        if (m2 && s2 == 0) bad = true;
+      } else {
+        m1 = byte_of(1);
+        m2 = byte_of(2);
+        s1 = f.ls1 - f.rs1;
+        s2 = f.ls2 - f.rs2;
+        if ((m1 && f.ls1 && f.rs1) || (m2 && f.ls2 && f.rs2)) bad = true;
+      }
+      int s = 99;
+      if (m1 && m2) s = 98;
+      else if (m1) s = (bad || m1 != keeps(s1)) ? 97 : s1;
+      else if (m2) s = (bad || m2 != keeps(s2)) ? 97 : s2;
+      out.shift[(size_t)i] = s;
+    }
+  }
 }
 
 }  // namespace mpc

@@ -202,10 +202,7 @@ inline std::string bases_of(const mpc::VpcPlan &plan)
   std::string s;
   for (int q = 0; q < P.n_pred; q++) {
     s += q ? ", {" : "{";
-    for (int i = 0; i < P.L; i++) {
-      const bool has = P.fm[q].gather && i != P.fm[q].root;
-      s += (i ? "," : "") + std::to_string(has ? (int)plan.gtab[(size_t)(P.gm[q].off_base + i)] : -1);
-    }
+    for (int i = 0; i < P.L; i++) s += (i ? "," : "") + std::to_string(mpc::jit_base_entry(plan, q, i));
     s += "}";
   }
   return s;
@@ -218,14 +215,7 @@ inline std::string shifts_of(const mpc::VpcPlan &plan)
   std::string s;
   for (int q = 0; q < P.n_pred; q++) {
     s += q ? ", {" : "{";
-    for (int i = 0; i < P.L; i++) {
-      int v = 99;
-      if (P.fm[q].wgen && i != P.fm[q].root) {
-        v = (int)(signed char)plan.gtab[(size_t)(P.gm[q].off_shift + i)];
-        if (v >= 8 || v <= -8) v = 99;
-      }
-      s += (i ? "," : "") + std::to_string(v);
-    }
+    for (int i = 0; i < P.L; i++) s += (i ? "," : "") + std::to_string(mpc::jit_shift_entry(plan, q, i));
     s += "}";
   }
   return s;

@@ -302,7 +302,9 @@ int mpc_stats_reset(mpc_handle *h);
  * Parses and validates a VPC configuration exactly as mpc_create_vpc does and
  * writes a JSON description (line size, modules, id bits, which kernel path the
  * configuration maps to and why, whether the module sequence has an unrolled
- * instantiation or runs in the fast kernel's run-time module loop) into out[cap].  Touches no HIP API.  Returns
+ * instantiation or runs in the fast kernel's run-time module loop; "needs" / "runtime_only" and, per prediction module of a
+ * fast plan, "kernel_base" / "kernel_shift" / "kernel_diff" / "base_form": what the planned kernel reads and does for every
+ * byte, decoded from the kernel's own tables -- some 2 KiB per module at 128-byte lines) into out[cap].  Touches no HIP API.  Returns
  * 0, or the negative code mpc_create_vpc would return ({"error": ...}).     */
 int mpc_config_describe(const char *config_json_text, char *out, size_t cap);
 

@@ -453,7 +453,9 @@ def test_vpc_sequences_compiled_at_creation(mpc, oracle, configs, traces, L, tmp
     # predicted word is assembled from the table as compile-time constants -- alone, with a gathered base, roots and truncation
     w4 = [[1.0, 0.5, 0.25, 2.0][i % 4] for i in range(L)]
     w19 = [float(2.0 ** ((i * 7) % 19 - 9)) for i in range(L)]
+    # (two words back with four shift distances: words 2.. lie outside the window, so the base is gathered as well)
     for mods in ([az, aws, configs.weight_base(L, prev4, w4, 0, True), configs.one_base(L, 0, False)],
+                 [az, aws, configs.weight_base(L, prev8, w4, 0, True), configs.one_base(L, 0, False)],
                  [az, configs.weight_base(L, prev16, w19, 6, False), configs.consecutive_base(L, 0, True), configs.weight_base(L, prev1, w4, 0, True)],
                  [az, aws, configs.diff_base(L, prev4, diff, 2, True, trunc(5 * L)), configs.weight_base(L, prev4, w19, 0, False, trunc(5 * L))]):
         cfg = configs.make_config(L, mods)

@@ -135,12 +135,18 @@ def test_config_reader_under_sanitizers(tmp_path, configs):
         p = tmp_path / f"bad{i}.json"
         p.write_text(bad)
         files.append(str(p))
+    # the named cases of the planner's decision table (tests/vpc_plan_cases.py): planned and read back
+    import vpc_plan_cases
+    damaged = len(files)
+    for name, make in vpc_plan_cases.NAMED.items():
+        files.append(configs.write_config(make(), str(tmp_path / f"plan_{name}.json")))
     r = subprocess.run([probe] + files, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = r.stdout.strip().split("\n")
     assert len(out) == len(files)
     assert all(": rc 0 " in line and "path fast" in line for line in out[:3])
-    assert sum(": rc -" in line for line in out[3:]) > 60
+    assert sum(": rc -" in line for line in out[3:damaged]) > 60
+    assert all(": rc 0 " in line and " read " in line for line in out[damaged:]), [line for line in out[damaged:] if ": rc 0 " not in line][:3]
 
 
 def test_oracle_under_sanitizers(tmp_path):

@@ -24,6 +24,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPC_HIP_LIB") or os.path.join(HERE, "libmpc_hip.so")   # override: development builds only
 
 MPC_SIZE_BINS = 4096          # bins of a size histogram (include/mpc_hip_sizes.h)
+MPC_CLASS_COUNT, MPC_CLASS_ROW = 256, 10      # a class table is uint64[256][10] (include/mpc_hip_classes.h)
+MPC_CLASS_TABLE_LEN = MPC_CLASS_COUNT * MPC_CLASS_ROW
+MPC_CLASS_BEST = -1           # mpc_group_class_stats_get: the best-of's table
+CLASS_LOG_FIELDS = {None: 0, "kernel": 1, "rw": 2, "mftype": 3}      # MPC_CLASS_LOG_*
 MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2, MPC_PATH_PATTERN = 1, 2, 3, 4, 5, 6, 7
 MPC_PATH_PATTERN_EVICTING = 9
 MPC_PATH_CPACK = 8
@@ -136,6 +140,20 @@ def lib() -> C.CDLL:
             "mpc_group_best_reset": ([H], C.c_int),
             "mpc_size_sectors": ([C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
                                   C.POINTER(C.c_double)], C.c_int),
+            "mpc_class_stats_enable": ([H, C.c_uint], C.c_int),
+            "mpc_class_stats_get": ([H, C.c_void_p, C.c_size_t], C.c_int),
+            "mpc_class_stats_merge": ([H, C.c_void_p, C.c_size_t], C.c_int),
+            "mpc_class_sector_bytes": ([H, C.POINTER(C.c_uint)], C.c_int),
+            "mpc_compress_batch_classed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "mpc_compress_batch_device_classed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "mpc_class_log_field": ([H, C.c_int], C.c_int),
+            "mpc_group_class_stats_enable": ([H, C.c_uint], C.c_int),
+            "mpc_group_class_stats_get": ([H, C.c_int, C.c_void_p, C.c_size_t], C.c_int),
+            "mpc_group_compress_batch_classed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int),
+            "mpc_group_compress_batch_device_classed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                         C.c_void_p], C.c_int),
+            "mpc_group_class_log_field": ([H, C.c_int], C.c_int),
+            "mpc_group_class_from_member": ([H, C.c_int], C.c_int),
         }
         for name, (args, res) in sigs.items():
             fn = getattr(L, name)
@@ -164,6 +182,11 @@ EXPORTED_SC2_SYMBOLS = ["mpc_create_sc2", "mpc_sc2_sampling_lines", "mpc_sc2_cod
 # The size accounting entry points, declared in include/mpc_hip_sizes.h (which mpc_hip.h includes).
 EXPORTED_SIZE_SYMBOLS = ["mpc_size_hist_enable", "mpc_size_hist_get", "mpc_group_best_enable", "mpc_group_best_get",
                          "mpc_group_best_reset", "mpc_size_sectors"]
+# The per-class accounting entry points, declared in include/mpc_hip_classes.h (which mpc_hip.h includes).
+EXPORTED_CLASS_SYMBOLS = ["mpc_class_stats_enable", "mpc_class_stats_get", "mpc_class_stats_merge", "mpc_class_sector_bytes",
+                          "mpc_compress_batch_classed", "mpc_compress_batch_device_classed", "mpc_class_log_field",
+                          "mpc_group_class_stats_enable", "mpc_group_class_stats_get", "mpc_group_compress_batch_classed",
+                          "mpc_group_compress_batch_device_classed", "mpc_group_class_log_field", "mpc_group_class_from_member"]
 
 
 def gpgpusim_log_line_size(path: str) -> int:
@@ -203,6 +226,31 @@ def _as_lines(lines, line_size: int) -> np.ndarray:
     if lines.ndim != 2 or lines.shape[1] != line_size:
         raise ValueError(f"expected [n, {line_size}] uint8")
     return lines
+
+
+def _as_classes(classes, n: int) -> np.ndarray:
+    """The ``classes=`` argument of ``compress_lines``: one uint8 per line, C-contiguous."""
+    arr = np.asarray(classes)
+    if arr.shape != (n,) or not (np.issubdtype(arr.dtype, np.integer) or arr.dtype == np.bool_):
+        raise ValueError(f"classes: {n} integers from 0 to 255, one per line")
+    if arr.size and (int(arr.min()) < 0 or int(arr.max()) > 255):
+        raise ValueError("classes: a class is an integer from 0 to 255")
+    return np.ascontiguousarray(arr, dtype=np.uint8)
+
+
+def _class_log_field(field) -> int:
+    if field not in CLASS_LOG_FIELDS:
+        raise ValueError(f"class_log_field: one of 'kernel', 'rw', 'mftype' or None, not {field!r}")
+    return CLASS_LOG_FIELDS[field]
+
+
+def class_table_view(table: np.ndarray, line_size: int, sector_bytes: int) -> Dict:
+    """A class table ``uint64[256 * MPC_CLASS_ROW]`` as a dict of arrays over the 256 classes: ``lines``, ``bits`` (the
+    sum of the compressed sizes) and ``sectors[256, S]`` (column k - 1: lines that occupy k sectors), S =
+    ceil(line_size / sector_bytes)."""
+    t = np.asarray(table, dtype=np.uint64).reshape(MPC_CLASS_COUNT, MPC_CLASS_ROW)
+    S = -(-int(line_size) // int(sector_bytes))
+    return {"lines": t[:, 0].copy(), "bits": t[:, 1].copy(), "sectors": t[:, 2:2 + S].copy()}
 
 
 def _ratio(original, compressed, lines) -> float:
@@ -258,21 +306,33 @@ class _Evaluator:
 
     # -- hot path -----------------------------------------------------------
     def compress_lines(self, lines: np.ndarray, want_sizes: bool = True,
-                       want_selected: bool = True) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+                       want_selected: bool = True, *, classes=None) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
         """Host buffer [n, L] uint8 -> (size_bits uint16[n], selected int8[n]); staged
-        through the pinned double buffers.  Statistics accumulate in the handle."""
+        through the pinned double buffers.  Statistics accumulate in the handle.
+        ``classes``: one class (0..255) per line for ``class_stats()``; needs ``enable_class_stats()``."""
         lines = _as_lines(lines, self.line_size)
         n = lines.shape[0]
         sizes = np.empty(n, dtype=np.uint16) if want_sizes else None
         sel = np.empty(n, dtype=np.int8) if want_selected else None
+        if classes is not None:
+            cls = _as_classes(classes, n)
+            self._check(lib().mpc_compress_batch_classed(self._h, lines.ctypes.data, n, cls.ctypes.data,
+                                                         sizes.ctypes.data if want_sizes else None,
+                                                         sel.ctypes.data if want_selected else None))
+            return sizes, sel
         self._check(lib().mpc_compress_batch(self._h, lines.ctypes.data, n,
                                              sizes.ctypes.data if want_sizes else None,
                                              sel.ctypes.data if want_selected else None))
         return sizes, sel
 
     def compress_device(self, d_lines: int, n_lines: int, d_sizes: int = 0, d_selected: int = 0,
-                        stream: int = 0) -> None:
-        """Device-resident lines (raw pointers, e.g. ``tensor.data_ptr()``); asynchronous."""
+                        stream: int = 0, *, classes: int = 0) -> None:
+        """Device-resident lines (raw pointers, e.g. ``tensor.data_ptr()``); asynchronous.
+        ``classes``: raw device pointer to ``n_lines`` uint8 classes; needs ``enable_class_stats()``."""
+        if classes:
+            self._check(lib().mpc_compress_batch_device_classed(self._h, d_lines, n_lines, classes, d_sizes or None,
+                                                                d_selected or None, stream or None))
+            return
         self._check(lib().mpc_compress_batch_device(self._h, d_lines, n_lines, d_sizes or None,
                                                     d_selected or None, stream or None))
 
@@ -339,6 +399,41 @@ class _Evaluator:
         bins = np.zeros(MPC_SIZE_BINS, dtype=np.uint64)
         self._check(lib().mpc_size_hist_get(self._h, bins.ctypes.data, MPC_SIZE_BINS))
         return bins
+
+    # -- per-class accounting -------------------------------------------------
+    def enable_class_stats(self, sector_bytes: int = 32) -> None:
+        """Sum, from now on, lines, compressed bits and sector counts per class of a line (``mpc_class_stats_enable``);
+        idempotent for the same ``sector_bytes``.  Lines of calls without ``classes=`` count in class 0."""
+        sector_bytes = int(sector_bytes)
+        if not 0 <= sector_bytes < 1 << 32:
+            raise MpcError(-22, "mpc_class_stats_enable: sector_bytes is unsigned")
+        self._check(lib().mpc_class_stats_enable(self._h, sector_bytes))
+
+    def class_sector_bytes(self) -> int:
+        b = C.c_uint()
+        self._check(lib().mpc_class_sector_bytes(self._h, C.byref(b)))
+        return int(b.value)
+
+    def class_table(self) -> np.ndarray:
+        """The raw table ``uint64[256, MPC_CLASS_ROW]`` (``mpc_class_stats_get``): what ``class_stats_merge`` takes."""
+        t = np.zeros(MPC_CLASS_TABLE_LEN, dtype=np.uint64)
+        self._check(lib().mpc_class_stats_get(self._h, t.ctypes.data, t.size))
+        return t.reshape(MPC_CLASS_COUNT, MPC_CLASS_ROW)
+
+    def class_stats(self) -> Dict:
+        """Arrays over the 256 classes since accounting was switched on or the last ``reset()``: ``lines``, ``bits``,
+        ``sectors[256, S]``.  Raises ``MpcError`` (MPC_E_INVAL) when accounting is off."""
+        return class_table_view(self.class_table(), self.line_size, self.class_sector_bytes())
+
+    def class_stats_merge(self, table: np.ndarray) -> None:
+        """Add another evaluator's ``class_table()`` (a shard's)."""
+        table = np.ascontiguousarray(table, dtype=np.uint64)
+        self._check(lib().mpc_class_stats_merge(self._h, table.ctypes.data, table.size))
+
+    def class_log_field(self, field) -> None:
+        """Which field of a ``.log`` record is the class of its line in ``compress_gpgpusim_log``: ``"kernel"`` (the
+        kernel id), ``"rw"`` (0 = read, 1 = write), ``"mftype"`` or ``None`` (class 0)."""
+        self._check(lib().mpc_class_log_field(self._h, _class_log_field(field)))
 
 
 class VPC(_Evaluator):
@@ -628,24 +723,31 @@ class EvaluatorSet:
     def _pointers(self, values):
         return (C.c_void_p * len(self.members))(*values)
 
-    def compress_lines(self, lines: np.ndarray, want_sizes: bool = True, want_selected: bool = True):
-        """Host buffer [n, L] uint8 -> one ``(size_bits, selected)`` pair per member, in member order."""
+    def compress_lines(self, lines: np.ndarray, want_sizes: bool = True, want_selected: bool = True, *, classes=None):
+        """Host buffer [n, L] uint8 -> one ``(size_bits, selected)`` pair per member, in member order.
+        ``classes``: one class (0..255) per line for ``class_stats()``; needs ``enable_class_stats()``."""
         lines = _as_lines(lines, self.line_size)
         n = lines.shape[0]
         sizes = [np.empty(n, dtype=np.uint16) if want_sizes else None for _ in self.members]
         sel = [np.empty(n, dtype=np.int8) if want_selected else None for _ in self.members]
-        self._check(lib().mpc_group_compress_batch(
-            self._g, lines.ctypes.data, n,
-            self._pointers([a.ctypes.data for a in sizes]) if want_sizes else None,
-            self._pointers([a.ctypes.data for a in sel]) if want_selected else None))
+        p_sizes = self._pointers([a.ctypes.data for a in sizes]) if want_sizes else None
+        p_sel = self._pointers([a.ctypes.data for a in sel]) if want_selected else None
+        if classes is not None:
+            cls = _as_classes(classes, n)
+            self._check(lib().mpc_group_compress_batch_classed(self._g, lines.ctypes.data, n, cls.ctypes.data, p_sizes, p_sel))
+        else:
+            self._check(lib().mpc_group_compress_batch(self._g, lines.ctypes.data, n, p_sizes, p_sel))
         return list(zip(sizes, sel))
 
-    def compress_device(self, d_lines: int, n_lines: int, d_sizes=None, d_selected=None, stream: int = 0) -> None:
-        """Device-resident lines; ``d_sizes`` / ``d_selected``: one raw device pointer (or 0 / None) per member."""
-        self._check(lib().mpc_group_compress_batch_device(
-            self._g, d_lines, n_lines,
-            self._pointers([p or None for p in d_sizes]) if d_sizes is not None else None,
-            self._pointers([p or None for p in d_selected]) if d_selected is not None else None, stream or None))
+    def compress_device(self, d_lines: int, n_lines: int, d_sizes=None, d_selected=None, stream: int = 0, *, classes: int = 0) -> None:
+        """Device-resident lines; ``d_sizes`` / ``d_selected``: one raw device pointer (or 0 / None) per member.
+        ``classes``: raw device pointer to ``n_lines`` uint8 classes; needs ``enable_class_stats()``."""
+        p_sizes = self._pointers([p or None for p in d_sizes]) if d_sizes is not None else None
+        p_sel = self._pointers([p or None for p in d_selected]) if d_selected is not None else None
+        if classes:
+            self._check(lib().mpc_group_compress_batch_device_classed(self._g, d_lines, n_lines, classes, p_sizes, p_sel, stream or None))
+        else:
+            self._check(lib().mpc_group_compress_batch_device(self._g, d_lines, n_lines, p_sizes, p_sel, stream or None))
 
     def compress_npy(self, path: str, first_row: int = 0, n_rows: int = (1 << 62), skip_last_row: bool = True) -> int:
         done = C.c_uint64()
@@ -681,6 +783,43 @@ class EvaluatorSet:
 
     def reset_best(self) -> None:
         self._check(lib().mpc_group_best_reset(self._g))
+
+    # -- per-class accounting ----------------------------------------------------
+    def enable_class_stats(self, sector_bytes: int = 32) -> None:
+        """``enable_class_stats`` for every member; with ``enable_best()`` (before or after) also a table of the
+        per-line smallest size.  Idempotent for the same ``sector_bytes``."""
+        sector_bytes = int(sector_bytes)
+        if not 0 <= sector_bytes < 1 << 32:
+            raise MpcError(-22, "mpc_group_class_stats_enable: sector_bytes is unsigned")
+        self._check(lib().mpc_group_class_stats_enable(self._g, sector_bytes))
+        self._class_sector_bytes = sector_bytes
+
+    def class_table(self, member: int) -> np.ndarray:
+        """The raw table ``uint64[256, MPC_CLASS_ROW]`` of member ``member`` or, with ``MPC_CLASS_BEST``, of the best-of."""
+        t = np.zeros(MPC_CLASS_TABLE_LEN, dtype=np.uint64)
+        self._check(lib().mpc_group_class_stats_get(self._g, int(member), t.ctypes.data, t.size))
+        return t.reshape(MPC_CLASS_COUNT, MPC_CLASS_ROW)
+
+    def class_stats(self) -> Dict:
+        """``{0: ..., 1: ..., "best": ...}``: one entry per member, in member order, and -- while the best-of is on --
+        ``"best"``; each as ``_Evaluator.class_stats()`` returns it."""
+        sb = getattr(self, "_class_sector_bytes", None)
+        if sb is None:
+            self._check(lib().mpc_group_class_stats_get(self._g, 0, None, 0))      # (raises: accounting is off)
+        out = {i: class_table_view(self.class_table(i), self.line_size, sb) for i in range(len(self.members))}
+        t = np.zeros(MPC_CLASS_TABLE_LEN, dtype=np.uint64)
+        if lib().mpc_group_class_stats_get(self._g, MPC_CLASS_BEST, t.ctypes.data, t.size) == 0:
+            out["best"] = class_table_view(t, self.line_size, sb)
+        return out
+
+    def class_log_field(self, field) -> None:
+        """``_Evaluator.class_log_field`` for ``compress_gpgpusim_log`` of the set."""
+        self._check(lib().mpc_group_class_log_field(self._g, _class_log_field(field)))
+
+    def class_from_member(self, member: Optional[int]) -> None:
+        """The class of a line is member ``member``'s ``selected`` + 1 (``mpc_group_class_from_member``): for a VPC
+        member 0 = uncompressed, k + 1 = module k's cluster; for a BDI member the state + 1.  ``None`` switches it off."""
+        self._check(lib().mpc_group_class_from_member(self._g, -1 if member is None else int(member)))
 
 
 def size_sectors(bins, line_size: int, sector_bytes: int = 32) -> Dict:

@@ -19,6 +19,7 @@
 #include "mpc_sc2.h"
 #include "mpc_pattern.h"
 #include "mpc_sizes.h"
+#include "mpc_classes.h"
 #include "mpc_fit.h"
 #include "mpc_launch.h"
 
@@ -32,8 +33,8 @@ constexpr size_t kTestWords = kRouteWords + (MPC_STAMPS ? MPC_STAMP_WORDS : 0); 
 
 typedef unsigned long long u64;
 
-// Size accounting on mpc_compress_batch_device without a sizes array of the caller's: the batch is evaluated in pieces of
-// this many lines, each evaluator launch followed by the accounting pass over a scratch array (8 MiB per member).
+// Size or class accounting on mpc_compress_batch_device without a sizes array of the caller's: the batch is evaluated in
+// pieces of this many lines, each evaluator launch followed by the accounting passes over ONE scratch array (8 MiB per member).
 constexpr u64 kAccountLines = 4ull << 20;
 
 #include "mpc_jit.h"
@@ -145,10 +146,17 @@ struct mpc_handle {
     bool on = false;
     u64 *d_hist = nullptr;             // [MPC_SIZE_BINS]; not for VPC, whose histogram is in its statistics
     std::vector<u64> vpc_base;         // VPC: that histogram when accounting was switched on (only later lines count)
-    uint16_t *d_scratch = nullptr;     // [kAccountLines] sizes of a piece of a device batch
+    uint16_t *d_scratch = nullptr;     // [kAccountLines] sizes of a piece of a device batch (class accounting reads the same array)
     hipEvent_t scratch_done = nullptr; // behind the last pass that read the scratch, whichever stream that was
     bool recorded = false;
   } acct;
+  // per-class accounting (mpc_classes.h): nothing of it exists before mpc_class_stats_enable
+  struct {
+    bool on = false;
+    unsigned sector_bytes = 0;
+    u64 *d_tab = nullptr;              // [MPC_CLASS_TABLE_LEN]
+    std::vector<u64> extra;            // merged-in tables
+  } cls;
   std::string error;
 };
 
@@ -166,6 +174,15 @@ struct mpc_group {
   // device batches with accounting: per member the scratch sizes of a piece (null until needed), the pointers of the piece
   std::vector<uint16_t *> d_scratch, piece_sizes;
   std::vector<int8_t *> piece_sel;
+  // per-class accounting of the group (mpc_classes.h): the members' tables are their handles'
+  struct {
+    bool on = false;
+    unsigned sector_bytes = 0;
+    u64 *d_best = nullptr;             // [MPC_CLASS_TABLE_LEN] of the per-line minimum; exists while this and the best-of are both on
+    int from_member = -1;              // the class of a line is this member's selected + 1 (-1: the caller's classes or a .log field)
+    int log_field = MPC_CLASS_LOG_NONE;
+    int8_t *d_scratch_sel = nullptr;   // [kAccountLines] that member's selected values of a piece of a device batch
+  } cls;
   hipEvent_t scratch_done = nullptr;
   bool recorded = false;
   std::string form, error;
@@ -191,14 +208,15 @@ int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t 
 int pattern_status(mpc_handle *h);
 int group_launch(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, hipStream_t s);
 int group_members_status(mpc_group *g);
-int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s);
-int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, hipStream_t s);
+int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, const uint8_t *d_classes, hipStream_t s);
+int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes,
+                           hipStream_t s);
 
 Sink sink_of(mpc_handle *h)
 {
   return {h,
-          [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, hipStream_t s) {
-            return launch_accounted(static_cast<mpc_handle *>(c), d, n, ds ? ds[0] : nullptr, dl ? dl[0] : nullptr, s);
+          [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, const uint8_t *dc, hipStream_t s) {
+            return launch_accounted(static_cast<mpc_handle *>(c), d, n, ds ? ds[0] : nullptr, dl ? dl[0] : nullptr, dc, s);
           },
           [](void *c, int code, const std::string &msg) { return set_err(static_cast<mpc_handle *>(c), code, msg); },
           [](void *c) { return pattern_status(static_cast<mpc_handle *>(c)); }};
@@ -207,8 +225,8 @@ Sink sink_of(mpc_handle *h)
 Sink sink_of(mpc_group *g)
 {
   return {g,
-          [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, hipStream_t s) {
-            return group_launch_accounted(static_cast<mpc_group *>(c), d, n, ds, dl, s);
+          [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, const uint8_t *dc, hipStream_t s) {
+            return group_launch_accounted(static_cast<mpc_group *>(c), d, n, ds, dl, dc, s);
           },
           [](void *c, int code, const std::string &msg) { return group_err(static_cast<mpc_group *>(c), code, msg); },
           [](void *c) { return group_members_status(static_cast<mpc_group *>(c)); }};
@@ -795,13 +813,20 @@ bool accounts(const mpc_handle *h) { return h->acct.on && h->algorithm != Algo::
 
 bool in_best(const mpc_group *g, int i) { return g->best.on && std::find(g->best.set.begin(), g->best.set.end(), i) != g->best.set.end(); }
 
+// a handle whose sizes are wanted on the device, asked for by the caller or not
+bool needs_sizes(const mpc_handle *h) { return accounts(h) || h->cls.on; }
+
 // ... a member whose sizes a group needs on the device, asked for by the caller or not
-bool group_accounts(const mpc_group *g, int i) { return accounts(g->m[(size_t)i]) || in_best(g, i); }
+bool group_accounts(const mpc_group *g, int i) { return needs_sizes(g->m[(size_t)i]) || in_best(g, i); }
 
 // (a handle's accounting may have been switched on since the group's last call)
 void group_refresh(mpc_group *g)
 {
-  for (int i = 0; i < (int)g->m.size(); i++) g->stage.account[(size_t)i] = group_accounts(g, i) ? 1 : 0;
+  for (int i = 0; i < (int)g->m.size(); i++) {
+    g->stage.account[(size_t)i] = group_accounts(g, i) ? 1 : 0;
+    g->stage.need_sel[(size_t)i] = g->cls.from_member == i ? 1 : 0;
+  }
+  g->stage.log_field = (g->cls.on && g->cls.from_member < 0) ? g->cls.log_field : MPC_CLASS_LOG_NONE;
 }
 
 hipError_t sizes_pass(const mpc_handle *h, const MpcSizesArgs &A, u64 n, hipStream_t s)
@@ -820,13 +845,43 @@ int account(mpc_handle *h, const uint16_t *d_sizes, u64 n, hipStream_t s)
   return MPC_OK;
 }
 
-// a staged or in-place chunk of a handle: the stager has asked for the sizes of a handle that accounts
-int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, hipStream_t s)
+// the per-class pass (mpc_classes.h) behind the evaluators' launches of a chunk
+hipError_t classes_pass(const mpc_handle *h, const MpcClassArgs &A, u64 n, hipStream_t s)
 {
-  const int rc = launch(h, d_lines, n, d_sizes, d_sel, s);
-  if (rc != MPC_OK || n == 0 || !accounts(h)) return rc;
+  return mpc_launch_classes(&A, n, grid_for(h, n / 8 + 1, 256, mpc_classes_wg_per_cu(&A)), s);
+}
+
+void class_sectors(MpcClassArgs &A, unsigned L, unsigned sector_bytes)
+{
+  A.sector_bits = 8u * sector_bytes;
+  A.max_sectors = (L + sector_bytes - 1) / sector_bytes;
+}
+
+// the refusals of mpc_class_stats_enable that need no device
+const char *class_sector_refusal(unsigned L, unsigned sector_bytes)
+{
+  if (sector_bytes == 0 || sector_bytes > L) return "class accounting: sector_bytes must be 1 .. line_size";
+  if ((L + sector_bytes - 1) / sector_bytes > MPC_CLASS_MAX_SECTORS) return "class accounting: a line of more than 8 sectors (sector_bytes is too small for the line size)";
+  return nullptr;
+}
+
+// a staged or in-place chunk of a handle: the stager has asked for the sizes of a handle that accounts
+int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, const uint8_t *d_classes, hipStream_t s)
+{
+  int rc = launch(h, d_lines, n, d_sizes, d_sel, s);
+  if (rc != MPC_OK || n == 0 || !needs_sizes(h)) return rc;
   if (!d_sizes) return set_err(h, MPC_E_INVAL, "size accounting: the chunk has no sizes array");
-  return account(h, d_sizes, n, s);
+  if (accounts(h)) rc = account(h, d_sizes, n, s);
+  if (rc != MPC_OK || !h->cls.on) return rc;
+  MpcClassArgs A{};
+  A.m = 1;
+  A.sizes[0] = d_sizes;
+  A.table[0] = h->cls.d_tab;
+  A.classes = d_classes;
+  class_sectors(A, (unsigned)h->L, h->cls.sector_bytes);
+  const hipError_t e = classes_pass(h, A, n, s);
+  if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch (class accounting): ") + hipGetErrorString(e));
+  return MPC_OK;
 }
 
 // The members' sizes of one chunk (one pointer per member, non-null for every member that group_accounts): first the
@@ -864,17 +919,74 @@ int group_account(mpc_group *g, uint16_t *const *d_sizes, u64 n, hipStream_t s)
   return A.m ? pass(A) : MPC_OK;
 }
 
-int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, hipStream_t s)
+// The per-class tables of one chunk, behind every member's launch and the size pass: the best-of set in one launch
+// (the minimum's table, with the tables of its members), then the other members, MPC_SIZES_MAX arrays a launch.
+int group_class_account(mpc_group *g, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes, u64 n, hipStream_t s)
 {
-  const int rc = group_launch(g, d_lines, n, d_sizes, d_sel, s);
+  const mpc_handle *h0 = g->m[0];
+  MpcClassArgs base{};
+  unsigned sb = 0;
+  for (const mpc_handle *h : g->m) {
+    if (!h->cls.on) continue;
+    if (sb && h->cls.sector_bytes != sb)
+      return group_err(g, MPC_E_INVAL, "class accounting: the members of a group count with different sector_bytes (" + std::to_string(sb) + " and " +
+                                           std::to_string(h->cls.sector_bytes) + ")");
+    sb = h->cls.sector_bytes;
+  }
+  if (!sb) return MPC_OK;
+  class_sectors(base, (unsigned)g->stage.L, sb);
+  base.classes = d_classes;
+  if (g->cls.from_member >= 0) {
+    if (!d_sel || !d_sel[g->cls.from_member])
+      return group_err(g, MPC_E_INVAL, "class accounting: the chunk has no selected array for member " + std::to_string(g->cls.from_member));
+    base.classes = reinterpret_cast<const uint8_t *>(d_sel[g->cls.from_member]);
+    base.class_bias = 1;
+  }
+  auto pass = [&](const MpcClassArgs &A) {
+    const hipError_t e = classes_pass(h0, A, n, s);
+    return e == hipSuccess ? MPC_OK : group_err(g, MPC_E_HIP, std::string("kernel launch (class accounting): ") + hipGetErrorString(e));
+  };
+  const bool with_best = g->best.on && g->cls.d_best;
+  if (with_best) {
+    MpcClassArgs A = base;
+    for (int i : g->best.set) {
+      A.sizes[A.m] = d_sizes[i];
+      A.table[A.m] = g->m[(size_t)i]->cls.on ? g->m[(size_t)i]->cls.d_tab : nullptr;
+      A.m++;
+    }
+    A.best = g->cls.d_best;
+    const int rc = pass(A);
+    if (rc != MPC_OK) return rc;
+  }
+  MpcClassArgs A = base;
+  for (int i = 0; i < (int)g->m.size(); i++) {
+    if (!g->m[(size_t)i]->cls.on || (with_best && in_best(g, i))) continue;
+    A.sizes[A.m] = d_sizes[i];
+    A.table[A.m] = g->m[(size_t)i]->cls.d_tab;
+    if (++A.m == MPC_SIZES_MAX) {
+      const int rc = pass(A);
+      if (rc != MPC_OK) return rc;
+      A = base;
+    }
+  }
+  return A.m ? pass(A) : MPC_OK;
+}
+
+int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes,
+                           hipStream_t s)
+{
+  int rc = group_launch(g, d_lines, n, d_sizes, d_sel, s);
   if (rc != MPC_OK || n == 0) return rc;
-  bool any = false;
+  bool any = false, sizes = false;
   for (int i = 0; i < (int)g->m.size(); i++) {
     if (!group_accounts(g, i)) continue;
     if (!d_sizes || !d_sizes[i]) return group_err(g, MPC_E_INVAL, "size accounting: the chunk has no sizes array for member " + std::to_string(i));
     any = true;
+    sizes = sizes || accounts(g->m[(size_t)i]) || in_best(g, i);
   }
-  return any ? group_account(g, d_sizes, n, s) : MPC_OK;
+  if (!any) return MPC_OK;
+  if (sizes) rc = group_account(g, d_sizes, n, s);
+  return rc == MPC_OK ? group_class_account(g, d_sizes, d_sel, d_classes, n, s) : rc;
 }
 
 // VPC: the size histogram is the sum over the clusters of the histogram in the raw statistics, clipped into MPC_SIZE_BINS bins
@@ -963,6 +1075,26 @@ int create_fit(unsigned line_size, const uint8_t *base, int device, mpc_handle *
   *out = h;
   return MPC_OK;
 }
+
+// the class table of the per-line minimum exists while the group's class accounting and its best-of are both on
+int group_class_best_ensure(mpc_group *g)
+{
+  if (!g->cls.on || !g->best.on || g->cls.d_best) return MPC_OK;
+  HIPCHK(g, hipSetDevice(g->stage.device));
+  if (hipMalloc((void **)&g->cls.d_best, MPC_CLASS_TABLE_LEN * sizeof(u64)) != hipSuccess) {
+    g->cls.d_best = nullptr;
+    return group_err(g, MPC_E_NOMEM, "hipMalloc(class table of the best-of) failed");
+  }
+  HIPCHK(g, hipMemset(g->cls.d_best, 0, MPC_CLASS_TABLE_LEN * sizeof(u64)));
+  HIPCHK(g, hipDeviceSynchronize());   // (the kernels run on non-blocking streams)
+  return MPC_OK;
+}
+
+const char *const kClassesOff = "class accounting is not switched on for this handle (mpc_class_stats_enable)";
+const char *const kGroupClassesOff = "class accounting is not switched on for this group (mpc_group_class_stats_enable)";
+const char *const kClassTableLen = "a class table has MPC_CLASS_TABLE_LEN (256 x 10 = 2560) entries";
+
+bool class_log_field_ok(int field) { return field >= MPC_CLASS_LOG_NONE && field <= MPC_CLASS_LOG_MFTYPE; }
 
 uint32_t *g_sine_dev[16] = {nullptr};   // per device float32 sine period for mpc_synth_fill
 
@@ -1265,6 +1397,7 @@ void mpc_destroy(mpc_handle *h)
   if (h->acct.d_hist) (void)hipFree(h->acct.d_hist);
   if (h->acct.d_scratch) (void)hipFree(h->acct.d_scratch);
   if (h->acct.scratch_done) (void)hipEventDestroy(h->acct.scratch_done);
+  if (h->cls.d_tab) (void)hipFree(h->cls.d_tab);
   delete h;
 }
 
@@ -1333,15 +1466,16 @@ const char *mpc_path_reason(const mpc_handle *h)
   return (h && h->algorithm == Algo::VPC) ? h->route.why_generic.c_str() : "";
 }
 
-int mpc_compress_batch_device(mpc_handle *h, const void *d_lines, uint64_t n, uint16_t *d_sizes, int8_t *d_sel,
-                              void *hip_stream)
+// mpc_compress_batch_device and its classed twin (d_classes: null for class 0)
+static int batch_device(mpc_handle *h, const void *d_lines, uint64_t n, const uint8_t *d_classes, uint16_t *d_sizes, int8_t *d_sel,
+                        void *hip_stream)
 {
   if (!h || (!d_lines && n)) return MPC_E_INVAL;
   if (((uintptr_t)d_lines) & 15u) return set_err(h, MPC_E_INVAL, "device line buffer must be 16-byte aligned");
   if (h->algorithm == Algo::Fit && (d_sizes || d_sel)) return set_err(h, MPC_E_INVAL, kFitNoPerLine);
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  if (!accounts(h) || d_sizes) return launch_accounted(h, d_lines, n, d_sizes, d_sel, s);
+  if (!needs_sizes(h) || d_sizes) return launch_accounted(h, d_lines, n, d_sizes, d_sel, d_classes, s);
   // accounting without a sizes array of the caller's: pieces of kAccountLines lines over the handle's scratch array
   if (!h->acct.d_scratch) {
     HIPCHK(h, hipMalloc((void **)&h->acct.d_scratch, kAccountLines * sizeof(uint16_t)));
@@ -1350,12 +1484,19 @@ int mpc_compress_batch_device(mpc_handle *h, const void *d_lines, uint64_t n, ui
   if (h->acct.recorded) HIPCHK(h, hipStreamWaitEvent(s, h->acct.scratch_done, 0));
   for (u64 at = 0; at < n; at += kAccountLines) {
     const u64 take = std::min<u64>(n - at, kAccountLines);
-    const int rc = launch_accounted(h, static_cast<const uint8_t *>(d_lines) + at * (u64)h->L, take, h->acct.d_scratch, d_sel ? d_sel + at : nullptr, s);
+    const int rc = launch_accounted(h, static_cast<const uint8_t *>(d_lines) + at * (u64)h->L, take, h->acct.d_scratch, d_sel ? d_sel + at : nullptr,
+                                    d_classes ? d_classes + at : nullptr, s);
     if (rc != MPC_OK) return rc;
   }
   HIPCHK(h, hipEventRecord(h->acct.scratch_done, s));
   h->acct.recorded = true;
   return MPC_OK;
+}
+
+int mpc_compress_batch_device(mpc_handle *h, const void *d_lines, uint64_t n, uint16_t *d_sizes, int8_t *d_sel,
+                              void *hip_stream)
+{
+  return batch_device(h, d_lines, n, nullptr, d_sizes, d_sel, hip_stream);
 }
 
 int mpc_sync(mpc_handle *h)
@@ -1373,7 +1514,7 @@ int mpc_compress_batch(mpc_handle *h, const uint8_t *lines, uint64_t n, uint16_t
   if (!h || (!lines && n)) return MPC_E_INVAL;
   if (h->algorithm == Algo::Fit && (sizes || sel)) return set_err(h, MPC_E_INVAL, kFitNoPerLine);
   if (n == 0) return MPC_OK;
-  return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, &sizes, &sel);   // (a group of one)
+  return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, nullptr, &sizes, &sel);   // (a group of one)
 }
 
 int mpc_npy_shape(const char *path, uint64_t *rows, uint64_t *cols)
@@ -1464,6 +1605,8 @@ void mpc_group_destroy(mpc_group *g)
   for (mpc_handle *h : g->m) h->fed_by.erase(std::remove(h->fed_by.begin(), h->fed_by.end(), &g->stage), h->fed_by.end());
   mpcstage::destroy(g->stage);
   if (g->best.d_acc) (void)hipFree(g->best.d_acc);
+  if (g->cls.d_best) (void)hipFree(g->cls.d_best);
+  if (g->cls.d_scratch_sel) (void)hipFree(g->cls.d_scratch_sel);
   for (uint16_t *p : g->d_scratch) if (p) (void)hipFree(p);
   if (g->scratch_done) (void)hipEventDestroy(g->scratch_done);
   delete g;
@@ -1478,11 +1621,12 @@ int mpc_group_compress_batch(mpc_group *g, const uint8_t *lines, uint64_t n, uin
   if (!g || (!lines && n)) return MPC_E_INVAL;
   if (n == 0) return MPC_OK;
   group_refresh(g);
-  return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, sizes, sel);
+  return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, nullptr, sizes, sel);
 }
 
-int mpc_group_compress_batch_device(mpc_group *g, const void *d_lines, uint64_t n, uint16_t *const *d_sizes, int8_t *const *d_sel,
-                                    void *hip_stream)
+// mpc_group_compress_batch_device and its classed twin (d_classes: null for class 0, or the classes come from a member)
+static int group_batch_device(mpc_group *g, const void *d_lines, uint64_t n, const uint8_t *d_classes, uint16_t *const *d_sizes,
+                              int8_t *const *d_sel, void *hip_stream)
 {
   if (!g || (!d_lines && n)) return MPC_E_INVAL;
   if (((uintptr_t)d_lines) & 15u) return group_err(g, MPC_E_INVAL, "device line buffer must be 16-byte aligned");
@@ -1495,8 +1639,10 @@ int mpc_group_compress_batch_device(mpc_group *g, const void *d_lines, uint64_t 
     any = true;
     scratch = scratch || !(d_sizes && d_sizes[i]);
   }
+  const int fm = g->cls.from_member;       // its selected values are needed on the device, asked for or not
+  const bool sel_scratch = fm >= 0 && !(d_sel && d_sel[fm]);
   if (!any) return group_launch(g, d_lines, n, d_sizes, d_sel, s);
-  if (!scratch) return group_launch_accounted(g, d_lines, n, d_sizes, d_sel, s);
+  if (!scratch && !sel_scratch) return group_launch_accounted(g, d_lines, n, d_sizes, d_sel, d_classes, s);
   // accounting of a member without a sizes array of the caller's: pieces of kAccountLines lines, that member's sizes in a scratch array
   g->d_scratch.resize(nm, nullptr);
   g->piece_sizes.assign(nm, nullptr);
@@ -1504,20 +1650,28 @@ int mpc_group_compress_batch_device(mpc_group *g, const void *d_lines, uint64_t 
   for (size_t i = 0; i < nm; i++)
     if (group_accounts(g, (int)i) && !(d_sizes && d_sizes[i]) && !g->d_scratch[i])
       HIPCHK(g, hipMalloc((void **)&g->d_scratch[i], kAccountLines * sizeof(uint16_t)));
+  if (sel_scratch && !g->cls.d_scratch_sel) HIPCHK(g, hipMalloc((void **)&g->cls.d_scratch_sel, kAccountLines));
   if (!g->scratch_done) HIPCHK(g, hipEventCreateWithFlags(&g->scratch_done, hipEventDisableTiming));
   if (g->recorded) HIPCHK(g, hipStreamWaitEvent(s, g->scratch_done, 0));
   for (u64 at = 0; at < n; at += kAccountLines) {
     const u64 take = std::min<u64>(n - at, kAccountLines);
     for (size_t i = 0; i < nm; i++) {
       g->piece_sizes[i] = (d_sizes && d_sizes[i]) ? d_sizes[i] + at : group_accounts(g, (int)i) ? g->d_scratch[i] : nullptr;
-      g->piece_sel[i] = (d_sel && d_sel[i]) ? d_sel[i] + at : nullptr;
+      g->piece_sel[i] = (d_sel && d_sel[i]) ? d_sel[i] + at : (sel_scratch && (int)i == fm) ? g->cls.d_scratch_sel : nullptr;
     }
-    const int rc = group_launch_accounted(g, static_cast<const uint8_t *>(d_lines) + at * (u64)g->stage.L, take, g->piece_sizes.data(), g->piece_sel.data(), s);
+    const int rc = group_launch_accounted(g, static_cast<const uint8_t *>(d_lines) + at * (u64)g->stage.L, take, g->piece_sizes.data(), g->piece_sel.data(),
+                                          d_classes ? d_classes + at : nullptr, s);
     if (rc != MPC_OK) return rc;
   }
   HIPCHK(g, hipEventRecord(g->scratch_done, s));
   g->recorded = true;
   return MPC_OK;
+}
+
+int mpc_group_compress_batch_device(mpc_group *g, const void *d_lines, uint64_t n, uint16_t *const *d_sizes, int8_t *const *d_sel,
+                                    void *hip_stream)
+{
+  return group_batch_device(g, d_lines, n, nullptr, d_sizes, d_sel, hip_stream);
 }
 
 int mpc_group_compress_npy(mpc_group *g, const char *path, uint64_t first_row, uint64_t n_rows, int skip_last_row, uint64_t *rows_done)
@@ -1610,6 +1764,8 @@ int mpc_stats_reset(mpc_handle *h)
   HIPCHK(h, hipMemset(h->d_raw, 0, (h->raw_len + kTestWords) * sizeof(u64)));
   if (h->acct.d_hist) HIPCHK(h, hipMemset(h->acct.d_hist, 0, MPC_SIZE_BINS * sizeof(u64)));
   if (h->acct.on) h->acct.vpc_base.assign(h->acct.vpc_base.size(), 0);
+  if (h->cls.d_tab) HIPCHK(h, hipMemset(h->cls.d_tab, 0, MPC_CLASS_TABLE_LEN * sizeof(u64)));
+  h->cls.extra.assign(h->cls.extra.size(), 0);
   h->extra.assign(h->stats_len, 0);
   h->sc2.lines = h->sc2.warm = 0;     // SC2: the table and the line counter stay (C-Pack in blocks: the open block and the position in it)
   return MPC_OK;
@@ -1695,7 +1851,7 @@ int mpc_group_best_enable(mpc_group *g)
   HIPCHK(g, hipDeviceSynchronize());   // (the kernels run on non-blocking streams)
   g->best.set = std::move(set);
   g->best.on = true;
-  return MPC_OK;
+  return group_class_best_ensure(g);
 }
 
 int mpc_group_best_get(mpc_group *g, uint64_t *bins, size_t n, uint64_t *wins, size_t n_members, uint64_t *best_bits, uint64_t *lines)
@@ -1727,6 +1883,7 @@ int mpc_group_best_reset(mpc_group *g)
   const int rc = mpc_group_sync(g);
   if (rc != MPC_OK) return rc;
   HIPCHK(g, hipMemset(g->best.d_acc, 0, MPC_SIZES_BEST_LEN * sizeof(u64)));
+  if (g->cls.d_best) HIPCHK(g, hipMemset(g->cls.d_best, 0, MPC_CLASS_TABLE_LEN * sizeof(u64)));
   return MPC_OK;
 }
 
@@ -1747,6 +1904,171 @@ int mpc_size_sectors(const uint64_t *bins, size_t n, unsigned line_size, unsigne
   if (classes) std::memcpy(classes, cls.data(), most * sizeof(u64));
   if (total_sectors) *total_sectors = sectors;
   if (ratio) *ratio = sectors ? (double)(lines * most) / (double)sectors : 0.0;
+  return MPC_OK;
+}
+
+// ---- per-class accounting (include/mpc_hip_classes.h) ----------------------------
+int mpc_class_stats_enable(mpc_handle *h, unsigned sector_bytes)
+{
+  if (!h) return MPC_E_INVAL;
+  if (h->algorithm == Algo::Fit) return set_err(h, MPC_E_INVAL, "Fit: an analysis has no per-line sizes to account");
+  if (const char *why = class_sector_refusal((unsigned)h->L, sector_bytes)) return set_err(h, MPC_E_INVAL, why);
+  if (h->cls.on) {
+    if (h->cls.sector_bytes == sector_bytes) return MPC_OK;
+    return set_err(h, MPC_E_INVAL, "class accounting is already on with sector_bytes " + std::to_string(h->cls.sector_bytes));
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (hipMalloc((void **)&h->cls.d_tab, MPC_CLASS_TABLE_LEN * sizeof(u64)) != hipSuccess) {
+    h->cls.d_tab = nullptr;
+    return set_err(h, MPC_E_NOMEM, "hipMalloc(class table) failed");
+  }
+  HIPCHK(h, hipMemset(h->cls.d_tab, 0, MPC_CLASS_TABLE_LEN * sizeof(u64)));
+  HIPCHK(h, hipDeviceSynchronize());   // (the kernels run on non-blocking streams)
+  h->cls.extra.assign(MPC_CLASS_TABLE_LEN, 0);
+  h->cls.sector_bytes = sector_bytes;
+  h->stage.account[0] = 1;
+  h->cls.on = true;
+  return MPC_OK;
+}
+
+int mpc_class_stats_get(mpc_handle *h, uint64_t *table, size_t n)
+{
+  if (!h) return MPC_E_INVAL;
+  if (!h->cls.on) return set_err(h, MPC_E_INVAL, kClassesOff);
+  if (!table || n != MPC_CLASS_TABLE_LEN) return set_err(h, MPC_E_INVAL, kClassTableLen);
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = sync_all(h);
+  if (rc != MPC_OK) return rc;
+  HIPCHK(h, hipDeviceSynchronize());   // callers may have used their own streams
+  rc = pattern_status(h);
+  if (rc != MPC_OK) return rc;
+  HIPCHK(h, hipMemcpy(table, h->cls.d_tab, MPC_CLASS_TABLE_LEN * sizeof(u64), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; i++) table[i] += h->cls.extra[i];
+  return MPC_OK;
+}
+
+int mpc_class_stats_merge(mpc_handle *h, const uint64_t *table, size_t n)
+{
+  if (!h) return MPC_E_INVAL;
+  if (!h->cls.on) return set_err(h, MPC_E_INVAL, kClassesOff);
+  if (!table || n != MPC_CLASS_TABLE_LEN) return set_err(h, MPC_E_INVAL, kClassTableLen);
+  for (size_t i = 0; i < n; i++) h->cls.extra[i] += table[i];
+  return MPC_OK;
+}
+
+int mpc_class_sector_bytes(const mpc_handle *h, unsigned *sector_bytes)
+{
+  if (!h || !sector_bytes || !h->cls.on) return MPC_E_INVAL;
+  *sector_bytes = h->cls.sector_bytes;
+  return MPC_OK;
+}
+
+int mpc_compress_batch_classed(mpc_handle *h, const uint8_t *lines, uint64_t n, const uint8_t *classes, uint16_t *sizes, int8_t *sel)
+{
+  if (!h || (!lines && n)) return MPC_E_INVAL;
+  if (!h->cls.on) return set_err(h, MPC_E_INVAL, kClassesOff);
+  if (n == 0) return MPC_OK;
+  return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, classes, &sizes, &sel);
+}
+
+int mpc_compress_batch_device_classed(mpc_handle *h, const void *d_lines, uint64_t n, const uint8_t *d_classes, uint16_t *d_sizes, int8_t *d_sel,
+                                      void *hip_stream)
+{
+  if (!h) return MPC_E_INVAL;
+  if (!h->cls.on) return set_err(h, MPC_E_INVAL, kClassesOff);
+  return batch_device(h, d_lines, n, d_classes, d_sizes, d_sel, hip_stream);
+}
+
+int mpc_class_log_field(mpc_handle *h, int field)
+{
+  if (!h) return MPC_E_INVAL;
+  if (!class_log_field_ok(field)) return set_err(h, MPC_E_INVAL, "class accounting: the .log field is one of MPC_CLASS_LOG_NONE, _KERNEL, _RW, _MFTYPE (0 .. 3)");
+  if (!h->cls.on) return set_err(h, MPC_E_INVAL, kClassesOff);
+  h->stage.log_field = field;
+  return MPC_OK;
+}
+
+int mpc_group_class_stats_enable(mpc_group *g, unsigned sector_bytes)
+{
+  if (!g) return MPC_E_INVAL;
+  if (const char *why = class_sector_refusal((unsigned)g->stage.L, sector_bytes)) return group_err(g, MPC_E_INVAL, why);
+  // (nothing is switched on unless every member can be)
+  for (size_t i = 0; i < g->m.size(); i++)
+    if (g->m[i]->cls.on && g->m[i]->cls.sector_bytes != sector_bytes)
+      return group_err(g, MPC_E_INVAL, "class accounting: member " + std::to_string(i) + " already counts with sector_bytes " +
+                                           std::to_string(g->m[i]->cls.sector_bytes));
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const int rc = mpc_class_stats_enable(g->m[i], sector_bytes);
+    if (rc != MPC_OK) return group_err(g, rc, "member " + std::to_string(i) + " (" + algorithm_name(g->m[i]->algorithm) + "): " + g->m[i]->error);
+  }
+  g->cls.sector_bytes = sector_bytes;
+  g->cls.on = true;
+  return group_class_best_ensure(g);
+}
+
+int mpc_group_class_stats_get(mpc_group *g, int member, uint64_t *table, size_t n)
+{
+  if (!g) return MPC_E_INVAL;
+  if (!g->cls.on) return group_err(g, MPC_E_INVAL, kGroupClassesOff);
+  if (!table || n != MPC_CLASS_TABLE_LEN) return group_err(g, MPC_E_INVAL, kClassTableLen);
+  if (member != MPC_CLASS_BEST && (member < 0 || member >= (int)g->m.size()))
+    return group_err(g, MPC_E_INVAL, "class accounting: member " + std::to_string(member) + " is not a member of the group or MPC_CLASS_BEST");
+  if (member == MPC_CLASS_BEST && !g->cls.d_best) return group_err(g, MPC_E_INVAL, "best-of is not switched on for this group (mpc_group_best_enable)");
+  int rc = mpc_group_sync(g);
+  if (rc != MPC_OK) return rc;
+  if (member == MPC_CLASS_BEST) {
+    HIPCHK(g, hipMemcpy(table, g->cls.d_best, MPC_CLASS_TABLE_LEN * sizeof(u64), hipMemcpyDeviceToHost));
+    return MPC_OK;
+  }
+  mpc_handle *h = g->m[(size_t)member];
+  rc = mpc_class_stats_get(h, table, n);
+  return rc == MPC_OK ? rc : group_err(g, rc, "member " + std::to_string(member) + " (" + algorithm_name(h->algorithm) + "): " + h->error);
+}
+
+int mpc_group_compress_batch_classed(mpc_group *g, const uint8_t *lines, uint64_t n, const uint8_t *classes, uint16_t *const *sizes,
+                                     int8_t *const *sel)
+{
+  if (!g || (!lines && n)) return MPC_E_INVAL;
+  if (!g->cls.on) return group_err(g, MPC_E_INVAL, kGroupClassesOff);
+  if (classes && g->cls.from_member >= 0)
+    return group_err(g, MPC_E_INVAL, "class accounting: the classes come from member " + std::to_string(g->cls.from_member) + ", the call must not bring its own");
+  if (n == 0) return MPC_OK;
+  group_refresh(g);
+  return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, classes, sizes, sel);
+}
+
+int mpc_group_compress_batch_device_classed(mpc_group *g, const void *d_lines, uint64_t n, const uint8_t *d_classes, uint16_t *const *d_sizes,
+                                            int8_t *const *d_sel, void *hip_stream)
+{
+  if (!g) return MPC_E_INVAL;
+  if (!g->cls.on) return group_err(g, MPC_E_INVAL, kGroupClassesOff);
+  if (d_classes && g->cls.from_member >= 0)
+    return group_err(g, MPC_E_INVAL, "class accounting: the classes come from member " + std::to_string(g->cls.from_member) + ", the call must not bring its own");
+  return group_batch_device(g, d_lines, n, d_classes, d_sizes, d_sel, hip_stream);
+}
+
+int mpc_group_class_log_field(mpc_group *g, int field)
+{
+  if (!g) return MPC_E_INVAL;
+  if (!class_log_field_ok(field)) return group_err(g, MPC_E_INVAL, "class accounting: the .log field is one of MPC_CLASS_LOG_NONE, _KERNEL, _RW, _MFTYPE (0 .. 3)");
+  if (!g->cls.on) return group_err(g, MPC_E_INVAL, kGroupClassesOff);
+  g->cls.log_field = field;
+  return MPC_OK;
+}
+
+int mpc_group_class_from_member(mpc_group *g, int member)
+{
+  if (!g) return MPC_E_INVAL;
+  if (!g->cls.on) return group_err(g, MPC_E_INVAL, kGroupClassesOff);
+  if (member < -1 || member >= (int)g->m.size())
+    return group_err(g, MPC_E_INVAL, "class accounting: member " + std::to_string(member) + " is not a member of the group");
+  if (member >= 0) {
+    const Algo a = g->m[(size_t)member]->algorithm;
+    if (a == Algo::FPC || a == Algo::BPC || a == Algo::CPack)
+      return group_err(g, MPC_E_INVAL, std::string("class accounting: member ") + std::to_string(member) + " (" + algorithm_name(a) +
+                                           ") has no selected output to take classes from (it is always 0)");
+  }
+  g->cls.from_member = member;
   return MPC_OK;
 }
 

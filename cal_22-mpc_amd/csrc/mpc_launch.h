@@ -2,12 +2,12 @@
 //
 // The launchers have C linkage, so a declaration that drifted from its definition would still link and then misbehave.
 // This header is therefore included by the callers (mpc_capi.hip, mpc_jit.h) AND by the units that define the
-// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_fit.hip, mpc_sizes.hip, the host section of mpc_vpc_lane.hip):
+// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_fit.hip, mpc_sizes.hip, mpc_classes.hip, the host section of mpc_vpc_lane.hip):
 // the compiler sees declaration and definition together and refuses a mismatch.  Host code only -- the run-time
 // compiled source of mpc_jit.h (-DMPC_LANE_JIT) never sees it, and it is not one of the files that key the code
 // object cache.
 //
-// The parameter blocks are only named here (their definitions: mpc_device.h, mpc_sc2.h, mpc_pattern.h, mpc_sizes.h).
+// The parameter blocks are only named here (their definitions: mpc_device.h, mpc_sc2.h, mpc_pattern.h, mpc_sizes.h, mpc_classes.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -19,6 +19,7 @@ struct MpcSc2Table;
 struct MpcPatternSet;
 struct MpcEvictSet;
 struct MpcSizesArgs;
+struct MpcClassArgs;
 
 extern "C" {
 // mpc_kernels.hip
@@ -99,4 +100,8 @@ hipError_t mpc_launch_fit_residues(const void *d_lines, unsigned long long n_lin
 // mpc_sizes.hip
 int mpc_sizes_wg_per_cu(const MpcSizesArgs *A);
 hipError_t mpc_launch_sizes(const MpcSizesArgs *A, unsigned long long n_lines, int grid, hipStream_t stream);
+
+// mpc_classes.hip: the per-class tables of the sizes of n_lines lines (mpc_classes.h); cut into launches as mpc_launch_sizes is
+int mpc_classes_wg_per_cu(const MpcClassArgs *A);
+hipError_t mpc_launch_classes(const MpcClassArgs *A, unsigned long long n_lines, int grid, hipStream_t stream);
 }

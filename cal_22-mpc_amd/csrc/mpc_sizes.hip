@@ -212,7 +212,7 @@ extern "C" hipError_t mpc_launch_sizes(const MpcSizesArgs *A, u64 n_lines, int g
 
 #if MPC_TESTING
 // test library only (not part of include/mpc_hip.h): the kernel launches that mpc_launch_vpc_lane,
-// mpc_launch_vpc_lane_jit and mpc_launch_sizes have made in this process, one per piece of a batch
+// mpc_launch_vpc_lane_jit, mpc_launch_sizes and mpc_launch_classes have made in this process, one per piece of a batch
 // (mpc_kernel_common.h: mpc_count_launch)
 extern "C" unsigned long long mpc_test_launches(void) { return __atomic_load_n(&mpc_test_launch_counter(), __ATOMIC_RELAXED); }
 #endif

@@ -7,7 +7,9 @@
 // output.  Calls of up to kMiniLines lines skip the slots: one pinned, device-visible buffer that the kernels read the
 // lines from and write the results to.  A member whose sizes are accounted on the device (Stager::account, mpc_sizes.h)
 // gets its device array of sizes whether or not the caller asked; the copy back and the pinned mirror stay tied to
-// "the caller asked".
+// "the caller asked".  The same holds for a member whose `selected` gives the classes of the lines (Stager::need_sel).
+// With per-class accounting on (mpc_classes.h) a chunk may carry one class byte per line: a pinned buffer per slot
+// beside the lines, with a device twin, both allocated when the first such chunk arrives.
 //
 // A handle is a group of one: the only difference between the two is "one output pointer" against "one output pointer
 // per member", so every function here takes arrays of `members` pointers.  What a stager feeds is told by a Sink:
@@ -34,8 +36,9 @@ constexpr size_t kMiniLines = 512;            // batches up to this many lines a
 
 struct Sink {
   void *ctx;
-  // every member over the same device-visible lines on stream s; d_sizes / d_sel: one pointer per member (null: not asked for)
-  int (*launch)(void *ctx, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, hipStream_t s);
+  // every member over the same device-visible lines on stream s; d_sizes / d_sel: one pointer per member (null: not asked for);
+  // d_classes: one device-visible class byte per line, or null (class 0)
+  int (*launch)(void *ctx, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes, hipStream_t s);
   int (*fail)(void *ctx, int code, const std::string &msg);   // keeps the message, returns the code
   int (*status)(void *ctx);                                   // at a point where the work is complete (Pattern's capacity)
 };
@@ -56,6 +59,8 @@ struct Slot {
   hipEvent_t done = nullptr;
   uint8_t *h_in = nullptr;       // pinned
   uint8_t *d_in = nullptr;
+  uint8_t *h_cls = nullptr;      // pinned, [stage_lines] class bytes; null until a chunk carries classes
+  uint8_t *d_cls = nullptr;
   // per member; the buffers are allocated when a call first asks for that member's per-line output
   std::vector<uint16_t *> d_sizes, h_sizes, user_sizes;   // user_*: where the pending results go
   std::vector<int8_t *> d_sel, h_sel, user_sel;
@@ -75,6 +80,9 @@ struct Stager {
   std::vector<int8_t *> ask_sel;       // did not ask (kept here so that no call allocates)
   std::vector<char> account;           // per member: its sizes are wanted on the device whether or not the caller asked (size
                                        // accounting, mpc_sizes.h); all 0 unless the owner switched accounting on
+  std::vector<char> need_sel;          // per member: the same for its `selected` (it gives the lines' classes)
+  uint8_t *mini_cls = nullptr;         // [kMiniLines] pinned class bytes of an in-place call; null until one carries classes
+  int log_field = 0;                   // MPC_CLASS_LOG_*: the class of a .log record's line (the owner keeps it 0 while accounting is off)
 };
 
 inline void init(Stager &st, int device, int L, size_t members)
@@ -90,6 +98,7 @@ inline void init(Stager &st, int device, int L, size_t members)
   st.ask_sizes.assign(members, nullptr);
   st.ask_sel.assign(members, nullptr);
   st.account.assign(members, 0);
+  st.need_sel.assign(members, 0);
 }
 
 // Creates what a staged call needs and is still missing.  When that is differs on purpose: a handle has nothing before
@@ -114,10 +123,16 @@ inline int ensure_outputs(Stager &st, const Sink &k, Slot &s, size_t i, bool siz
 {
   if ((sizes || st.account[i]) && !s.d_sizes[i]) HIPCHK(k, hipMalloc((void **)&s.d_sizes[i], st.stage_lines * sizeof(uint16_t)));
   if (sizes && !s.h_sizes[i]) HIPCHK(k, hipHostMalloc((void **)&s.h_sizes[i], st.stage_lines * sizeof(uint16_t), hipHostMallocDefault));
-  if (sel && !s.d_sel[i]) {
-    HIPCHK(k, hipMalloc((void **)&s.d_sel[i], st.stage_lines));
-    HIPCHK(k, hipHostMalloc((void **)&s.h_sel[i], st.stage_lines, hipHostMallocDefault));
-  }
+  if ((sel || st.need_sel[i]) && !s.d_sel[i]) HIPCHK(k, hipMalloc((void **)&s.d_sel[i], st.stage_lines));
+  if (sel && !s.h_sel[i]) HIPCHK(k, hipHostMalloc((void **)&s.h_sel[i], st.stage_lines, hipHostMallocDefault));
+  return MPC_OK;
+}
+
+// the class buffers of a slot, when a walk carries classes for the first time
+inline int ensure_classes(Stager &st, const Sink &k, Slot &s)
+{
+  if (!s.h_cls) HIPCHK(k, hipHostMalloc((void **)&s.h_cls, st.stage_lines, hipHostMallocDefault));
+  if (!s.d_cls) HIPCHK(k, hipMalloc((void **)&s.d_cls, st.stage_lines));
   return MPC_OK;
 }
 
@@ -134,9 +149,10 @@ inline int retire(Stager &st, const Sink &k, Slot &s)
   return MPC_OK;
 }
 
-// submit the chunk already sitting in s.h_in: one copy, then the sink's launch on the slot's stream.
+// submit the chunk already sitting in s.h_in (with_classes: and its class bytes in s.h_cls): one copy, then the sink's
+// launch on the slot's stream.
 // sizes / sel: the caller's arrays of per-member pointers (or null), `first` the chunk's first line in them.
-inline int submit(Stager &st, const Sink &k, Slot &s, u64 lines, uint16_t *const *sizes, int8_t *const *sel, u64 first)
+inline int submit(Stager &st, const Sink &k, Slot &s, u64 lines, uint16_t *const *sizes, int8_t *const *sel, u64 first, bool with_classes)
 {
   for (size_t i = 0; i < st.members; i++) {
     s.user_sizes[i] = (sizes && sizes[i]) ? sizes[i] + first : nullptr;
@@ -144,10 +160,11 @@ inline int submit(Stager &st, const Sink &k, Slot &s, u64 lines, uint16_t *const
     const int rc = ensure_outputs(st, k, s, i, s.user_sizes[i] != nullptr, s.user_sel[i] != nullptr);
     if (rc != MPC_OK) return rc;
     st.ask_sizes[i] = (s.user_sizes[i] || st.account[i]) ? s.d_sizes[i] : nullptr;
-    st.ask_sel[i] = s.user_sel[i] ? s.d_sel[i] : nullptr;
+    st.ask_sel[i] = (s.user_sel[i] || st.need_sel[i]) ? s.d_sel[i] : nullptr;
   }
   HIPCHK(k, hipMemcpyAsync(s.d_in, s.h_in, lines * (u64)st.L, hipMemcpyHostToDevice, s.stream));
-  const int rc = k.launch(k.ctx, s.d_in, lines, st.ask_sizes.data(), st.ask_sel.data(), s.stream);
+  if (with_classes) HIPCHK(k, hipMemcpyAsync(s.d_cls, s.h_cls, lines, hipMemcpyHostToDevice, s.stream));
+  const int rc = k.launch(k.ctx, s.d_in, lines, st.ask_sizes.data(), st.ask_sel.data(), with_classes ? s.d_cls : nullptr, s.stream);
   if (rc != MPC_OK) return rc;
   for (size_t i = 0; i < st.members; i++) {
     if (s.user_sizes[i]) HIPCHK(k, hipMemcpyAsync(s.h_sizes[i], s.d_sizes[i], lines * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
@@ -200,7 +217,8 @@ inline int finish(Stager &st, const Sink &k, hipStream_t own)
 // n <= kMiniLines lines, evaluated in place from pinned host memory: the sink's launch on stream s, one synchronisation
 // (polling hipStreamQuery instead was slower: 46 k vs 58 k lines/s).  The stream is the caller's choice and differs on
 // purpose: a handle's own stream, a group's first slot stream (idle: every group call ends synchronised).
-inline int in_place(Stager &st, const Sink &k, hipStream_t s, const uint8_t *lines, u64 n, uint16_t *const *sizes, int8_t *const *sel)
+inline int in_place(Stager &st, const Sink &k, hipStream_t s, const uint8_t *lines, u64 n, const uint8_t *classes, uint16_t *const *sizes,
+                    int8_t *const *sel)
 {
   const size_t nm = st.members;
   if (!st.mini) HIPCHK(k, hipHostMalloc((void **)&st.mini, kMiniLines * ((size_t)st.L + nm * (sizeof(uint16_t) + 1)), hipHostMallocDefault));
@@ -208,23 +226,28 @@ inline int in_place(Stager &st, const Sink &k, hipStream_t s, const uint8_t *lin
   int8_t *out_sel = reinterpret_cast<int8_t *>(out_sizes + nm * kMiniLines);
   for (size_t i = 0; i < nm; i++) {
     st.ask_sizes[i] = ((sizes && sizes[i]) || st.account[i]) ? out_sizes + i * kMiniLines : nullptr;
-    st.ask_sel[i] = (sel && sel[i]) ? out_sel + i * kMiniLines : nullptr;
+    st.ask_sel[i] = ((sel && sel[i]) || st.need_sel[i]) ? out_sel + i * kMiniLines : nullptr;
   }
   std::memcpy(st.mini, lines, (size_t)(n * (u64)st.L));
-  const int rc = k.launch(k.ctx, st.mini, n, st.ask_sizes.data(), st.ask_sel.data(), s);
+  if (classes) {
+    if (!st.mini_cls) HIPCHK(k, hipHostMalloc((void **)&st.mini_cls, kMiniLines, hipHostMallocDefault));
+    std::memcpy(st.mini_cls, classes, (size_t)n);
+  }
+  const int rc = k.launch(k.ctx, st.mini, n, st.ask_sizes.data(), st.ask_sel.data(), classes ? st.mini_cls : nullptr, s);
   if (rc != MPC_OK) { (void)hipStreamSynchronize(s); return rc; }   // (what was enqueued before the failure reads st.mini)
   HIPCHK(k, hipStreamSynchronize(s));
   for (size_t i = 0; i < nm; i++) {
     if (sizes && sizes[i]) std::memcpy(sizes[i], st.ask_sizes[i], (size_t)n * sizeof(uint16_t));
-    if (st.ask_sel[i]) std::memcpy(sel[i], st.ask_sel[i], (size_t)n);
+    if (sel && sel[i]) std::memcpy(sel[i], st.ask_sel[i], (size_t)n);
   }
   return k.status(k.ctx);
 }
 
-// A walk over a trace: retire a slot, let `fill` put up to `room` lines into its pinned buffer, submit them, take the
-// other slot; until fill returns 0 lines or fails (< 0: the code, already reported).  Then finish, or abandon after a failure.
+// A walk over a trace: retire a slot, let `fill` put up to `room` lines into its pinned buffer (with_classes: and their
+// class bytes into the slot's class buffer, else that argument is null), submit them, take the other slot; until fill
+// returns 0 lines or fails (< 0: the code, already reported).  Then finish, or abandon after a failure.
 template <class Fill>
-inline int pump(Stager &st, const Sink &k, hipStream_t own, uint16_t *const *sizes, int8_t *const *sel, u64 *lines_done, Fill fill)
+inline int pump(Stager &st, const Sink &k, hipStream_t own, uint16_t *const *sizes, int8_t *const *sel, u64 *lines_done, bool with_classes, Fill fill)
 {
   int rc = ensure(st, k);
   u64 done = 0;
@@ -232,11 +255,12 @@ inline int pump(Stager &st, const Sink &k, hipStream_t own, uint16_t *const *siz
   while (rc == MPC_OK) {
     Slot &s = st.slots[which];
     rc = retire(st, k, s);   // the slot's previous chunk (overlapped with the other slot's work)
+    if (rc == MPC_OK && with_classes) rc = ensure_classes(st, k, s);
     if (rc != MPC_OK) break;
-    const long long got = fill(s.h_in, (u64)st.stage_lines, done);
+    const long long got = fill(s.h_in, with_classes ? s.h_cls : nullptr, (u64)st.stage_lines, done);
     if (got < 0) rc = (int)got;
     if (got <= 0) break;
-    rc = submit(st, k, s, (u64)got, sizes, sel, done);
+    rc = submit(st, k, s, (u64)got, sizes, sel, done, with_classes);
     if (rc != MPC_OK) break;
     done += (u64)got;
     which ^= 1;
@@ -248,13 +272,16 @@ inline int pump(Stager &st, const Sink &k, hipStream_t own, uint16_t *const *siz
 }
 
 // n lines in the caller's memory.  sizes / sel: arrays of one pointer per member (the array or any entry may be null).
-inline int compress_batch(Stager &st, const Sink &k, hipStream_t own, const uint8_t *lines, u64 n, uint16_t *const *sizes, int8_t *const *sel)
+// classes: one class byte per line in the caller's memory, or null.
+inline int compress_batch(Stager &st, const Sink &k, hipStream_t own, const uint8_t *lines, u64 n, const uint8_t *classes, uint16_t *const *sizes,
+                          int8_t *const *sel)
 {
   HIPCHK(k, hipSetDevice(st.device));
-  if (n <= kMiniLines) return in_place(st, k, own ? own : st.slots[0].stream, lines, n, sizes, sel);
-  return pump(st, k, own, sizes, sel, nullptr, [&](uint8_t *buf, u64 room, u64 done) -> long long {
+  if (n <= kMiniLines) return in_place(st, k, own ? own : st.slots[0].stream, lines, n, classes, sizes, sel);
+  return pump(st, k, own, sizes, sel, nullptr, classes != nullptr, [&](uint8_t *buf, uint8_t *cls, u64 room, u64 done) -> long long {
     const u64 take = (n - done) < room ? (n - done) : room;
     mpctrace::parallel_copy(buf, lines + done * (u64)st.L, (size_t)(take * (u64)st.L));
+    if (cls) std::memcpy(cls, classes + done, (size_t)take);
     return (long long)take;
   });
 }
@@ -281,7 +308,7 @@ inline int compress_npy(Stager &st, const Sink &k, hipStream_t own, const char *
   if (hipSetDevice(st.device) != hipSuccess) { fclose(f); return k.fail(k.ctx, MPC_E_HIP, "hipSetDevice failed"); }
   const int fd = fileno(f);
   u64 done_rows = 0;
-  rc = pump(st, k, own, nullptr, nullptr, &done_rows, [&](uint8_t *buf, u64 room, u64 done) -> long long {
+  rc = pump(st, k, own, nullptr, nullptr, &done_rows, false, [&](uint8_t *buf, uint8_t *, u64 room, u64 done) -> long long {
     const u64 take = (end - begin - done) < room ? (end - begin - done) : room;
     if (take && !mpctrace::parallel_pread(fd, buf, (size_t)(take * cols), off + (begin + done) * cols))
       return k.fail(k.ctx, MPC_E_PARSE, "short read: .npy file is truncated");
@@ -305,7 +332,8 @@ inline int compress_gpgpusim_log(Stager &st, const Sink &k, hipStream_t own, con
   const u64 L = (u64)st.L;
   u64 requests = 0, lines = 0;
   bool first = true, ended = false;
-  rc = pump(st, k, own, nullptr, nullptr, &lines, [&](uint8_t *buf, u64 room, u64) -> long long {
+  const int field = st.log_field;       // the class of a record's line: a byte of the record's header (mpc_hip_classes.h)
+  rc = pump(st, k, own, nullptr, nullptr, &lines, field != MPC_CLASS_LOG_NONE, [&](uint8_t *buf, uint8_t *cls, u64 room, u64) -> long long {
     u64 fill = 0;
     uint32_t req_type, req_size;
     const unsigned char *payload;
@@ -319,6 +347,10 @@ inline int compress_gpgpusim_log(Stager &st, const Sink &k, hipStream_t own, con
         if (req_size != L)
           return k.fail(k.ctx, MPC_E_INVAL, "the GPGPU-sim trace mixes request sizes (" + std::to_string(req_size) + " after " + std::to_string(L) + " bytes)");
         std::memcpy(buf + fill * L, payload, (size_t)L);
+        if (cls) {
+          const unsigned char *rec = payload - mpctrace::kLogRecordHeader;
+          cls[fill] = field == MPC_CLASS_LOG_KERNEL ? rec[0] : field == MPC_CLASS_LOG_MFTYPE ? rec[1] : (req_type == 4u ? 1 : 0);
+        }
         fill++;
       }
       requests++;
@@ -339,6 +371,8 @@ inline void destroy(Stager &st)
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.h_in) (void)hipHostFree(s.h_in);
     if (s.d_in) (void)hipFree(s.d_in);
+    if (s.h_cls) (void)hipHostFree(s.h_cls);
+    if (s.d_cls) (void)hipFree(s.d_cls);
     for (uint16_t *p : s.d_sizes) if (p) (void)hipFree(p);
     for (uint16_t *p : s.h_sizes) if (p) (void)hipHostFree(p);
     for (int8_t *p : s.d_sel) if (p) (void)hipFree(p);
@@ -349,6 +383,8 @@ inline void destroy(Stager &st)
   }
   if (st.mini) (void)hipHostFree(st.mini);
   st.mini = nullptr;
+  if (st.mini_cls) (void)hipHostFree(st.mini_cls);
+  st.mini_cls = nullptr;
   st.slots_ready = false;
 }
 

@@ -70,6 +70,36 @@ BestReport CompressorSet::GetBest(unsigned sectorBytes)
   return best;
 }
 
+void CompressorSet::EnableClassStats(unsigned sectorBytes)
+{
+  Prepare();
+  int rc = mpc_group_class_stats_enable(m_Group, sectorBytes);
+  if (rc != MPC_OK) fail("CompressorSet::EnableClassStats", rc, mpc_group_last_error(m_Group));
+  m_ClassSectorBytes = sectorBytes;
+}
+
+ClassReport CompressorSet::GetClassStats(size_t i)
+{
+  Prepare();
+  ClassReport report(GetLineSize(), m_ClassSectorBytes);
+  report.Table.assign(MPC_CLASS_TABLE_LEN, 0);
+  int rc = mpc_group_class_stats_get(m_Group, i == BestMember ? MPC_CLASS_BEST : (int)i, report.Table.data(), report.Table.size());
+  if (rc != MPC_OK) fail("CompressorSet::GetClassStats", rc, mpc_group_last_error(m_Group));
+  return report;
+}
+
+void CompressorSet::SetLogClassField(int field)
+{
+  int rc = mpc_group_class_log_field(m_Group, field);
+  if (rc != MPC_OK) fail("CompressorSet::SetLogClassField", rc, mpc_group_last_error(m_Group));
+}
+
+void CompressorSet::ClassFromMember(size_t i)
+{
+  int rc = mpc_group_class_from_member(m_Group, (int)i);
+  if (rc != MPC_OK) fail("CompressorSet::ClassFromMember", rc, mpc_group_last_error(m_Group));
+}
+
 unsigned long long CompressorSet::CompressFile(const std::string &tracePath)
 {
   Prepare();

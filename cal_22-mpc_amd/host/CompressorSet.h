@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "Compressor.h"
+#include "ClassReport.h"
 #include "SizeReport.h"
 
 struct mpc_group;
@@ -42,11 +43,21 @@ public:
   // but Pattern ones, ties to the first minimal member); refused with a message when fewer than two take part
   void EnableBest();
   BestReport GetBest(unsigned sectorBytes = ACCESS_GRAN);
+  // ADDITIVE: per-class sums for every member and, with EnableBest (before or after), for the per-line smallest size
+  // (mpc_group_class_stats_enable); off by default
+  void EnableClassStats(unsigned sectorBytes = ACCESS_GRAN);
+  // member i's sums, or with i == BestMember those of the best-of
+  static constexpr size_t BestMember = (size_t)-1;
+  ClassReport GetClassStats(size_t i);
+  void SetLogClassField(int field);
+  // the class of a line is member i's selected + 1: a VPC member's cluster + 1, 0 = uncompressed (mpc_group_class_from_member)
+  void ClassFromMember(size_t i);
 
 private:
   void Prepare();      // members' buffered lines first
   std::vector<Compressor *> m_Members;
   mpc_group *m_Group;
+  unsigned m_ClassSectorBytes = 0;
 };
 
 }  // namespace comp

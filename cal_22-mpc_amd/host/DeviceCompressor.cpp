@@ -79,6 +79,32 @@ SizeReport DeviceCompressor::GetSizeHistogram(unsigned sectorBytes)
   return report;
 }
 
+void DeviceCompressor::EnableClassStats(unsigned sectorBytes)
+{
+  FlushLines();
+  int rc = mpc_class_stats_enable(m_Handle, sectorBytes);
+  if (rc != MPC_OK) Fail(m_Tag + "::EnableClassStats", rc);
+}
+
+ClassReport DeviceCompressor::GetClassStats()
+{
+  FlushLines();
+  unsigned sectorBytes = 0;
+  int rc = mpc_class_sector_bytes(m_Handle, &sectorBytes);
+  ClassReport report(m_LineSize, sectorBytes);
+  report.Table.assign(MPC_CLASS_TABLE_LEN, 0);
+  // (accounting off: the get call refuses and leaves the message)
+  rc = mpc_class_stats_get(m_Handle, report.Table.data(), report.Table.size());
+  if (rc != MPC_OK) Fail(m_Tag + "::GetClassStats", rc);
+  return report;
+}
+
+void DeviceCompressor::SetLogClassField(int field)
+{
+  int rc = mpc_class_log_field(m_Handle, field);
+  if (rc != MPC_OK) Fail(m_Tag + "::SetLogClassField", rc);
+}
+
 CompResult *DeviceCompressor::GetResult()
 {
   FlushLines();

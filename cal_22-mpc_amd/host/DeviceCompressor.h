@@ -7,6 +7,7 @@
 #include <string>
 
 #include "Compressor.h"
+#include "ClassReport.h"
 #include "SizeReport.h"
 
 namespace comp
@@ -32,6 +33,13 @@ public:
   void EnableSizeHistogram();
   // ... that histogram (mpc_size_hist_get), buffered lines evaluated first; a failure (not enabled) exits like every other
   SizeReport GetSizeHistogram(unsigned sectorBytes = ACCESS_GRAN);
+  // ADDITIVE: sum, from now on, lines, bits and sector counts per class of a line (mpc_class_stats_enable); off by default.
+  // Lines count in class 0 unless they come from a .log file after SetLogClassField.
+  void EnableClassStats(unsigned sectorBytes = ACCESS_GRAN);
+  // ... those sums (mpc_class_stats_get), buffered lines evaluated first; a failure (not enabled) exits like every other
+  ClassReport GetClassStats();
+  // which field of a .log record is the class of its line: MPC_CLASS_LOG_NONE / _KERNEL / _RW / _MFTYPE (mpc_class_log_field)
+  void SetLogClassField(int field);
 
 protected:
   // tag: the short name in front of this class's messages ("BDI", "VPC", ...)

@@ -11,6 +11,11 @@
 // ADDITIVE: --size-histogram / --sector BYTES also write OUTDIR/<stem>_results_sizes.csv (comp::SizeReport: the
 // distribution of the per-line sizes and the sectors they occupy) and, for a list, the per-line best of the list as
 // BEST_results_sizes.csv and a "BEST comp.ratio:" line.  Without them nothing changes.
+// ADDITIVE: --by kernel|rw|mftype|cluster also writes OUTDIR/<stem>_results_classes.csv (comp::ClassReport: lines, bits,
+// ratio and sector ratio per class of a line).  kernel, rw and mftype take the class from the records of a .log trace;
+// cluster takes it from the first VPC member of a list (its cluster + 1, 0 = uncompressed).  With a list every member
+// gets its file, and with --size-histogram the per-line best of the list BEST_results_classes.csv.  --sector sets the
+// sector size of these files too.  Without --by nothing changes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,6 +52,10 @@ static const char *kHelp =
     "                       per-line best of the list (BEST_results_sizes.csv)\n"
     "      --sector arg     Sector size in bytes for that file. Default=32\n"
     "                       (implies --size-histogram)\n"
+    "      --by arg         Also write <stem>_results_classes.csv: lines, bits and\n"
+    "                       sectors per class of a line [kernel/rw/mftype/cluster].\n"
+    "                       kernel, rw, mftype: a field of a .log trace's records;\n"
+    "                       cluster: the first VPC of a list picks the class\n"
     "  -h, --help           Print usage\n";
 
 struct Args {
@@ -56,6 +65,8 @@ struct Args {
   unsigned long long line_buffer = 0;   // ADDITIVE --line-buffer N: that loop with Compressor::SetLineBuffering(N)
   bool size_histogram = false;          // ADDITIVE --size-histogram: <stem>_results_sizes.csv (SizeReport.h)
   unsigned sector = ACCESS_GRAN;        // ADDITIVE --sector BYTES: the sector size of that file; implies --size-histogram
+  std::string by;                       // ADDITIVE --by kernel|rw|mftype|cluster: <stem>_results_classes.csv (ClassReport.h); empty: off
+  bool has_by = false;
 };
 
 static bool take_value(int argc, char **argv, int &i, const std::string &arg, const char *shortf, const char *longf,
@@ -113,12 +124,26 @@ static trace::Loader *openTrace(const std::string &tracePath, trace::MemReq_t **
   return loader;
 }
 
-// --sector against the trace: a sector is at most a line
+// --sector against the trace: a sector is at most a line, and --by counts up to 8 sectors a line
 static void requireSector(const Args &a, unsigned traceLineSize)
 {
-  if (!a.size_histogram || a.sector <= traceLineSize) return;
-  printf("--sector %u: a sector cannot be larger than the trace's %u-byte lines.\n", a.sector, traceLineSize);
-  exit(1);
+  if ((a.size_histogram || a.has_by) && a.sector > traceLineSize) {
+    printf("--sector %u: a sector cannot be larger than the trace's %u-byte lines.\n", a.sector, traceLineSize);
+    exit(1);
+  }
+  if (a.has_by && (traceLineSize + a.sector - 1) / a.sector > comp::ClassReport::Row - 2) {
+    printf("--by with --sector %u: the trace's %u-byte lines have more than %zu sectors.\n", a.sector, traceLineSize, comp::ClassReport::Row - 2);
+    exit(1);
+  }
+}
+
+// --by kernel|rw|mftype: the field of a .log record (MPC_CLASS_LOG_*); 0 for cluster
+static int logFieldOf(const std::string &by) { return by == "kernel" ? 1 : by == "rw" ? 2 : by == "mftype" ? 3 : 0; }
+
+static void writeClasses(comp::ClassReport report, const std::string &workloadName, const std::string &outputDirPath,
+                         const std::string &saveFileName)
+{
+  report.Print(workloadName, outputDirPath + "/" + saveFileName + "_results_classes.csv");
 }
 
 static void writeSizes(comp::SizeReport report, const std::string &workloadName, const std::string &outputDirPath,
@@ -211,6 +236,15 @@ int main(int argc, char **argv)
       a.size_histogram = true;
       continue;
     }
+    if (arg == "--by" || arg.compare(0, 5, "--by=") == 0) {
+      if (arg == "--by" && i + 1 >= argc) {
+        std::cout << "Option 'by' is missing an argument" << std::endl;
+        exit(1);
+      }
+      a.by = arg == "--by" ? argv[++i] : arg.substr(5);
+      a.has_by = true;
+      continue;
+    }
     if (take_value(argc, argv, i, arg, "-a", "algorithm", a.algorithm, a.has_algorithm)) continue;
     if (take_value(argc, argv, i, arg, "-i", "input", a.input, a.has_input)) continue;
     if (take_value(argc, argv, i, arg, "-c", "config", a.config, a.has_config)) continue;
@@ -247,6 +281,27 @@ int main(int argc, char **argv)
     std::cout << kHelp << std::endl;
     return 0;
   }
+  // --by: checked before anything is opened or written, one message each
+  if (a.has_by) {
+    if (!(a.by == "kernel" || a.by == "rw" || a.by == "mftype" || a.by == "cluster")) {
+      std::cout << "--by takes one of kernel, rw, mftype and cluster, not \"" << a.by << "\"." << std::endl;
+      return 1;
+    }
+    if (a.by != "cluster" && !trace::IsGpgpuSimLog(a.input)) {
+      std::cout << "--by " << a.by << " takes the class from the records of a GPGPU-Sim .log trace: \"" << a.input << "\" is not one." << std::endl;
+      return 1;
+    }
+    bool vpcInList = false;
+    for (const std::string &n : list) vpcInList = vpcInList || n == "VPC";
+    if (a.by == "cluster" && !vpcInList) {
+      std::cout << "--by cluster needs a list of algorithms with a VPC member (-a VPC,BDI,...): its cluster is the class." << std::endl;
+      return 1;
+    }
+    if (a.per_line) {
+      std::cout << "--by is evaluated in batches: it does not go with --per-line / --line-buffer." << std::endl;
+      return 1;
+    }
+  }
   const std::string tracePath = a.input, configPath = a.config, outputDirPath = a.has_output ? a.output : "";
   if (!list.empty()) return runList(list, tracePath, configPath, outputDirPath, a);
 
@@ -267,6 +322,10 @@ int main(int argc, char **argv)
   if (a.line_buffer) compressor->SetLineBuffering(a.line_buffer);
   requireLineSize(loader->GetCachelineSize(), compressor->GetLineSize());
   if (a.size_histogram) compressor->EnableSizeHistogram();
+  if (a.has_by) {
+    compressor->EnableClassStats(a.sector);
+    compressor->SetLogClassField(logFieldOf(a.by));
+  }
   if (!a.per_line && (loader->SupportsBatch() || !loader->GetStreamablePath().empty()))
     compressBatches(compressor, loader);
   else
@@ -278,6 +337,7 @@ int main(int argc, char **argv)
   std::cout << "comp.ratio: " << mpctext::num(compStat->CompRatio) << std::endl;
   writeResults(compStat, workloadName, outputDirPath, saveFileName);
   if (a.size_histogram) writeSizes(compressor->GetSizeHistogram(a.sector), workloadName, outputDirPath, saveFileName);
+  if (a.has_by) writeClasses(compressor->GetClassStats(), workloadName, outputDirPath, saveFileName);
 
   delete memReq;      // (the reference leaks its request object)
   delete loader;
@@ -309,6 +369,16 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
   {
     comp::CompressorSet set(members);
     if (a.size_histogram) set.EnableBest();
+    if (a.has_by) {
+      set.EnableClassStats(a.sector);
+      if (a.by == "cluster") {
+        size_t vpc = 0;
+        while (names[vpc] != "VPC") vpc++;      // (main() has checked that there is one)
+        set.ClassFromMember(vpc);
+      } else {
+        set.SetLogClassField(logFieldOf(a.by));
+      }
+    }
     compressBatches(&set, loader);
     for (size_t i = 0; i < names.size(); i++) {
       comp::CompResult *compStat = set.GetResult(i);
@@ -316,11 +386,13 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
       std::cout << names[i] << " comp.ratio: " << mpctext::num(compStat->CompRatio) << std::endl;
       writeResults(compStat, workloadName, outputDirPath, saveFileName);
       if (a.size_histogram) writeSizes(evaluators[i]->GetSizeHistogram(a.sector), workloadName, outputDirPath, saveFileName);
+      if (a.has_by) writeClasses(set.GetClassStats(i), workloadName, outputDirPath, saveFileName);
     }
     if (a.size_histogram) {
       const comp::BestReport best = set.GetBest(a.sector);
       std::cout << "BEST comp.ratio: " << mpctext::num(best.CompRatio()) << std::endl;
       writeSizes(best.Sizes, workloadName, outputDirPath, "BEST");
+      if (a.has_by) writeClasses(set.GetClassStats(comp::CompressorSet::BestMember), workloadName, outputDirPath, "BEST");
     }
   }
   delete memReq;

@@ -377,6 +377,9 @@ int mpc_group_sync(mpc_group *g);
 }
 #endif
 #include "mpc_hip_sizes.h"
+/* ---- per-class accounting: an evaluator's lines, bits and sector counts broken down by a class byte per line ----
+ * Additive and off by default as well, in a header of its own for the same reason.                                  */
+#include "mpc_hip_classes.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

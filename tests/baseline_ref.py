@@ -1,7 +1,8 @@
 """Seeded inputs of the BDI / FPC / BPC parity fixture (tests/golden/ref_baseline_vectors.npz, written by
 tests/golden/make_ref_baseline_vectors.py from the reference's own compressors), so that the CPU and GPU tests can
 rebuild them.  One case per (compressor, line size); every case mixes hand-built edge families with the trace
-families of cal_22-mpc_amd/traces.py, in a seeded order."""
+families of cal_22-mpc_amd/traces.py, in a seeded order.  Lines built for a chosen plane, run, delta or immediate at a
+chosen place are in tests/baseline_chosen.py, with a fixture of their own."""
 from __future__ import annotations
 
 import hashlib

@@ -27,6 +27,9 @@ MPC_SIZE_BINS = 4096          # bins of a size histogram (include/mpc_hip_sizes.
 MPC_CLASS_COUNT, MPC_CLASS_ROW = 256, 10      # a class table is uint64[256][10] (include/mpc_hip_classes.h)
 MPC_CLASS_TABLE_LEN = MPC_CLASS_COUNT * MPC_CLASS_ROW
 MPC_CLASS_BEST = -1           # mpc_group_class_stats_get: the best-of's table
+MPC_PACK_MAX_SECTORS = 1024   # a pack table is uint64[8 + 1024] (include/mpc_hip_pack.h)
+MPC_PACK_TABLE_LEN = 8 + MPC_PACK_MAX_SECTORS
+MPC_PACK_BEST = -1            # mpc_group_pack_stats_get: the table of the per-line minimum
 CLASS_LOG_FIELDS = {None: 0, "kernel": 1, "rw": 2, "mftype": 3}      # MPC_CLASS_LOG_*
 MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2, MPC_PATH_PATTERN = 1, 2, 3, 4, 5, 6, 7
 MPC_PATH_PATTERN_EVICTING = 9
@@ -154,6 +157,13 @@ def lib() -> C.CDLL:
                                                          C.c_void_p], C.c_int),
             "mpc_group_class_log_field": ([H, C.c_int], C.c_int),
             "mpc_group_class_from_member": ([H, C.c_int], C.c_int),
+            "mpc_pack_stats_enable": ([H, C.c_uint64, C.c_uint, C.c_uint], C.c_int),
+            "mpc_pack_check_values": ([C.c_uint, C.c_uint64, C.c_uint, C.c_uint], C.c_int),
+            "mpc_pack_stats_get": ([H, C.c_void_p, C.c_size_t], C.c_int),
+            "mpc_pack_stats_merge": ([H, C.c_void_p, C.c_size_t], C.c_int),
+            "mpc_pack_sectors_of_tail": ([C.c_void_p, C.c_size_t, C.c_uint, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
+            "mpc_group_pack_stats_enable": ([H, C.c_uint64, C.c_uint, C.c_uint], C.c_int),
+            "mpc_group_pack_stats_get": ([H, C.c_int, C.c_void_p, C.c_size_t], C.c_int),
         }
         for name, (args, res) in sigs.items():
             fn = getattr(L, name)
@@ -187,6 +197,9 @@ EXPORTED_CLASS_SYMBOLS = ["mpc_class_stats_enable", "mpc_class_stats_get", "mpc_
                           "mpc_compress_batch_classed", "mpc_compress_batch_device_classed", "mpc_class_log_field",
                           "mpc_group_class_stats_enable", "mpc_group_class_stats_get", "mpc_group_compress_batch_classed",
                           "mpc_group_compress_batch_device_classed", "mpc_group_class_log_field", "mpc_group_class_from_member"]
+# The pack accounting entry points, declared in include/mpc_hip_pack.h (which mpc_hip.h includes).
+EXPORTED_PACK_SYMBOLS = ["mpc_pack_stats_enable", "mpc_pack_check_values", "mpc_pack_stats_get", "mpc_pack_stats_merge", "mpc_pack_sectors_of_tail",
+                         "mpc_group_pack_stats_enable", "mpc_group_pack_stats_get"]
 
 
 def gpgpusim_log_line_size(path: str) -> int:
@@ -251,6 +264,52 @@ def class_table_view(table: np.ndarray, line_size: int, sector_bytes: int) -> Di
     t = np.asarray(table, dtype=np.uint64).reshape(MPC_CLASS_COUNT, MPC_CLASS_ROW)
     S = -(-int(line_size) // int(sector_bytes))
     return {"lines": t[:, 0].copy(), "bits": t[:, 1].copy(), "sectors": t[:, 2:2 + S].copy()}
+
+
+def _pack_values(fn: str, block_lines, sector_bytes, header_bits):
+    """The three values of ``enable_pack_stats`` as the C ABI takes them (unsigned)."""
+    block_lines, sector_bytes, header_bits = int(block_lines), int(sector_bytes), int(header_bits)
+    if not (0 <= block_lines < 1 << 64 and 0 <= sector_bytes < 1 << 32 and 0 <= header_bits < 1 << 32):
+        raise MpcError(-22, f"{fn}: block_lines, sector_bytes and header_bits are unsigned")
+    return block_lines, sector_bytes, header_bits
+
+
+def pack_check_values(line_size: int, block_lines: int, sector_bytes: int = 32, header_bits: int = 0) -> None:
+    """Raises ``MpcError`` with the message ``enable_pack_stats`` would give for these values (``mpc_pack_check_values``;
+    no device)."""
+    rc = lib().mpc_pack_check_values(int(line_size), *_pack_values("mpc_pack_check_values", block_lines, sector_bytes, header_bits))
+    if rc != 0:
+        raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
+
+
+def pack_sectors_of_tail(table, line_size: int):
+    """``(tail_sectors, tail_cap)`` of a pack table's open block, closed as a short block (``mpc_pack_sectors_of_tail``;
+    no device); ``(0, 0)`` without open lines."""
+    t = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1)
+    sectors, cap = C.c_uint64(), C.c_uint64()
+    rc = lib().mpc_pack_sectors_of_tail(t.ctypes.data, t.size, int(line_size), C.byref(sectors), C.byref(cap))
+    if rc != 0:
+        raise MpcError(rc, "mpc_pack_sectors_of_tail: not a pack table (MPC_PACK_TABLE_LEN entries, open lines below block_lines)")
+    return int(sectors.value), int(cap.value)
+
+
+def pack_table_view(table: np.ndarray, line_size: int, close_tail: bool = True) -> Dict:
+    """A pack table ``uint64[MPC_PACK_TABLE_LEN]`` as a dict: ``block_lines``, ``sector_bytes``, ``header_bits``,
+    ``block_sectors`` (S_B), ``blocks``, ``payload_bits``, ``sectors``, ``histogram[S_B]`` (entry k - 1: closed blocks
+    that occupy k sectors), ``open_lines``, ``open_bits``, ``tail_sectors`` and ``tail_cap`` (the open block closed as a
+    short one; both 0 with ``close_tail=False``), ``sector_ratio`` = (blocks x S_B + tail_cap) / (sectors +
+    tail_sectors) and ``sector_ratio_closed``, the same without the tail (0.0 without sectors)."""
+    t = np.asarray(table, dtype=np.uint64).reshape(MPC_PACK_TABLE_LEN)
+    N, sb, hb = int(t[5]), int(t[6]), int(t[7])
+    S = -(-N * int(line_size) // sb)
+    blocks, sectors = int(t[0]), int(t[2])
+    tail_sectors, tail_cap = pack_sectors_of_tail(t, line_size) if close_tail else (0, 0)
+    total = sectors + tail_sectors
+    return {"block_lines": N, "sector_bytes": sb, "header_bits": hb, "block_sectors": S, "blocks": blocks, "payload_bits": int(t[1]),
+            "sectors": sectors, "histogram": t[8:8 + S].copy(), "open_lines": int(t[3]), "open_bits": int(t[4]),
+            "tail_sectors": tail_sectors, "tail_cap": tail_cap,
+            "sector_ratio": (blocks * S + tail_cap) / total if total else 0.0,
+            "sector_ratio_closed": blocks * S / sectors if sectors else 0.0}
 
 
 def _ratio(original, compressed, lines) -> float:
@@ -434,6 +493,31 @@ class _Evaluator:
         """Which field of a ``.log`` record is the class of its line in ``compress_gpgpusim_log``: ``"kernel"`` (the
         kernel id), ``"rw"`` (0 = read, 1 = write), ``"mftype"`` or ``None`` (class 0)."""
         self._check(lib().mpc_class_log_field(self._h, _class_log_field(field)))
+
+
+    # -- pack accounting --------------------------------------------------------
+    def enable_pack_stats(self, block_lines: int, sector_bytes: int = 32, header_bits: int = 0) -> None:
+        """Count, from now on, the sectors of ``sector_bytes`` bytes that blocks of ``block_lines`` consecutive lines
+        occupy when their compressed lines are packed and rounded up once, ``header_bits`` added per block
+        (``mpc_pack_stats_enable``); idempotent for the same values.  Lines are numbered from 0 in the order of the
+        calls, from now or the last ``reset()``."""
+        self._check(lib().mpc_pack_stats_enable(self._h, *_pack_values("mpc_pack_stats_enable", block_lines, sector_bytes, header_bits)))
+
+    def pack_table(self) -> np.ndarray:
+        """The raw table ``uint64[MPC_PACK_TABLE_LEN]`` (``mpc_pack_stats_get``): what ``pack_stats_merge`` takes."""
+        t = np.zeros(MPC_PACK_TABLE_LEN, dtype=np.uint64)
+        self._check(lib().mpc_pack_stats_get(self._h, t.ctypes.data, t.size))
+        return t
+
+    def pack_stats(self, close_tail: bool = True) -> Dict:
+        """``pack_table_view`` of the table since accounting was switched on or the last ``reset()``."""
+        return pack_table_view(self.pack_table(), self.line_size, close_tail)
+
+    def pack_stats_merge(self, table: np.ndarray) -> None:
+        """Add another evaluator's ``pack_table()`` (a shard's, cut at a multiple of ``block_lines``) and take over its
+        open block."""
+        table = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1)
+        self._check(lib().mpc_pack_stats_merge(self._h, table.ctypes.data, table.size))
 
 
 class VPC(_Evaluator):
@@ -810,6 +894,28 @@ class EvaluatorSet:
         t = np.zeros(MPC_CLASS_TABLE_LEN, dtype=np.uint64)
         if lib().mpc_group_class_stats_get(self._g, MPC_CLASS_BEST, t.ctypes.data, t.size) == 0:
             out["best"] = class_table_view(t, self.line_size, sb)
+        return out
+
+    # -- pack accounting -----------------------------------------------------------
+    def enable_pack_stats(self, block_lines: int, sector_bytes: int = 32, header_bits: int = 0) -> None:
+        """``enable_pack_stats`` for every member with the same values; with ``enable_best()`` BEFORE it also a table of
+        the per-line smallest size, counted with ``header_bits + block_lines x tag_bits``."""
+        self._check(lib().mpc_group_pack_stats_enable(self._g, *_pack_values("mpc_group_pack_stats_enable", block_lines, sector_bytes,
+                                                                              header_bits)))
+
+    def pack_table(self, member: int) -> np.ndarray:
+        """The raw table of member ``member`` or, with ``MPC_PACK_BEST``, of the per-line minimum."""
+        t = np.zeros(MPC_PACK_TABLE_LEN, dtype=np.uint64)
+        self._check(lib().mpc_group_pack_stats_get(self._g, int(member), t.ctypes.data, t.size))
+        return t
+
+    def pack_stats(self, close_tail: bool = True) -> Dict:
+        """``{0: ..., 1: ..., "best": ...}``: one entry per member, in member order, and ``"best"`` if the best-of was
+        on when pack accounting was switched on; each as ``_Evaluator.pack_stats()`` returns it."""
+        out = {i: pack_table_view(self.pack_table(i), self.line_size, close_tail) for i in range(len(self.members))}
+        t = np.zeros(MPC_PACK_TABLE_LEN, dtype=np.uint64)
+        if lib().mpc_group_pack_stats_get(self._g, MPC_PACK_BEST, t.ctypes.data, t.size) == 0:
+            out["best"] = pack_table_view(t, self.line_size, close_tail)
         return out
 
     def class_log_field(self, field) -> None:

@@ -20,6 +20,7 @@
 #include "mpc_pattern.h"
 #include "mpc_sizes.h"
 #include "mpc_classes.h"
+#include "mpc_pack.h"
 #include "mpc_fit.h"
 #include "mpc_launch.h"
 
@@ -33,7 +34,7 @@ constexpr size_t kTestWords = kRouteWords + (MPC_STAMPS ? MPC_STAMP_WORDS : 0); 
 
 typedef unsigned long long u64;
 
-// Size or class accounting on mpc_compress_batch_device without a sizes array of the caller's: the batch is evaluated in
+// Size, class or pack accounting on mpc_compress_batch_device without a sizes array of the caller's: the batch is evaluated in
 // pieces of this many lines, each evaluator launch followed by the accounting passes over ONE scratch array (8 MiB per member).
 constexpr u64 kAccountLines = 4ull << 20;
 
@@ -157,6 +158,21 @@ struct mpc_handle {
     u64 *d_tab = nullptr;              // [MPC_CLASS_TABLE_LEN]
     std::vector<u64> extra;            // merged-in tables
   } cls;
+  // pack accounting (mpc_pack.h): nothing of it exists before mpc_pack_stats_enable.  A launch may begin or end inside a
+  // block: the open block's payload stays on the device, double-buffered, and every launch that reads or writes it waits,
+  // on its own stream, for the event the one before it recorded -- whichever stream that was (as cpk above).
+  struct {
+    bool on = false;
+    u64 N = 0;
+    unsigned sector_bytes = 0, header_bits = 0;
+    u64 seen = 0;                      // lines evaluated since accounting was switched on or last reset; the open block has seen % N
+    u64 *d_tab = nullptr;              // [MPC_PACK_DEV_LEN]
+    uint32_t *d_carry = nullptr;       // [2]: a launch reads word `cur` and writes the other
+    int cur = 0;
+    hipEvent_t done = nullptr;
+    bool recorded = false;
+    std::vector<u64> extra;            // merged-in tables, device layout
+  } pack;
   std::string error;
 };
 
@@ -183,6 +199,18 @@ struct mpc_group {
     int log_field = MPC_CLASS_LOG_NONE;
     int8_t *d_scratch_sel = nullptr;   // [kAccountLines] that member's selected values of a piece of a device batch
   } cls;
+  // pack accounting of the group (mpc_pack.h): the members' tables are their handles'; the per-line minimum's is the group's
+  struct {
+    bool on = false;
+    u64 N = 0;
+    unsigned sector_bytes = 0, header_bits = 0, best_header_bits = 0;
+    u64 *d_best = nullptr;             // [MPC_PACK_DEV_LEN]; exists if the best-of was on when this was switched on
+    uint32_t *d_carry = nullptr;       // [2], as a handle's
+    int cur = 0;
+    u64 best_seen = 0;                 // lines that table has seen
+    hipEvent_t done = nullptr;
+    bool recorded = false;
+  } pack;
   hipEvent_t scratch_done = nullptr;
   bool recorded = false;
   std::string form, error;
@@ -814,7 +842,7 @@ bool accounts(const mpc_handle *h) { return h->acct.on && h->algorithm != Algo::
 bool in_best(const mpc_group *g, int i) { return g->best.on && std::find(g->best.set.begin(), g->best.set.end(), i) != g->best.set.end(); }
 
 // a handle whose sizes are wanted on the device, asked for by the caller or not
-bool needs_sizes(const mpc_handle *h) { return accounts(h) || h->cls.on; }
+bool needs_sizes(const mpc_handle *h) { return accounts(h) || h->cls.on || h->pack.on; }
 
 // ... a member whose sizes a group needs on the device, asked for by the caller or not
 bool group_accounts(const mpc_group *g, int i) { return needs_sizes(g->m[(size_t)i]) || in_best(g, i); }
@@ -865,6 +893,102 @@ const char *class_sector_refusal(unsigned L, unsigned sector_bytes)
   return nullptr;
 }
 
+// ---- pack accounting (mpc_pack.h) ----
+// the refusals of mpc_pack_stats_enable that need no device
+std::string pack_refusal(unsigned L, u64 block_lines, unsigned sector_bytes, unsigned header_bits)
+{
+  if (block_lines == 0) return "pack accounting: block_lines must be at least 1";
+  if (block_lines > MPC_PACK_MAX_BLOCK_LINES)
+    return "pack accounting: block_lines above " + std::to_string(MPC_PACK_MAX_BLOCK_LINES) + " (a block's bits are summed in 32 bits)";
+  const u64 block_bytes = block_lines * (u64)L;
+  if (sector_bytes == 0 || (u64)sector_bytes > block_bytes)
+    return "pack accounting: sector_bytes must be 1 .. block_lines x line_size (" + std::to_string(block_bytes) + ")";
+  if ((block_bytes + sector_bytes - 1) / sector_bytes > MPC_PACK_MAX_SECTORS)
+    return "pack accounting: a block of more than " + std::to_string(MPC_PACK_MAX_SECTORS) + " sectors (sector_bytes is too small for block_lines x line_size = " +
+           std::to_string(block_bytes) + ")";
+  if (header_bits > 65535u) return "pack accounting: header_bits must be 0 .. 65535";
+  return "";
+}
+
+std::string pack_values(u64 N, unsigned sb, unsigned hb)
+{
+  return "block_lines " + std::to_string(N) + ", sector_bytes " + std::to_string(sb) + ", header_bits " + std::to_string(hb);
+}
+
+// device table (mpc_pack.h) -> the ABI's table; open_lines / open_bits: the open block
+void pack_table_out(const std::vector<u64> &dev, u64 N, unsigned L, unsigned sb, unsigned hb, u64 open_lines, u64 open_bits, uint64_t *table)
+{
+  std::fill(table, table + MPC_PACK_TABLE_LEN, 0);
+  const u64 S = (N * (u64)L + sb - 1) / sb;
+  for (u64 k = 1; k <= S; k++) {
+    table[8 + k - 1] = dev[k];
+    table[0] += dev[k];
+    table[2] += dev[k] * k;
+  }
+  table[1] = dev[0];
+  table[3] = open_lines;
+  table[4] = open_bits;
+  table[5] = N;
+  table[6] = sb;
+  table[7] = hb;
+}
+
+// One pass behind the evaluators' launches of a chunk for `m` handles that count with the same values and stand at the
+// same line (the caller has checked), with the group's table of the per-line minimum over them when `g` is given.
+// Only a launch that begins or ends inside a block touches the carries, and only those are chained.
+int pack_pass(const Sink &k, const mpc_handle *grid_of, mpc_handle *const *hs, const uint16_t *const *d_sizes, int m, mpc_group *g, u64 n, hipStream_t s)
+{
+  const auto &P0 = hs[0]->pack;
+  const u64 N = P0.N, pos = P0.seen % N;
+  const bool loads = pos != 0, stores = (pos + n) % N != 0;
+  MpcPackArgs A{};
+  A.m = m;
+  A.block_lines = N;
+  A.pos = pos;
+  A.sector_bits = 8u * P0.sector_bytes;
+  A.max_sectors = (unsigned)((N * (u64)hs[0]->L + P0.sector_bytes - 1) / P0.sector_bytes);
+  A.header_bits = P0.header_bits;
+  for (int i = 0; i < m; i++) {
+    auto &P = hs[i]->pack;
+    A.sizes[i] = d_sizes[i];
+    if (!P.on) continue;
+    A.table[i] = P.d_tab;
+    A.carry_in[i] = P.d_carry + P.cur;
+    A.carry_out[i] = P.d_carry + (P.cur ^ 1);
+    if ((loads || stores) && P.recorded) HIPCHK(k, hipStreamWaitEvent(s, P.done, 0));
+  }
+  if (g) {
+    A.best = g->pack.d_best;
+    A.best_carry_in = g->pack.d_carry + g->pack.cur;
+    A.best_carry_out = g->pack.d_carry + (g->pack.cur ^ 1);
+    A.best_header_bits = g->pack.best_header_bits;
+    if ((loads || stores) && g->pack.recorded) HIPCHK(k, hipStreamWaitEvent(s, g->pack.done, 0));
+  }
+  const u64 blocks = (pos + n + N - 1) / N;
+  const u64 per_wg = N <= MPC_PACK_LANE_MAX ? 256 : N <= MPC_PACK_WAVE_MAX ? 4 : 1;
+  const hipError_t e = mpc_launch_pack(&A, n, grid_for(grid_of, (blocks + per_wg - 1) / per_wg, 1, 4), s);      // (the launcher sizes it down further)
+  if (e != hipSuccess) return k.fail(k.ctx, MPC_E_HIP, std::string("kernel launch (pack accounting): ") + hipGetErrorString(e));
+  for (int i = 0; i < m; i++) {
+    auto &P = hs[i]->pack;
+    if (!P.on) continue;
+    if (loads || stores) {
+      HIPCHK(k, hipEventRecord(P.done, s));
+      P.recorded = true;
+    }
+    if (stores) P.cur ^= 1;
+    P.seen += n;
+  }
+  if (g) {
+    if (loads || stores) {
+      HIPCHK(k, hipEventRecord(g->pack.done, s));
+      g->pack.recorded = true;
+    }
+    if (stores) g->pack.cur ^= 1;
+    g->pack.best_seen += n;
+  }
+  return MPC_OK;
+}
+
 // a staged or in-place chunk of a handle: the stager has asked for the sizes of a handle that accounts
 int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, const uint8_t *d_classes, hipStream_t s)
 {
@@ -872,16 +996,20 @@ int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_size
   if (rc != MPC_OK || n == 0 || !needs_sizes(h)) return rc;
   if (!d_sizes) return set_err(h, MPC_E_INVAL, "size accounting: the chunk has no sizes array");
   if (accounts(h)) rc = account(h, d_sizes, n, s);
-  if (rc != MPC_OK || !h->cls.on) return rc;
-  MpcClassArgs A{};
-  A.m = 1;
-  A.sizes[0] = d_sizes;
-  A.table[0] = h->cls.d_tab;
-  A.classes = d_classes;
-  class_sectors(A, (unsigned)h->L, h->cls.sector_bytes);
-  const hipError_t e = classes_pass(h, A, n, s);
-  if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch (class accounting): ") + hipGetErrorString(e));
-  return MPC_OK;
+  if (rc == MPC_OK && h->cls.on) {
+    MpcClassArgs A{};
+    A.m = 1;
+    A.sizes[0] = d_sizes;
+    A.table[0] = h->cls.d_tab;
+    A.classes = d_classes;
+    class_sectors(A, (unsigned)h->L, h->cls.sector_bytes);
+    const hipError_t e = classes_pass(h, A, n, s);
+    if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch (class accounting): ") + hipGetErrorString(e));
+  }
+  if (rc != MPC_OK || !h->pack.on) return rc;
+  mpc_handle *one[1] = {h};
+  const uint16_t *arr[1] = {d_sizes};
+  return pack_pass(sink_of(h), h, one, arr, 1, nullptr, n, s);
 }
 
 // The members' sizes of one chunk (one pointer per member, non-null for every member that group_accounts): first the
@@ -972,6 +1100,70 @@ int group_class_account(mpc_group *g, uint16_t *const *d_sizes, int8_t *const *d
   return A.m ? pass(A) : MPC_OK;
 }
 
+// The pack tables of one chunk, behind the other accounting passes.  A group with pack accounting on has its members at
+// one line with one set of values (group_pack_check): the best-of set in one launch (the minimum's table with the tables
+// of its members), then the other members, MPC_SIZES_MAX arrays a launch.  Else every member that counts on its own
+// takes a launch of its own, with its own values.
+int group_pack_account(mpc_group *g, uint16_t *const *d_sizes, u64 n, hipStream_t s)
+{
+  const Sink k = sink_of(g);
+  mpc_handle *hs[MPC_SIZES_MAX];
+  const uint16_t *arr[MPC_SIZES_MAX];
+  if (!g->pack.on) {
+    for (size_t i = 0; i < g->m.size(); i++) {
+      if (!g->m[i]->pack.on) continue;
+      hs[0] = g->m[i];
+      arr[0] = d_sizes[i];
+      const int rc = pack_pass(k, g->m[0], hs, arr, 1, nullptr, n, s);
+      if (rc != MPC_OK) return rc;
+    }
+    return MPC_OK;
+  }
+  const bool with_best = g->pack.d_best != nullptr;
+  int m = 0;
+  if (with_best) {
+    for (int i : g->best.set) {
+      hs[m] = g->m[(size_t)i];
+      arr[m++] = d_sizes[i];
+    }
+    const int rc = pack_pass(k, g->m[0], hs, arr, m, g, n, s);
+    if (rc != MPC_OK) return rc;
+    m = 0;
+  }
+  for (int i = 0; i < (int)g->m.size(); i++) {
+    if (with_best && in_best(g, i)) continue;
+    hs[m] = g->m[(size_t)i];
+    arr[m] = d_sizes[i];
+    if (++m == MPC_SIZES_MAX) {
+      const int rc = pack_pass(k, g->m[0], hs, arr, m, nullptr, n, s);
+      if (rc != MPC_OK) return rc;
+      m = 0;
+    }
+  }
+  return m ? pack_pass(k, g->m[0], hs, arr, m, nullptr, n, s) : MPC_OK;
+}
+
+// Before a group call feeds its members: with the group's pack accounting on they stand at one common line.
+int group_pack_check(mpc_group *g)
+{
+  if (!g->pack.on) return MPC_OK;
+  const u64 at = g->m[0]->pack.seen;
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const auto &P = g->m[i]->pack;
+    if (!P.on || P.N != g->pack.N || P.sector_bytes != g->pack.sector_bytes || P.header_bits != g->pack.header_bits)
+      return group_err(g, MPC_E_INVAL, "pack accounting: member " + std::to_string(i) + " does not count with the group's values (" +
+                                           pack_values(g->pack.N, g->pack.sector_bytes, g->pack.header_bits) + ")");
+    if (P.seen != at)
+      return group_err(g, MPC_E_INVAL, "pack accounting: member " + std::to_string(i) + " (" + algorithm_name(g->m[i]->algorithm) + ") is at line " +
+                                           std::to_string(P.seen) + ", member 0 at line " + std::to_string(at) +
+                                           ": a member was fed outside the group, its blocks no longer line up with the others' (reset the members to start over)");
+  }
+  if (g->pack.d_best && g->pack.best_seen != at)
+    return group_err(g, MPC_E_INVAL, "pack accounting: the members are at line " + std::to_string(at) + ", the table of the best-of at line " +
+                                         std::to_string(g->pack.best_seen) + ": the members were fed or reset outside the group (reset the members and mpc_group_best_reset to start over)");
+  return MPC_OK;
+}
+
 int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes,
                            hipStream_t s)
 {
@@ -986,7 +1178,8 @@ int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *c
   }
   if (!any) return MPC_OK;
   if (sizes) rc = group_account(g, d_sizes, n, s);
-  return rc == MPC_OK ? group_class_account(g, d_sizes, d_sel, d_classes, n, s) : rc;
+  if (rc == MPC_OK) rc = group_class_account(g, d_sizes, d_sel, d_classes, n, s);
+  return rc == MPC_OK ? group_pack_account(g, d_sizes, n, s) : rc;
 }
 
 // VPC: the size histogram is the sum over the clusters of the histogram in the raw statistics, clipped into MPC_SIZE_BINS bins
@@ -1398,6 +1591,9 @@ void mpc_destroy(mpc_handle *h)
   if (h->acct.d_scratch) (void)hipFree(h->acct.d_scratch);
   if (h->acct.scratch_done) (void)hipEventDestroy(h->acct.scratch_done);
   if (h->cls.d_tab) (void)hipFree(h->cls.d_tab);
+  if (h->pack.d_tab) (void)hipFree(h->pack.d_tab);
+  if (h->pack.d_carry) (void)hipFree(h->pack.d_carry);
+  if (h->pack.done) (void)hipEventDestroy(h->pack.done);
   delete h;
 }
 
@@ -1607,6 +1803,9 @@ void mpc_group_destroy(mpc_group *g)
   if (g->best.d_acc) (void)hipFree(g->best.d_acc);
   if (g->cls.d_best) (void)hipFree(g->cls.d_best);
   if (g->cls.d_scratch_sel) (void)hipFree(g->cls.d_scratch_sel);
+  if (g->pack.d_best) (void)hipFree(g->pack.d_best);
+  if (g->pack.d_carry) (void)hipFree(g->pack.d_carry);
+  if (g->pack.done) (void)hipEventDestroy(g->pack.done);
   for (uint16_t *p : g->d_scratch) if (p) (void)hipFree(p);
   if (g->scratch_done) (void)hipEventDestroy(g->scratch_done);
   delete g;
@@ -1621,6 +1820,7 @@ int mpc_group_compress_batch(mpc_group *g, const uint8_t *lines, uint64_t n, uin
   if (!g || (!lines && n)) return MPC_E_INVAL;
   if (n == 0) return MPC_OK;
   group_refresh(g);
+  if (const int prc = group_pack_check(g)) return prc;
   return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, nullptr, sizes, sel);
 }
 
@@ -1632,6 +1832,7 @@ static int group_batch_device(mpc_group *g, const void *d_lines, uint64_t n, con
   if (((uintptr_t)d_lines) & 15u) return group_err(g, MPC_E_INVAL, "device line buffer must be 16-byte aligned");
   HIPCHK(g, hipSetDevice(g->stage.device));
   hipStream_t s = (hipStream_t)hip_stream;
+  if (const int prc = group_pack_check(g)) return prc;
   const size_t nm = g->m.size();
   bool any = false, scratch = false;
   for (size_t i = 0; i < nm; i++) {
@@ -1678,6 +1879,7 @@ int mpc_group_compress_npy(mpc_group *g, const char *path, uint64_t first_row, u
 {
   if (!g || !path) return MPC_E_INVAL;
   group_refresh(g);
+  if (const int prc = group_pack_check(g)) return prc;
   return mpcstage::compress_npy(g->stage, sink_of(g), nullptr, path, first_row, n_rows, skip_last_row, rows_done);
 }
 
@@ -1685,6 +1887,7 @@ int mpc_group_compress_gpgpusim_log(mpc_group *g, const char *log_path, uint64_t
 {
   if (!g || !log_path) return MPC_E_INVAL;
   group_refresh(g);
+  if (const int prc = group_pack_check(g)) return prc;
   return mpcstage::compress_gpgpusim_log(g->stage, sink_of(g), nullptr, log_path, requests_read, lines_done);
 }
 
@@ -1766,6 +1969,9 @@ int mpc_stats_reset(mpc_handle *h)
   if (h->acct.on) h->acct.vpc_base.assign(h->acct.vpc_base.size(), 0);
   if (h->cls.d_tab) HIPCHK(h, hipMemset(h->cls.d_tab, 0, MPC_CLASS_TABLE_LEN * sizeof(u64)));
   h->cls.extra.assign(h->cls.extra.size(), 0);
+  if (h->pack.d_tab) HIPCHK(h, hipMemset(h->pack.d_tab, 0, MPC_PACK_DEV_LEN * sizeof(u64)));
+  h->pack.extra.assign(h->pack.extra.size(), 0);
+  h->pack.seen = 0;                   // (the open block goes with the position: its carry is read only behind a launch that wrote it)
   h->extra.assign(h->stats_len, 0);
   h->sc2.lines = h->sc2.warm = 0;     // SC2: the table and the line counter stay (C-Pack in blocks: the open block and the position in it)
   return MPC_OK;
@@ -1884,6 +2090,8 @@ int mpc_group_best_reset(mpc_group *g)
   if (rc != MPC_OK) return rc;
   HIPCHK(g, hipMemset(g->best.d_acc, 0, MPC_SIZES_BEST_LEN * sizeof(u64)));
   if (g->cls.d_best) HIPCHK(g, hipMemset(g->cls.d_best, 0, MPC_CLASS_TABLE_LEN * sizeof(u64)));
+  if (g->pack.d_best) HIPCHK(g, hipMemset(g->pack.d_best, 0, MPC_PACK_DEV_LEN * sizeof(u64)));
+  g->pack.best_seen = 0;
   return MPC_OK;
 }
 
@@ -1905,6 +2113,205 @@ int mpc_size_sectors(const uint64_t *bins, size_t n, unsigned line_size, unsigne
   if (total_sectors) *total_sectors = sectors;
   if (ratio) *ratio = sectors ? (double)(lines * most) / (double)sectors : 0.0;
   return MPC_OK;
+}
+
+
+// ---- pack accounting (include/mpc_hip_pack.h) ------------------------------------
+namespace {
+const char *const kPackOff = "pack accounting is not switched on for this handle (mpc_pack_stats_enable)";
+const char *const kGroupPackOff = "pack accounting is not switched on for this group (mpc_group_pack_stats_enable)";
+const char *const kPackTableLen = "a pack table has MPC_PACK_TABLE_LEN (8 + 1024 = 1032) entries";
+
+u64 pack_sectors_of(u64 bits, u64 sector_bytes, u64 cap)
+{
+  return std::min(std::max<u64>(1, (bits + 8 * sector_bytes - 1) / (8 * sector_bytes)), cap);
+}
+}  // namespace
+
+int mpc_pack_check_values(unsigned line_size, uint64_t block_lines, unsigned sector_bytes, unsigned header_bits)
+{
+  const std::string why = line_size == 0 ? std::string("pack accounting: line_size must be at least 1") : pack_refusal(line_size, block_lines, sector_bytes, header_bits);
+  return why.empty() ? MPC_OK : set_err(nullptr, MPC_E_INVAL, why);
+}
+
+int mpc_pack_stats_enable(mpc_handle *h, uint64_t block_lines, unsigned sector_bytes, unsigned header_bits)
+{
+  if (!h) return MPC_E_INVAL;
+  if (h->algorithm == Algo::Fit) return set_err(h, MPC_E_INVAL, "Fit: an analysis has no per-line sizes to account");
+  const std::string why = pack_refusal((unsigned)h->L, block_lines, sector_bytes, header_bits);
+  if (!why.empty()) return set_err(h, MPC_E_INVAL, why);
+  auto &P = h->pack;
+  if (P.on) {
+    if (P.N == block_lines && P.sector_bytes == sector_bytes && P.header_bits == header_bits) return MPC_OK;
+    return set_err(h, MPC_E_INVAL, "pack accounting is already on with " + pack_values(P.N, P.sector_bytes, P.header_bits));
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (hipMalloc((void **)&P.d_tab, MPC_PACK_DEV_LEN * sizeof(u64)) != hipSuccess) {
+    P.d_tab = nullptr;
+    return set_err(h, MPC_E_NOMEM, "hipMalloc(pack table) failed");
+  }
+  if (!P.d_carry && hipMalloc((void **)&P.d_carry, 2 * sizeof(uint32_t)) != hipSuccess) {
+    P.d_carry = nullptr;
+    (void)hipFree(P.d_tab);
+    P.d_tab = nullptr;
+    return set_err(h, MPC_E_NOMEM, "hipMalloc(pack carry) failed");
+  }
+  HIPCHK(h, hipMemset(P.d_tab, 0, MPC_PACK_DEV_LEN * sizeof(u64)));
+  HIPCHK(h, hipMemset(P.d_carry, 0, 2 * sizeof(uint32_t)));
+  if (!P.done) HIPCHK(h, hipEventCreateWithFlags(&P.done, hipEventDisableTiming));
+  HIPCHK(h, hipDeviceSynchronize());   // (the kernels run on non-blocking streams)
+  P.extra.assign(MPC_PACK_DEV_LEN, 0);
+  P.N = block_lines;
+  P.sector_bytes = sector_bytes;
+  P.header_bits = header_bits;
+  P.seen = 0;
+  P.cur = 0;
+  P.recorded = false;
+  h->stage.account[0] = 1;
+  P.on = true;
+  return MPC_OK;
+}
+
+int mpc_pack_stats_get(mpc_handle *h, uint64_t *table, size_t n)
+{
+  if (!h) return MPC_E_INVAL;
+  if (!h->pack.on) return set_err(h, MPC_E_INVAL, kPackOff);
+  if (!table || n != MPC_PACK_TABLE_LEN) return set_err(h, MPC_E_INVAL, kPackTableLen);
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = sync_all(h);
+  if (rc != MPC_OK) return rc;
+  HIPCHK(h, hipDeviceSynchronize());   // callers may have used their own streams
+  rc = pattern_status(h);
+  if (rc != MPC_OK) return rc;
+  const auto &P = h->pack;
+  std::vector<u64> dev(MPC_PACK_DEV_LEN);
+  HIPCHK(h, hipMemcpy(dev.data(), P.d_tab, MPC_PACK_DEV_LEN * sizeof(u64), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < dev.size(); i++) dev[i] += P.extra[i];
+  uint32_t open_bits = 0;
+  if (P.seen % P.N) HIPCHK(h, hipMemcpy(&open_bits, P.d_carry + P.cur, sizeof(open_bits), hipMemcpyDeviceToHost));
+  pack_table_out(dev, P.N, (unsigned)h->L, P.sector_bytes, P.header_bits, P.seen % P.N, open_bits, table);
+  return MPC_OK;
+}
+
+int mpc_pack_stats_merge(mpc_handle *h, const uint64_t *table, size_t n)
+{
+  if (!h) return MPC_E_INVAL;
+  auto &P = h->pack;
+  if (!P.on) return set_err(h, MPC_E_INVAL, kPackOff);
+  if (!table || n != MPC_PACK_TABLE_LEN) return set_err(h, MPC_E_INVAL, kPackTableLen);
+  if (table[5] != P.N || table[6] != P.sector_bytes || table[7] != P.header_bits)
+    return set_err(h, MPC_E_INVAL, "pack accounting: the table counts with other values than this handle (" + pack_values(P.N, P.sector_bytes, P.header_bits) + ")");
+  if (table[3] >= P.N || table[4] > 0xffffffffull) return set_err(h, MPC_E_INVAL, "pack accounting: the table's open block is not one of this block size");
+  if (table[3] && P.seen % P.N)
+    return set_err(h, MPC_E_INVAL, "pack accounting: both sides have an open block (" + std::to_string(P.seen % P.N) + " and " + std::to_string(table[3]) +
+                                       " lines); cut shards at multiples of block_lines, so that only the last has a tail");
+  if (table[3]) {       // take the shard's open block over: the next line continues it
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = sync_all(h);
+    if (rc != MPC_OK) return rc;
+    HIPCHK(h, hipDeviceSynchronize());
+    const uint32_t bits = (uint32_t)table[4];
+    HIPCHK(h, hipMemcpy(P.d_carry + P.cur, &bits, sizeof(bits), hipMemcpyHostToDevice));
+    P.seen += table[3];
+  }
+  P.extra[0] += table[1];
+  for (size_t k = 1; k <= MPC_PACK_MAX_SECTORS; k++) P.extra[k] += table[8 + k - 1];
+  return MPC_OK;
+}
+
+int mpc_pack_sectors_of_tail(const uint64_t *table, size_t n, unsigned line_size, uint64_t *tail_sectors, uint64_t *tail_cap)
+{
+  if (!table || n != MPC_PACK_TABLE_LEN || line_size == 0 || table[6] == 0 || table[5] == 0 || table[3] >= table[5]) return MPC_E_INVAL;
+  u64 sectors = 0, cap = 0;
+  if (table[3]) {
+    cap = (table[3] * (u64)line_size + table[6] - 1) / table[6];
+    sectors = pack_sectors_of(table[4] + table[7], table[6], cap);
+  }
+  if (tail_sectors) *tail_sectors = sectors;
+  if (tail_cap) *tail_cap = cap;
+  return MPC_OK;
+}
+
+int mpc_group_pack_stats_enable(mpc_group *g, uint64_t block_lines, unsigned sector_bytes, unsigned header_bits)
+{
+  if (!g) return MPC_E_INVAL;
+  const std::string why = pack_refusal((unsigned)g->stage.L, block_lines, sector_bytes, header_bits);
+  if (!why.empty()) return group_err(g, MPC_E_INVAL, why);
+  auto &G = g->pack;
+  if (G.on) {
+    if (G.N == block_lines && G.sector_bytes == sector_bytes && G.header_bits == header_bits) return MPC_OK;
+    return group_err(g, MPC_E_INVAL, "pack accounting is already on with " + pack_values(G.N, G.sector_bytes, G.header_bits));
+  }
+  // every member fresh (it starts at line 0), or on with the same values; then all at one line
+  bool first = true;
+  u64 at = 0;
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const auto &P = g->m[i]->pack;
+    if (g->m[i]->algorithm == Algo::Fit) return group_err(g, MPC_E_INVAL, "Fit: an analysis has no per-line sizes to account");
+    if (P.on && (P.N != block_lines || P.sector_bytes != sector_bytes || P.header_bits != header_bits))
+      return group_err(g, MPC_E_INVAL, "pack accounting: member " + std::to_string(i) + " already counts with " + pack_values(P.N, P.sector_bytes, P.header_bits));
+    const u64 seen = P.on ? P.seen : 0;
+    if (!first && seen != at)
+      return group_err(g, MPC_E_INVAL, "pack accounting: member " + std::to_string(i) + " is at line " + std::to_string(seen) + ", the members before it at line " +
+                                           std::to_string(at) + " (reset the members first)");
+    at = seen;
+    first = false;
+  }
+  if (g->best.on && at % block_lines)
+    return group_err(g, MPC_E_INVAL, "pack accounting: the members are " + std::to_string(at % block_lines) +
+                                         " lines into a block, where the table of the best-of cannot begin (reset the members first)");
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const int rc = mpc_pack_stats_enable(g->m[i], block_lines, sector_bytes, header_bits);
+    if (rc != MPC_OK) return group_err(g, rc, "member " + std::to_string(i) + " (" + algorithm_name(g->m[i]->algorithm) + "): " + g->m[i]->error);
+  }
+  if (g->best.on) {
+    unsigned tag_bits = 0;
+    while ((1u << tag_bits) < g->best.set.size()) tag_bits++;
+    HIPCHK(g, hipSetDevice(g->stage.device));
+    if (hipMalloc((void **)&G.d_best, MPC_PACK_DEV_LEN * sizeof(u64)) != hipSuccess) {
+      G.d_best = nullptr;
+      return group_err(g, MPC_E_NOMEM, "hipMalloc(pack table of the best-of) failed");
+    }
+    if (!G.d_carry) HIPCHK(g, hipMalloc((void **)&G.d_carry, 2 * sizeof(uint32_t)));
+    HIPCHK(g, hipMemset(G.d_best, 0, MPC_PACK_DEV_LEN * sizeof(u64)));
+    HIPCHK(g, hipMemset(G.d_carry, 0, 2 * sizeof(uint32_t)));
+    if (!G.done) HIPCHK(g, hipEventCreateWithFlags(&G.done, hipEventDisableTiming));
+    HIPCHK(g, hipDeviceSynchronize());   // (the kernels run on non-blocking streams)
+    G.best_header_bits = header_bits + (unsigned)block_lines * tag_bits;
+    G.best_seen = at;
+    G.cur = 0;
+    G.recorded = false;
+  }
+  G.N = block_lines;
+  G.sector_bytes = sector_bytes;
+  G.header_bits = header_bits;
+  G.on = true;
+  return MPC_OK;
+}
+
+int mpc_group_pack_stats_get(mpc_group *g, int member, uint64_t *table, size_t n)
+{
+  if (!g) return MPC_E_INVAL;
+  auto &G = g->pack;
+  if (!G.on) return group_err(g, MPC_E_INVAL, kGroupPackOff);
+  if (!table || n != MPC_PACK_TABLE_LEN) return group_err(g, MPC_E_INVAL, kPackTableLen);
+  if (member != MPC_PACK_BEST && (member < 0 || member >= (int)g->m.size()))
+    return group_err(g, MPC_E_INVAL, "pack accounting: member " + std::to_string(member) + " is not a member of the group or MPC_PACK_BEST");
+  if (member == MPC_PACK_BEST && !G.d_best)
+    return group_err(g, MPC_E_INVAL, "pack accounting: the best-of was not on when the group's pack accounting was switched on (mpc_group_best_enable first)");
+  int rc = mpc_group_sync(g);
+  if (rc != MPC_OK) return rc;
+  if (member == MPC_PACK_BEST) {
+    std::vector<u64> dev(MPC_PACK_DEV_LEN);
+    HIPCHK(g, hipMemcpy(dev.data(), G.d_best, MPC_PACK_DEV_LEN * sizeof(u64), hipMemcpyDeviceToHost));
+    uint32_t open_bits = 0;
+    if (G.best_seen % G.N) HIPCHK(g, hipMemcpy(&open_bits, G.d_carry + G.cur, sizeof(open_bits), hipMemcpyDeviceToHost));
+    pack_table_out(dev, G.N, (unsigned)g->stage.L, G.sector_bytes, G.best_header_bits, G.best_seen % G.N, open_bits, table);
+    return MPC_OK;
+  }
+  mpc_handle *h = g->m[(size_t)member];
+  rc = mpc_pack_stats_get(h, table, n);
+  return rc == MPC_OK ? rc : group_err(g, rc, "member " + std::to_string(member) + " (" + algorithm_name(h->algorithm) + "): " + h->error);
 }
 
 // ---- per-class accounting (include/mpc_hip_classes.h) ----------------------------
@@ -2034,6 +2441,7 @@ int mpc_group_compress_batch_classed(mpc_group *g, const uint8_t *lines, uint64_
     return group_err(g, MPC_E_INVAL, "class accounting: the classes come from member " + std::to_string(g->cls.from_member) + ", the call must not bring its own");
   if (n == 0) return MPC_OK;
   group_refresh(g);
+  if (const int prc = group_pack_check(g)) return prc;
   return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, classes, sizes, sel);
 }
 

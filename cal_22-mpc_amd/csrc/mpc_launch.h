@@ -2,12 +2,12 @@
 //
 // The launchers have C linkage, so a declaration that drifted from its definition would still link and then misbehave.
 // This header is therefore included by the callers (mpc_capi.hip, mpc_jit.h) AND by the units that define the
-// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_fit.hip, mpc_sizes.hip, mpc_classes.hip, the host section of mpc_vpc_lane.hip):
+// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_fit.hip, mpc_sizes.hip, mpc_classes.hip, mpc_pack.hip, the host section of mpc_vpc_lane.hip):
 // the compiler sees declaration and definition together and refuses a mismatch.  Host code only -- the run-time
 // compiled source of mpc_jit.h (-DMPC_LANE_JIT) never sees it, and it is not one of the files that key the code
 // object cache.
 //
-// The parameter blocks are only named here (their definitions: mpc_device.h, mpc_sc2.h, mpc_pattern.h, mpc_sizes.h, mpc_classes.h).
+// The parameter blocks are only named here (their definitions: mpc_device.h, mpc_sc2.h, mpc_pattern.h, mpc_sizes.h, mpc_classes.h, mpc_pack.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -20,6 +20,7 @@ struct MpcPatternSet;
 struct MpcEvictSet;
 struct MpcSizesArgs;
 struct MpcClassArgs;
+struct MpcPackArgs;
 
 extern "C" {
 // mpc_kernels.hip
@@ -104,4 +105,9 @@ hipError_t mpc_launch_sizes(const MpcSizesArgs *A, unsigned long long n_lines, i
 // mpc_classes.hip: the per-class tables of the sizes of n_lines lines (mpc_classes.h); cut into launches as mpc_launch_sizes is
 int mpc_classes_wg_per_cu(const MpcClassArgs *A);
 hipError_t mpc_launch_classes(const MpcClassArgs *A, unsigned long long n_lines, int grid, hipStream_t stream);
+
+// mpc_pack.hip: the sector histograms of blocks of N lines over the sizes of n_lines lines (mpc_pack.h); one launch, never cut.
+// `grid` bounds the workgroups; the launcher sizes them down to the blocks.  The name of the kernel form a block size takes.
+const char *mpc_pack_form_name(unsigned long long block_lines);
+hipError_t mpc_launch_pack(const MpcPackArgs *A, unsigned long long n_lines, int grid, hipStream_t stream);
 }

@@ -88,6 +88,22 @@ ClassReport CompressorSet::GetClassStats(size_t i)
   return report;
 }
 
+void CompressorSet::EnablePackStats(unsigned long long blockLines, unsigned sectorBytes, unsigned headerBits)
+{
+  Prepare();
+  int rc = mpc_group_pack_stats_enable(m_Group, blockLines, sectorBytes, headerBits);
+  if (rc != MPC_OK) fail("CompressorSet::EnablePackStats", rc, mpc_group_last_error(m_Group));
+}
+
+PackReport CompressorSet::GetPackStats(size_t i)
+{
+  Prepare();
+  PackReport report(GetLineSize());
+  int rc = mpc_group_pack_stats_get(m_Group, i == BestMember ? MPC_PACK_BEST : (int)i, report.Table.data(), report.Table.size());
+  if (rc != MPC_OK) fail("CompressorSet::GetPackStats", rc, mpc_group_last_error(m_Group));
+  return report;
+}
+
 void CompressorSet::SetLogClassField(int field)
 {
   int rc = mpc_group_class_log_field(m_Group, field);

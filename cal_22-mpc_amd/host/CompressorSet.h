@@ -11,6 +11,7 @@
 
 #include "Compressor.h"
 #include "ClassReport.h"
+#include "PackReport.h"
 #include "SizeReport.h"
 
 struct mpc_group;
@@ -52,6 +53,11 @@ public:
   void SetLogClassField(int field);
   // the class of a line is member i's selected + 1: a VPC member's cluster + 1, 0 = uncompressed (mpc_group_class_from_member)
   void ClassFromMember(size_t i);
+  // ADDITIVE: EnablePackStats for every member with the same values; after EnableBest also a table of the per-line smallest
+  // size, counted with headerBits + blockLines x tag bits (mpc_group_pack_stats_enable); off by default
+  void EnablePackStats(unsigned long long blockLines, unsigned sectorBytes = ACCESS_GRAN, unsigned headerBits = 0);
+  // member i's table, or with i == BestMember that of the per-line smallest size
+  PackReport GetPackStats(size_t i);
 
 private:
   void Prepare();      // members' buffered lines first

@@ -99,6 +99,22 @@ ClassReport DeviceCompressor::GetClassStats()
   return report;
 }
 
+void DeviceCompressor::EnablePackStats(unsigned long long blockLines, unsigned sectorBytes, unsigned headerBits)
+{
+  FlushLines();
+  int rc = mpc_pack_stats_enable(m_Handle, blockLines, sectorBytes, headerBits);
+  if (rc != MPC_OK) Fail(m_Tag + "::EnablePackStats", rc);
+}
+
+PackReport DeviceCompressor::GetPackStats()
+{
+  FlushLines();
+  PackReport report(m_LineSize);
+  int rc = mpc_pack_stats_get(m_Handle, report.Table.data(), report.Table.size());
+  if (rc != MPC_OK) Fail(m_Tag + "::GetPackStats", rc);
+  return report;
+}
+
 void DeviceCompressor::SetLogClassField(int field)
 {
   int rc = mpc_class_log_field(m_Handle, field);

@@ -8,6 +8,7 @@
 
 #include "Compressor.h"
 #include "ClassReport.h"
+#include "PackReport.h"
 #include "SizeReport.h"
 
 namespace comp
@@ -40,6 +41,11 @@ public:
   ClassReport GetClassStats();
   // which field of a .log record is the class of its line: MPC_CLASS_LOG_NONE / _KERNEL / _RW / _MFTYPE (mpc_class_log_field)
   void SetLogClassField(int field);
+  // ADDITIVE: count, from now on, the sectors that blocks of blockLines consecutive lines occupy when they are packed and
+  // rounded up once, headerBits added per block (mpc_pack_stats_enable); off by default
+  void EnablePackStats(unsigned long long blockLines, unsigned sectorBytes = ACCESS_GRAN, unsigned headerBits = 0);
+  // ... that table (mpc_pack_stats_get), buffered lines evaluated first; a failure (not enabled) exits like every other
+  PackReport GetPackStats();
 
 protected:
   // tag: the short name in front of this class's messages ("BDI", "VPC", ...)

@@ -16,6 +16,10 @@
 // cluster takes it from the first VPC member of a list (its cluster + 1, 0 = uncompressed).  With a list every member
 // gets its file, and with --size-histogram the per-line best of the list BEST_results_classes.csv.  --sector sets the
 // sector size of these files too.  Without --by nothing changes.
+// ADDITIVE: --pack N [--sector BYTES] [--pack-header BITS] also writes OUTDIR/<stem>_results_pack.csv (comp::PackReport: the
+// sectors that blocks of N consecutive lines occupy when they are packed and rounded up once).  With a list every member
+// gets its file, and with --size-histogram the per-line best of the list BEST_results_pack.csv.  Next to --pack, --sector
+// does not imply --size-histogram.  Without --pack nothing changes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,6 +56,10 @@ static const char *kHelp =
     "                       per-line best of the list (BEST_results_sizes.csv)\n"
     "      --sector arg     Sector size in bytes for that file. Default=32\n"
     "                       (implies --size-histogram)\n"
+    "      --pack arg       Also write <stem>_results_pack.csv: the sectors that blocks\n"
+    "                       of that many consecutive lines occupy when packed; the\n"
+    "                       sector size is --sector's (which then implies nothing).\n"
+    "      --pack-header arg Bits added to every block of --pack. Default=0\n"
     "      --by arg         Also write <stem>_results_classes.csv: lines, bits and\n"
     "                       sectors per class of a line [kernel/rw/mftype/cluster].\n"
     "                       kernel, rw, mftype: a field of a .log trace's records;\n"
@@ -67,7 +75,19 @@ struct Args {
   unsigned sector = ACCESS_GRAN;        // ADDITIVE --sector BYTES: the sector size of that file; implies --size-histogram
   std::string by;                       // ADDITIVE --by kernel|rw|mftype|cluster: <stem>_results_classes.csv (ClassReport.h); empty: off
   bool has_by = false;
+  bool has_sector = false;
+  bool has_pack = false, has_pack_header = false;      // ADDITIVE --pack N [--pack-header BITS]: <stem>_results_pack.csv (PackReport.h)
+  unsigned long long pack = 0;
+  unsigned pack_header = 0;
 };
+
+// the value of --pack / --pack-header: digits only, up to `most`
+static bool takeNumber(const std::string &value, unsigned long long most, unsigned long long &out)
+{
+  char *end = nullptr;
+  out = strtoull(value.c_str(), &end, 10);
+  return !value.empty() && value[0] >= '0' && value[0] <= '9' && *end == 0 && value.size() <= 19 && out <= most;
+}
 
 static bool take_value(int argc, char **argv, int &i, const std::string &arg, const char *shortf, const char *longf,
                        std::string &out, bool &seen)
@@ -135,6 +155,26 @@ static void requireSector(const Args &a, unsigned traceLineSize)
     printf("--by with --sector %u: the trace's %u-byte lines have more than %zu sectors.\n", a.sector, traceLineSize, comp::ClassReport::Row - 2);
     exit(1);
   }
+}
+
+// --pack against the trace: a sector is at most a block, a block at most 1024 sectors
+static void requirePack(const Args &a, unsigned traceLineSize)
+{
+  if (!a.has_pack) return;
+  const unsigned long long blockBytes = a.pack * traceLineSize;
+  if (a.sector > blockBytes) {
+    printf("--pack %llu with --sector %u: a sector cannot be larger than a block of %llu bytes.\n", a.pack, a.sector, blockBytes);
+    exit(1);
+  }
+  if ((blockBytes + a.sector - 1) / a.sector > comp::PackReport::MaxSectors) {
+    printf("--pack %llu with --sector %u: a block of %llu bytes has more than %zu sectors.\n", a.pack, a.sector, blockBytes, comp::PackReport::MaxSectors);
+    exit(1);
+  }
+}
+
+static void writePack(comp::PackReport report, const std::string &workloadName, const std::string &outputDirPath, const std::string &saveFileName)
+{
+  report.Print(workloadName, outputDirPath + "/" + saveFileName + "_results_pack.csv");
 }
 
 // --by kernel|rw|mftype: the field of a .log record (MPC_CLASS_LOG_*); 0 for cluster
@@ -233,7 +273,35 @@ int main(int argc, char **argv)
         return 1;
       }
       a.sector = (unsigned)bytes;
-      a.size_histogram = true;
+      a.has_sector = true;
+      continue;
+    }
+    if (arg == "--pack" || arg.compare(0, 7, "--pack=") == 0) {
+      if (arg == "--pack" && i + 1 >= argc) {
+        std::cout << "Option 'pack' is missing an argument" << std::endl;
+        exit(1);
+      }
+      const std::string value = arg == "--pack" ? argv[++i] : arg.substr(7);
+      if (!takeNumber(value, 1ull << 19, a.pack) || a.pack == 0) {
+        std::cout << "--pack takes a number of lines from 1 to 524288, not \"" << value << "\"." << std::endl;
+        return 1;
+      }
+      a.has_pack = true;
+      continue;
+    }
+    if (arg == "--pack-header" || arg.compare(0, 14, "--pack-header=") == 0) {
+      if (arg == "--pack-header" && i + 1 >= argc) {
+        std::cout << "Option 'pack-header' is missing an argument" << std::endl;
+        exit(1);
+      }
+      const std::string value = arg == "--pack-header" ? argv[++i] : arg.substr(14);
+      unsigned long long bits = 0;
+      if (!takeNumber(value, 65535, bits)) {
+        std::cout << "--pack-header takes a number of bits from 0 to 65535, not \"" << value << "\"." << std::endl;
+        return 1;
+      }
+      a.pack_header = (unsigned)bits;
+      a.has_pack_header = true;
       continue;
     }
     if (arg == "--by" || arg.compare(0, 5, "--by=") == 0) {
@@ -252,6 +320,7 @@ int main(int argc, char **argv)
     std::cout << "Option '" << arg << "' does not exist" << std::endl;
     return 1;
   }
+  if (a.has_sector && !a.has_pack) a.size_histogram = true;      // (--sector implies --size-histogram, but not next to --pack)
   std::string algorithm = a.has_algorithm ? a.algorithm : "VPC";
   bool help = a.help;
   if (!a.has_input) help = true;
@@ -302,12 +371,22 @@ int main(int argc, char **argv)
       return 1;
     }
   }
+  // --pack: checked before anything is opened or written, one message each
+  if (a.has_pack_header && !a.has_pack) {
+    std::cout << "--pack-header adds bits to the blocks of --pack: give --pack N too." << std::endl;
+    return 1;
+  }
+  if (a.has_pack && a.per_line) {
+    std::cout << "--pack is evaluated in batches: it does not go with --per-line / --line-buffer." << std::endl;
+    return 1;
+  }
   const std::string tracePath = a.input, configPath = a.config, outputDirPath = a.has_output ? a.output : "";
   if (!list.empty()) return runList(list, tracePath, configPath, outputDirPath, a);
 
   trace::MemReq_t *memReq = nullptr;
   trace::Loader *loader = openTrace(tracePath, &memReq);
   requireSector(a, loader->GetCachelineSize());
+  requirePack(a, loader->GetCachelineSize());
 
   comp::DeviceCompressor *compressor = makeEvaluator(algorithm, configPath, loader->GetCachelineSize());
   if (!compressor) {
@@ -326,6 +405,7 @@ int main(int argc, char **argv)
     compressor->EnableClassStats(a.sector);
     compressor->SetLogClassField(logFieldOf(a.by));
   }
+  if (a.has_pack) compressor->EnablePackStats(a.pack, a.sector, a.pack_header);
   if (!a.per_line && (loader->SupportsBatch() || !loader->GetStreamablePath().empty()))
     compressBatches(compressor, loader);
   else
@@ -338,6 +418,7 @@ int main(int argc, char **argv)
   writeResults(compStat, workloadName, outputDirPath, saveFileName);
   if (a.size_histogram) writeSizes(compressor->GetSizeHistogram(a.sector), workloadName, outputDirPath, saveFileName);
   if (a.has_by) writeClasses(compressor->GetClassStats(), workloadName, outputDirPath, saveFileName);
+  if (a.has_pack) writePack(compressor->GetPackStats(), workloadName, outputDirPath, saveFileName);
 
   delete memReq;      // (the reference leaks its request object)
   delete loader;
@@ -358,6 +439,7 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
   trace::Loader *loader = openTrace(tracePath, &memReq);
   const unsigned lineSize = loader->GetCachelineSize();
   requireSector(a, lineSize);
+  requirePack(a, lineSize);
   std::vector<comp::DeviceCompressor *> evaluators;
   std::vector<comp::Compressor *> members;
   for (const std::string &n : names) {
@@ -379,6 +461,7 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
         set.SetLogClassField(logFieldOf(a.by));
       }
     }
+    if (a.has_pack) set.EnablePackStats(a.pack, a.sector, a.pack_header);      // (behind EnableBest: the best of the list gets its table)
     compressBatches(&set, loader);
     for (size_t i = 0; i < names.size(); i++) {
       comp::CompResult *compStat = set.GetResult(i);
@@ -387,12 +470,14 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
       writeResults(compStat, workloadName, outputDirPath, saveFileName);
       if (a.size_histogram) writeSizes(evaluators[i]->GetSizeHistogram(a.sector), workloadName, outputDirPath, saveFileName);
       if (a.has_by) writeClasses(set.GetClassStats(i), workloadName, outputDirPath, saveFileName);
+      if (a.has_pack) writePack(set.GetPackStats(i), workloadName, outputDirPath, saveFileName);
     }
     if (a.size_histogram) {
       const comp::BestReport best = set.GetBest(a.sector);
       std::cout << "BEST comp.ratio: " << mpctext::num(best.CompRatio()) << std::endl;
       writeSizes(best.Sizes, workloadName, outputDirPath, "BEST");
       if (a.has_by) writeClasses(set.GetClassStats(comp::CompressorSet::BestMember), workloadName, outputDirPath, "BEST");
+      if (a.has_pack) writePack(set.GetPackStats(comp::CompressorSet::BestMember), workloadName, outputDirPath, "BEST");
     }
   }
   delete memReq;

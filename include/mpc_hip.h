@@ -380,6 +380,9 @@ int mpc_group_sync(mpc_group *g);
 /* ---- per-class accounting: an evaluator's lines, bits and sector counts broken down by a class byte per line ----
  * Additive and off by default as well, in a header of its own for the same reason.                                  */
 #include "mpc_hip_classes.h"
+/* ---- pack accounting: the sectors that blocks of N consecutive lines occupy when they are packed and rounded once ----
+ * Additive and off by default as well, in a header of its own for the same reason.                                  */
+#include "mpc_hip_pack.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -352,8 +352,12 @@ class _Evaluator:
         self.line_size = self.info.line_size
         self.stats_len = int(self.info.stats_len)
 
+    _sets = ()          # the open EvaluatorSets this evaluator is a member of
+
     def close(self) -> None:
         if self._h:
+            for s in list(self._sets):      # a group is destroyed before its members (mpc_group_destroy reads them)
+                s.close()
             lib().mpc_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -770,7 +774,9 @@ class EvaluatorSet:
     """A group of evaluators of one line size on one device that are fed together (``mpc_group``): the trace is
     staged once per chunk and every member sees every line as if it had been called alone.  The members keep their
     own statistics: read them with each member's ``result()`` / ``stats_vector()`` as usual.  The set borrows its
-    members; close it before them (it keeps them alive until then)."""
+    members and has to go before them: it keeps them alive until it is closed, and closing (or collecting) a member
+    closes every open set it belongs to first, in whatever order the garbage collector finalizes a forgotten set and
+    its members."""
 
     def __init__(self, evaluators):
         self.members = list(evaluators)
@@ -781,6 +787,8 @@ class EvaluatorSet:
         rc = lib().mpc_group_create(arr, len(self.members), C.byref(self._g))
         if rc != 0:
             raise MpcError(rc, (lib().mpc_group_last_error(None) or b"").decode())
+        for e in self.members:
+            e._sets = list(e._sets) + [self]
         self.line_size = self.members[0].line_size
 
     def _check(self, rc: int) -> None:
@@ -797,6 +805,8 @@ class EvaluatorSet:
         if self._g:
             lib().mpc_group_destroy(self._g)
             self._g = C.c_void_p()
+            for e in self.members:
+                e._sets = [s for s in e._sets if s is not self]
 
     def __del__(self):
         try:

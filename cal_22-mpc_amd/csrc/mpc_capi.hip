@@ -2585,6 +2585,32 @@ int mpc_test_routes(mpc_handle *h, uint64_t *out, size_t n)
   for (size_t i = 0; i < n; i++) out[i] = i < kRouteWords ? tmp[i] : 0;
   return MPC_OK;
 }
+
+// test library only: what the evicting Pattern set's launches did since the handle was created -- out[0..6) = launches,
+// rotations, first occurrences of gone lines, at-risk occurrences, at-risk misses, entries put on list B (the
+// MPC_ESET_T_* words of mpc_pattern.h, which only the test library's kernels count in); out[i] = 0 beyond
+int mpc_test_evict_counters(mpc_handle *h, uint64_t *out, size_t n)
+{
+  if (!h || !out || h->algorithm != Algo::Pattern || !h->pat.evicting) return MPC_E_INVAL;
+  if (hipSetDevice(h->device) != hipSuccess) return MPC_E_HIP;
+  HIPCHK(h, hipDeviceSynchronize());
+  uint64_t ctl[MPC_ESET_WORDS];
+  HIPCHK(h, hipMemcpy(ctl, h->pat.evict.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+  const uint64_t v[6] = {ctl[MPC_ESET_SEQ], ctl[MPC_ESET_T_ROTATIONS], ctl[MPC_ESET_T_GONE], ctl[MPC_ESET_T_RISK], ctl[MPC_ESET_T_RISK_MISS],
+                         ctl[MPC_ESET_T_LIST_B]};
+  for (size_t i = 0; i < n; i++) out[i] = i < 6 ? v[i] : 0;
+  return MPC_OK;
+}
+
+// test library only: the MPC_ELINE_* kind of the first n lines of the evicting set's most recent launch
+int mpc_test_evict_kinds(mpc_handle *h, uint8_t *out, size_t n)
+{
+  if (!h || !out || h->algorithm != Algo::Pattern || !h->pat.evicting || n > (size_t)h->pat.evict.launch_max) return MPC_E_INVAL;
+  if (hipSetDevice(h->device) != hipSuccess) return MPC_E_HIP;
+  HIPCHK(h, hipDeviceSynchronize());
+  if (n) HIPCHK(h, hipMemcpy(out, h->pat.evict.kind, n, hipMemcpyDeviceToHost));
+  return MPC_OK;
+}
 #endif
 
 #if MPC_STAMPS

@@ -68,6 +68,13 @@ enum {
   MPC_ESET_SEQ,            /* launches so far                                                                          */
   MPC_ESET_N_GONE,         /* this launch: first occurrences of gone lines                                             */
   MPC_ESET_N_RISK,         /* this launch: occurrences of at-risk lines                                                */
+  /* test library only (-DMPC_TESTING=1; mpc_test_evict_counters): sums over the launches since creation; the product's
+   * kernels never touch these words */
+  MPC_ESET_T_ROTATIONS,    /* launches that recycled the older table                                                   */
+  MPC_ESET_T_GONE,         /* first occurrences of gone lines                                                          */
+  MPC_ESET_T_RISK,         /* occurrences of at-risk lines                                                             */
+  MPC_ESET_T_RISK_MISS,    /* ... that missed                                                                          */
+  MPC_ESET_T_LIST_B,       /* entries put on list B: by the compare pass and, round after round, by the tail            */
   MPC_ESET_WORDS = 16
 };
 

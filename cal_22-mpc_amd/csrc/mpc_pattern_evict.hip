@@ -116,6 +116,9 @@ __global__ void evict_begin_kernel(MpcEvictSet S)
   if (rotate) {
     S.ctl[MPC_ESET_NEWER] ^= 1ull;
     S.ctl[MPC_ESET_I_ROT] = I;
+#if MPC_TESTING     // (test library only, here and below: sums over the launches for mpc_test_evict_counters, mpc_pattern.h)
+    S.ctl[MPC_ESET_T_ROTATIONS] += 1ull;
+#endif
   }
   S.ctl[MPC_ESET_ROTATE] = rotate ? 1ull : 0ull;
   S.ctl[MPC_ESET_I0] = I;
@@ -180,6 +183,9 @@ evict_compare_kernel(const u64 *__restrict__ lines, int w8, MpcEvictSet S)
     if (ev_resolve(S, T, O, lines, w8, e, slot) == EV_MEET) {
       const u32 at = (u32)atomicAdd(&S.ctl[MPC_ESET_PENDING_B], 1ull);
       if (at < S.launch_max) S.pend_b[at] = make_uint2(e.x, slot);
+#if MPC_TESTING
+      atomicAdd(&S.ctl[MPC_ESET_T_LIST_B], 1ull);
+#endif
     }
   }
 }
@@ -198,7 +204,12 @@ evict_tail_kernel(const u64 *__restrict__ lines, int w8, MpcEvictSet S)
     for (u32 k = threadIdx.x; k < n; k += kThreads) {
       const uint2 e = cur[k];
       u32 slot;
-      if (ev_resolve(S, T, O, lines, w8, e, slot) == EV_MEET) next[atomicAdd(&s_next, 1u)] = make_uint2(e.x, slot);
+      if (ev_resolve(S, T, O, lines, w8, e, slot) == EV_MEET) {
+        next[atomicAdd(&s_next, 1u)] = make_uint2(e.x, slot);
+#if MPC_TESTING
+        atomicAdd(&S.ctl[MPC_ESET_T_LIST_B], 1ull);
+#endif
+      }
     }
     __threadfence();
     __syncthreads();         // this round's lines, stamps and list are written: the next round may read them
@@ -343,6 +354,11 @@ evict_walk_kernel(u32 n_lines, MpcEvictSet S, u64 *gstats)
     S.ctl[MPC_ESET_INSERTIONS] = I0 + misses;
     if (misses) atomicAdd(&gstats[MPC_PAT_JOINED], misses);
     if (n_lines - misses) atomicAdd(&gstats[MPC_PAT_EXISTED], (u64)n_lines - misses);
+#if MPC_TESTING
+    S.ctl[MPC_ESET_T_GONE] += ev_ctl(S, MPC_ESET_N_GONE);
+    S.ctl[MPC_ESET_T_RISK] += (u64)n_risk;
+    S.ctl[MPC_ESET_T_RISK_MISS] += (u64)s_missed;
+#endif
   }
 }
 

@@ -107,6 +107,69 @@ def test_group_create_rejects_bad_sets_without_a_device():
     assert e.value.code == -22
 
 
+def test_a_set_is_destroyed_before_its_members_whoever_goes_first(monkeypatch):
+    """mpc_group_destroy reads the group's members, so the binding destroys a set before any of its members: when the
+    members are closed while a set that was never closed is still alive (held by the traceback of an exception one of
+    its methods raised, say), and when the garbage collector finalizes a forgotten set and its members in an order of
+    its own.  The library is a stand-in that records the order of the destroy calls."""
+    import gc
+    mpc = pkg()
+    alive, groups, order, wrong = set(), {}, [], []
+
+    class Lib:
+        def mpc_group_create(self, arr, n, out):
+            out._obj.value = 1000 + len(order) + len(groups)
+            groups[out._obj.value] = [arr[i] for i in range(n)]
+            return 0
+
+        def mpc_group_destroy(self, g):
+            wrong.extend(h for h in groups.pop(g.value) if h not in alive)
+            order.append("set")
+
+        def mpc_destroy(self, h):
+            alive.discard(h.value)
+            order.append("member")
+
+    monkeypatch.setattr(mpc, "lib", lambda: Lib())
+
+    def members():
+        out = []
+        for k in (len(alive) + 1, len(alive) + 2):
+            e = object.__new__(mpc.BDI)
+            e._h, e.line_size = C.c_void_p(k), 64
+            alive.add(k)
+            out.append(e)
+        return out
+
+    # closed in the right order: nothing is left behind
+    m = members()
+    s = mpc.EvaluatorSet(m)
+    s.close()
+    assert all(e._sets == [] for e in m)
+    for e in m:
+        e.close()
+    assert order == ["set", "member", "member"] and not wrong and not alive and not groups
+    # a set that is never closed and stays alive in a cycle, the members closed by hand
+    del order[:]
+    m = members()
+    s = mpc.EvaluatorSet(m)
+    s.cycle = s
+    del s
+    m[1].close()
+    assert order == ["set", "member"] and not m[0]._sets
+    m[0].close()
+    gc.collect()
+    assert order == ["set", "member", "member"] and not wrong and not alive and not groups
+    # two sets over the same members, everything forgotten: the collector's order
+    del order[:]
+    m = members()
+    s, t = mpc.EvaluatorSet(m), mpc.EvaluatorSet(m[:1])
+    s.cycle = s
+    del s, t, m, e
+    gc.collect()
+    assert sorted(order) == ["member", "member", "set", "set"] and not wrong and not alive and not groups
+
+
 def _gfx950_code_objects(lib_path):
     """The gfx950 entries of the clang offload bundles in the library's .hip_fatbin section."""
     with open(lib_path, "rb") as f:

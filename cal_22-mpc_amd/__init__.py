@@ -30,6 +30,9 @@ MPC_CLASS_BEST = -1           # mpc_group_class_stats_get: the best-of's table
 MPC_PACK_MAX_SECTORS = 1024   # a pack table is uint64[8 + 1024] (include/mpc_hip_pack.h)
 MPC_PACK_TABLE_LEN = 8 + MPC_PACK_MAX_SECTORS
 MPC_PACK_BEST = -1            # mpc_group_pack_stats_get: the table of the per-line minimum
+MPC_IMAGE_MAX_SECTORS = 1024  # an image table is uint64[16 + 1024] (include/mpc_hip_image.h)
+MPC_IMAGE_TABLE_LEN = 16 + MPC_IMAGE_MAX_SECTORS
+MPC_IMAGE_MAX_CAPACITY = 1 << 28
 CLASS_LOG_FIELDS = {None: 0, "kernel": 1, "rw": 2, "mftype": 3}      # MPC_CLASS_LOG_*
 MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2, MPC_PATH_PATTERN = 1, 2, 3, 4, 5, 6, 7
 MPC_PATH_PATTERN_EVICTING = 9
@@ -164,6 +167,16 @@ def lib() -> C.CDLL:
             "mpc_pack_sectors_of_tail": ([C.c_void_p, C.c_size_t, C.c_uint, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
             "mpc_group_pack_stats_enable": ([H, C.c_uint64, C.c_uint, C.c_uint], C.c_int),
             "mpc_group_pack_stats_get": ([H, C.c_int, C.c_void_p, C.c_size_t], C.c_int),
+            "mpc_image_stats_enable": ([H, C.c_uint64, C.c_uint64, C.c_uint, C.c_uint], C.c_int),
+            "mpc_image_check_values": ([C.c_uint, C.c_uint64, C.c_uint64, C.c_uint, C.c_uint], C.c_int),
+            "mpc_image_stats_get": ([H, C.c_void_p, C.c_size_t], C.c_int),
+            "mpc_compress_batch_addressed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "mpc_compress_batch_device_addressed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "mpc_image_hash": ([C.c_uint64], C.c_uint64),
+            "mpc_group_image_stats_enable": ([H, C.c_uint64, C.c_uint64, C.c_uint, C.c_uint], C.c_int),
+            "mpc_group_image_stats_get": ([H, C.c_int, C.c_void_p, C.c_size_t], C.c_int),
+            "mpc_group_compress_batch_addressed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "mpc_group_compress_batch_device_addressed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
         }
         for name, (args, res) in sigs.items():
             fn = getattr(L, name)
@@ -200,6 +213,10 @@ EXPORTED_CLASS_SYMBOLS = ["mpc_class_stats_enable", "mpc_class_stats_get", "mpc_
 # The pack accounting entry points, declared in include/mpc_hip_pack.h (which mpc_hip.h includes).
 EXPORTED_PACK_SYMBOLS = ["mpc_pack_stats_enable", "mpc_pack_check_values", "mpc_pack_stats_get", "mpc_pack_stats_merge", "mpc_pack_sectors_of_tail",
                          "mpc_group_pack_stats_enable", "mpc_group_pack_stats_get"]
+# The image accounting entry points, declared in include/mpc_hip_image.h (which mpc_hip.h includes).
+EXPORTED_IMAGE_SYMBOLS = ["mpc_image_stats_enable", "mpc_image_check_values", "mpc_image_stats_get", "mpc_compress_batch_addressed",
+                          "mpc_compress_batch_device_addressed", "mpc_image_hash", "mpc_group_image_stats_enable", "mpc_group_image_stats_get",
+                          "mpc_group_compress_batch_addressed", "mpc_group_compress_batch_device_addressed"]
 
 
 def gpgpusim_log_line_size(path: str) -> int:
@@ -249,6 +266,16 @@ def _as_classes(classes, n: int) -> np.ndarray:
     if arr.size and (int(arr.min()) < 0 or int(arr.max()) > 255):
         raise ValueError("classes: a class is an integer from 0 to 255")
     return np.ascontiguousarray(arr, dtype=np.uint8)
+
+
+def _as_addresses(addresses, n: int) -> np.ndarray:
+    """The ``addresses=`` argument of ``compress_lines``: one uint64 per line, C-contiguous."""
+    arr = np.asarray(addresses)
+    if arr.shape != (n,) or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"addresses: {n} unsigned 64-bit integers, one per line")
+    if arr.dtype != np.uint64 and arr.size and int(arr.min()) < 0:
+        raise ValueError("addresses: an address is an unsigned 64-bit integer")
+    return np.ascontiguousarray(arr, dtype=np.uint64)
 
 
 def _class_log_field(field) -> int:
@@ -312,6 +339,45 @@ def pack_table_view(table: np.ndarray, line_size: int, close_tail: bool = True) 
             "sector_ratio_closed": blocks * S / sectors if sectors else 0.0}
 
 
+def _image_values(fn: str, capacity, block_lines, sector_bytes, header_bits):
+    """The four values of ``enable_image_stats`` as the C ABI takes them (unsigned), capacity first."""
+    capacity = int(capacity)
+    if not 0 <= capacity < 1 << 64:
+        raise MpcError(-22, f"{fn}: capacity is unsigned")
+    return (capacity,) + _pack_values(fn, block_lines, sector_bytes, header_bits)
+
+
+def image_check_values(line_size: int, block_lines: int, sector_bytes: int = 32, header_bits: int = 0, capacity: int = 1 << 24) -> None:
+    """Raises ``MpcError`` with the message ``enable_image_stats`` would give for these values
+    (``mpc_image_check_values``; no device)."""
+    rc = lib().mpc_image_check_values(int(line_size), *_image_values("mpc_image_check_values", capacity, block_lines, sector_bytes, header_bits))
+    if rc != 0:
+        raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
+
+
+def image_hash(key: int) -> int:
+    """``mpc_image_hash``: a key's first slot is ``image_hash(key) & (slots - 1)``, ``slots`` the smallest power of two
+    >= 2 x capacity and at least 2 (no device)."""
+    return int(lib().mpc_image_hash(int(key) & ((1 << 64) - 1)))
+
+
+def image_table_view(table: np.ndarray, line_size: int) -> Dict:
+    """An image table ``uint64[MPC_IMAGE_TABLE_LEN]`` as a dict of its named entries, ``block_sectors`` (S_B),
+    ``histogram[S_B]`` (entry k - 1: touched blocks that occupy k sectors) and the three ratios ``traffic_ratio`` =
+    lines x 8 L / bits, ``image_ratio`` = distinct_lines x 8 L / image_bits and ``image_sector_ratio`` = caps / sectors
+    (each 0.0 where its divisor is 0)."""
+    t = np.asarray(table, dtype=np.uint64).reshape(MPC_IMAGE_TABLE_LEN)
+    v = [int(x) for x in t[:12]]
+    L = int(line_size)
+    S = -(-v[8] * L // v[9])
+    return {"lines": v[0], "bits": v[1], "distinct_lines": v[2], "image_bits": v[3], "blocks": v[4], "sectors": v[5], "caps": v[6],
+            "misaligned": v[7], "block_lines": v[8], "sector_bytes": v[9], "header_bits": v[10], "capacity": v[11], "block_sectors": S,
+            "histogram": t[16:16 + S].copy(),
+            "traffic_ratio": v[0] * 8 * L / v[1] if v[1] else 0.0,
+            "image_ratio": v[2] * 8 * L / v[3] if v[3] else 0.0,
+            "image_sector_ratio": v[6] / v[5] if v[5] else 0.0}
+
+
 def _ratio(original, compressed, lines) -> float:
     """VPC (``VPC.h:49-60``): inf once lines of 0 bits are all there are, 0 before the first line."""
     if not lines:
@@ -369,14 +435,24 @@ class _Evaluator:
 
     # -- hot path -----------------------------------------------------------
     def compress_lines(self, lines: np.ndarray, want_sizes: bool = True,
-                       want_selected: bool = True, *, classes=None) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+                       want_selected: bool = True, *, classes=None, addresses=None) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
         """Host buffer [n, L] uint8 -> (size_bits uint16[n], selected int8[n]); staged
         through the pinned double buffers.  Statistics accumulate in the handle.
-        ``classes``: one class (0..255) per line for ``class_stats()``; needs ``enable_class_stats()``."""
+        ``classes``: one class (0..255) per line for ``class_stats()``; needs ``enable_class_stats()``.
+        ``addresses``: one uint64 line address per line for ``image_stats()``; needs ``enable_image_stats()`` (and is
+        needed once that is on); not together with ``classes``: addressed lines count in class 0."""
         lines = _as_lines(lines, self.line_size)
         n = lines.shape[0]
         sizes = np.empty(n, dtype=np.uint16) if want_sizes else None
         sel = np.empty(n, dtype=np.int8) if want_selected else None
+        if addresses is not None:
+            if classes is not None:
+                raise ValueError("compress_lines: classes= and addresses= cannot be given together")
+            adr = _as_addresses(addresses, n)
+            self._check(lib().mpc_compress_batch_addressed(self._h, lines.ctypes.data, n, adr.ctypes.data,
+                                                           sizes.ctypes.data if want_sizes else None,
+                                                           sel.ctypes.data if want_selected else None))
+            return sizes, sel
         if classes is not None:
             cls = _as_classes(classes, n)
             self._check(lib().mpc_compress_batch_classed(self._h, lines.ctypes.data, n, cls.ctypes.data,
@@ -389,9 +465,16 @@ class _Evaluator:
         return sizes, sel
 
     def compress_device(self, d_lines: int, n_lines: int, d_sizes: int = 0, d_selected: int = 0,
-                        stream: int = 0, *, classes: int = 0) -> None:
+                        stream: int = 0, *, classes: int = 0, addresses: int = 0) -> None:
         """Device-resident lines (raw pointers, e.g. ``tensor.data_ptr()``); asynchronous.
-        ``classes``: raw device pointer to ``n_lines`` uint8 classes; needs ``enable_class_stats()``."""
+        ``classes``: raw device pointer to ``n_lines`` uint8 classes; needs ``enable_class_stats()``.
+        ``addresses``: raw device pointer to ``n_lines`` uint64 line addresses; needs ``enable_image_stats()``."""
+        if addresses:
+            if classes:
+                raise ValueError("compress_device: classes= and addresses= cannot be given together")
+            self._check(lib().mpc_compress_batch_device_addressed(self._h, d_lines, n_lines, addresses, d_sizes or None,
+                                                                  d_selected or None, stream or None))
+            return
         if classes:
             self._check(lib().mpc_compress_batch_device_classed(self._h, d_lines, n_lines, classes, d_sizes or None,
                                                                 d_selected or None, stream or None))
@@ -522,6 +605,25 @@ class _Evaluator:
         open block."""
         table = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1)
         self._check(lib().mpc_pack_stats_merge(self._h, table.ctypes.data, table.size))
+
+
+    # -- image accounting -------------------------------------------------------
+    def enable_image_stats(self, block_lines: int, sector_bytes: int = 32, header_bits: int = 0, capacity: int = 1 << 24) -> None:
+        """Keep, from now on, the size of the latest line per line address (``addresses=``, or a ``.log``'s
+        ``mem_addr``), for up to ``capacity`` distinct lines (32 bytes of device memory each), and report what
+        address-aligned blocks of ``block_lines`` lines of that image occupy in sectors of ``sector_bytes`` bytes,
+        ``header_bits`` added per block (``mpc_image_stats_enable``); idempotent for the same values."""
+        self._check(lib().mpc_image_stats_enable(self._h, *_image_values("mpc_image_stats_enable", capacity, block_lines, sector_bytes, header_bits)))
+
+    def image_table(self) -> np.ndarray:
+        """The raw table ``uint64[MPC_IMAGE_TABLE_LEN]`` (``mpc_image_stats_get``); not destructive."""
+        t = np.zeros(MPC_IMAGE_TABLE_LEN, dtype=np.uint64)
+        self._check(lib().mpc_image_stats_get(self._h, t.ctypes.data, t.size))
+        return t
+
+    def image_stats(self) -> Dict:
+        """``image_table_view`` of the image since accounting was switched on or the last ``reset()``."""
+        return image_table_view(self.image_table(), self.line_size)
 
 
 class VPC(_Evaluator):
@@ -817,28 +919,40 @@ class EvaluatorSet:
     def _pointers(self, values):
         return (C.c_void_p * len(self.members))(*values)
 
-    def compress_lines(self, lines: np.ndarray, want_sizes: bool = True, want_selected: bool = True, *, classes=None):
+    def compress_lines(self, lines: np.ndarray, want_sizes: bool = True, want_selected: bool = True, *, classes=None, addresses=None):
         """Host buffer [n, L] uint8 -> one ``(size_bits, selected)`` pair per member, in member order.
-        ``classes``: one class (0..255) per line for ``class_stats()``; needs ``enable_class_stats()``."""
+        ``classes``: one class (0..255) per line for ``class_stats()``; needs ``enable_class_stats()``.
+        ``addresses``: one uint64 line address per line for ``image_stats()``; needs ``enable_image_stats()``."""
         lines = _as_lines(lines, self.line_size)
         n = lines.shape[0]
         sizes = [np.empty(n, dtype=np.uint16) if want_sizes else None for _ in self.members]
         sel = [np.empty(n, dtype=np.int8) if want_selected else None for _ in self.members]
         p_sizes = self._pointers([a.ctypes.data for a in sizes]) if want_sizes else None
         p_sel = self._pointers([a.ctypes.data for a in sel]) if want_selected else None
-        if classes is not None:
+        if addresses is not None:
+            if classes is not None:
+                raise ValueError("compress_lines: classes= and addresses= cannot be given together")
+            adr = _as_addresses(addresses, n)
+            self._check(lib().mpc_group_compress_batch_addressed(self._g, lines.ctypes.data, n, adr.ctypes.data, p_sizes, p_sel))
+        elif classes is not None:
             cls = _as_classes(classes, n)
             self._check(lib().mpc_group_compress_batch_classed(self._g, lines.ctypes.data, n, cls.ctypes.data, p_sizes, p_sel))
         else:
             self._check(lib().mpc_group_compress_batch(self._g, lines.ctypes.data, n, p_sizes, p_sel))
         return list(zip(sizes, sel))
 
-    def compress_device(self, d_lines: int, n_lines: int, d_sizes=None, d_selected=None, stream: int = 0, *, classes: int = 0) -> None:
+    def compress_device(self, d_lines: int, n_lines: int, d_sizes=None, d_selected=None, stream: int = 0, *, classes: int = 0,
+                        addresses: int = 0) -> None:
         """Device-resident lines; ``d_sizes`` / ``d_selected``: one raw device pointer (or 0 / None) per member.
-        ``classes``: raw device pointer to ``n_lines`` uint8 classes; needs ``enable_class_stats()``."""
+        ``classes``: raw device pointer to ``n_lines`` uint8 classes; needs ``enable_class_stats()``.
+        ``addresses``: raw device pointer to ``n_lines`` uint64 line addresses; needs ``enable_image_stats()``."""
         p_sizes = self._pointers([p or None for p in d_sizes]) if d_sizes is not None else None
         p_sel = self._pointers([p or None for p in d_selected]) if d_selected is not None else None
-        if classes:
+        if addresses:
+            if classes:
+                raise ValueError("compress_device: classes= and addresses= cannot be given together")
+            self._check(lib().mpc_group_compress_batch_device_addressed(self._g, d_lines, n_lines, addresses, p_sizes, p_sel, stream or None))
+        elif classes:
             self._check(lib().mpc_group_compress_batch_device_classed(self._g, d_lines, n_lines, classes, p_sizes, p_sel, stream or None))
         else:
             self._check(lib().mpc_group_compress_batch_device(self._g, d_lines, n_lines, p_sizes, p_sel, stream or None))
@@ -927,6 +1041,22 @@ class EvaluatorSet:
         if lib().mpc_group_pack_stats_get(self._g, MPC_PACK_BEST, t.ctypes.data, t.size) == 0:
             out["best"] = pack_table_view(t, self.line_size, close_tail)
         return out
+
+    # -- image accounting ----------------------------------------------------------
+    def enable_image_stats(self, block_lines: int, sector_bytes: int = 32, header_bits: int = 0, capacity: int = 1 << 24) -> None:
+        """``enable_image_stats`` for every member with the same values; a member's image is its own."""
+        self._check(lib().mpc_group_image_stats_enable(self._g, *_image_values("mpc_group_image_stats_enable", capacity, block_lines, sector_bytes,
+                                                                                header_bits)))
+
+    def image_table(self, member: int) -> np.ndarray:
+        """The raw table of member ``member``."""
+        t = np.zeros(MPC_IMAGE_TABLE_LEN, dtype=np.uint64)
+        self._check(lib().mpc_group_image_stats_get(self._g, int(member), t.ctypes.data, t.size))
+        return t
+
+    def image_stats(self) -> Dict:
+        """``{0: ..., 1: ...}``: one entry per member, in member order, each as ``_Evaluator.image_stats()`` returns it."""
+        return {i: image_table_view(self.image_table(i), self.line_size) for i in range(len(self.members))}
 
     def class_log_field(self, field) -> None:
         """``_Evaluator.class_log_field`` for ``compress_gpgpusim_log`` of the set."""

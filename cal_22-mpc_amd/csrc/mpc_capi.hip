@@ -21,6 +21,7 @@
 #include "mpc_sizes.h"
 #include "mpc_classes.h"
 #include "mpc_pack.h"
+#include "mpc_image.h"
 #include "mpc_fit.h"
 #include "mpc_launch.h"
 
@@ -34,7 +35,7 @@ constexpr size_t kTestWords = kRouteWords + (MPC_STAMPS ? MPC_STAMP_WORDS : 0); 
 
 typedef unsigned long long u64;
 
-// Size, class or pack accounting on mpc_compress_batch_device without a sizes array of the caller's: the batch is evaluated in
+// Size, class, pack or image accounting on mpc_compress_batch_device without a sizes array of the caller's: the batch is evaluated in
 // pieces of this many lines, each evaluator launch followed by the accounting passes over ONE scratch array (8 MiB per member).
 constexpr u64 kAccountLines = 4ull << 20;
 
@@ -173,6 +174,20 @@ struct mpc_handle {
     bool recorded = false;
     std::vector<u64> extra;            // merged-in tables, device layout
   } pack;
+  // image accounting (mpc_image.h): nothing of it exists before mpc_image_stats_enable.  Its update passes are atomic
+  // and stamped with the line's position, so launches on different streams need no order between them.
+  struct {
+    bool on = false;
+    u64 capacity = 0, N = 0;
+    unsigned sector_bytes = 0, header_bits = 0;
+    u64 seen = 0;                      // lines evaluated since accounting was switched on or last reset: the next line's position
+    u64 slots = 0;                     // the smallest power of two >= 2 x capacity
+    u64 hash_mask = ~0ull;             // (the test library: MPC_TEST_IMAGE_HASH_BITS)
+    u64 *d_keys = nullptr, *d_vals = nullptr;   // [slots]
+    u64 *d_ctl = nullptr;              // [MPC_IMAGE_CTL_LEN], then [MPC_IMAGE_OUT_LEN]: the table of a get's pass
+    u64 ctl[MPC_IMAGE_CTL_LEN] = {};   // what image_status last read of it
+    bool over = false;                 // a key beyond the capacity arrived: the handle takes no more lines
+  } img;
   std::string error;
 };
 
@@ -211,6 +226,12 @@ struct mpc_group {
     hipEvent_t done = nullptr;
     bool recorded = false;
   } pack;
+  // image accounting of the group (mpc_image.h): the members' images are their handles'
+  struct {
+    bool on = false;
+    u64 capacity = 0, N = 0;
+    unsigned sector_bytes = 0, header_bits = 0;
+  } img;
   hipEvent_t scratch_done = nullptr;
   bool recorded = false;
   std::string form, error;
@@ -236,15 +257,16 @@ int launch(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t 
 int pattern_status(mpc_handle *h);
 int group_launch(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, hipStream_t s);
 int group_members_status(mpc_group *g);
-int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, const uint8_t *d_classes, hipStream_t s);
+int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, const uint8_t *d_classes, const uint64_t *d_addrs,
+                     hipStream_t s);
 int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes,
-                           hipStream_t s);
+                           const uint64_t *d_addrs, hipStream_t s);
 
 Sink sink_of(mpc_handle *h)
 {
   return {h,
-          [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, const uint8_t *dc, hipStream_t s) {
-            return launch_accounted(static_cast<mpc_handle *>(c), d, n, ds ? ds[0] : nullptr, dl ? dl[0] : nullptr, dc, s);
+          [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, const uint8_t *dc, const uint64_t *da, hipStream_t s) {
+            return launch_accounted(static_cast<mpc_handle *>(c), d, n, ds ? ds[0] : nullptr, dl ? dl[0] : nullptr, dc, da, s);
           },
           [](void *c, int code, const std::string &msg) { return set_err(static_cast<mpc_handle *>(c), code, msg); },
           [](void *c) { return pattern_status(static_cast<mpc_handle *>(c)); }};
@@ -253,8 +275,8 @@ Sink sink_of(mpc_handle *h)
 Sink sink_of(mpc_group *g)
 {
   return {g,
-          [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, const uint8_t *dc, hipStream_t s) {
-            return group_launch_accounted(static_cast<mpc_group *>(c), d, n, ds, dl, dc, s);
+          [](void *c, const void *d, u64 n, uint16_t *const *ds, int8_t *const *dl, const uint8_t *dc, const uint64_t *da, hipStream_t s) {
+            return group_launch_accounted(static_cast<mpc_group *>(c), d, n, ds, dl, dc, da, s);
           },
           [](void *c, int code, const std::string &msg) { return group_err(static_cast<mpc_group *>(c), code, msg); },
           [](void *c) { return group_members_status(static_cast<mpc_group *>(c)); }};
@@ -608,9 +630,25 @@ int launch_pattern(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes,
   return MPC_OK;
 }
 
-// Pattern, at a point where the handle's work is complete: has a line beyond the capacity arrived?
+// image accounting, at a point where the handle's work is complete: has a key beyond the capacity arrived?
+int image_status(mpc_handle *h)
+{
+  if (!h->img.on) return MPC_OK;
+  if (!h->img.over) {
+    u64 *ctl = h->img.ctl;            // more claims than the capacity (the device's flag says the same, earlier)
+    HIPCHK(h, hipMemcpy(ctl, h->img.d_ctl, sizeof(h->img.ctl), hipMemcpyDeviceToHost));
+    h->img.over = ctl[MPC_IMAGE_CTL_KEYS] > h->img.capacity || ctl[MPC_IMAGE_CTL_OVERFLOW] != 0;
+  }
+  return h->img.over ? set_err(h, MPC_E_INVAL, "image accounting: more than " + std::to_string(h->img.capacity) +
+                                                   " distinct line addresses (capacity_lines of mpc_image_stats_enable): the image is incomplete, the handle takes no more lines")
+                     : MPC_OK;
+}
+
+// Pattern, at a point where the handle's work is complete: has a line beyond the capacity arrived?  (Image accounting's
+// capacity is checked at the same points, for every kind of handle.)
 int pattern_status(mpc_handle *h)
 {
+  if (const int rc = image_status(h)) return rc;
   if (h->algorithm != Algo::Pattern) return MPC_OK;
   if (h->pat.evicting) {       // nothing to run into: the flag says that a probe went round a whole table, which its sizing excludes
     u64 flag = 0;
@@ -842,7 +880,7 @@ bool accounts(const mpc_handle *h) { return h->acct.on && h->algorithm != Algo::
 bool in_best(const mpc_group *g, int i) { return g->best.on && std::find(g->best.set.begin(), g->best.set.end(), i) != g->best.set.end(); }
 
 // a handle whose sizes are wanted on the device, asked for by the caller or not
-bool needs_sizes(const mpc_handle *h) { return accounts(h) || h->cls.on || h->pack.on; }
+bool needs_sizes(const mpc_handle *h) { return accounts(h) || h->cls.on || h->pack.on || h->img.on; }
 
 // ... a member whose sizes a group needs on the device, asked for by the caller or not
 bool group_accounts(const mpc_group *g, int i) { return needs_sizes(g->m[(size_t)i]) || in_best(g, i); }
@@ -855,6 +893,7 @@ void group_refresh(mpc_group *g)
     g->stage.need_sel[(size_t)i] = g->cls.from_member == i ? 1 : 0;
   }
   g->stage.log_field = (g->cls.on && g->cls.from_member < 0) ? g->cls.log_field : MPC_CLASS_LOG_NONE;
+  g->stage.log_addrs = g->img.on;
 }
 
 hipError_t sizes_pass(const mpc_handle *h, const MpcSizesArgs &A, u64 n, hipStream_t s)
@@ -915,6 +954,25 @@ std::string pack_values(u64 N, unsigned sb, unsigned hb)
   return "block_lines " + std::to_string(N) + ", sector_bytes " + std::to_string(sb) + ", header_bits " + std::to_string(hb);
 }
 
+// ---- image accounting (mpc_image.h): its values ----
+// the refusals of mpc_image_stats_enable that need no device
+std::string image_refusal_of(unsigned L, u64 capacity, u64 block_lines, unsigned sector_bytes, unsigned header_bits)
+{
+  if (capacity == 0) return "image accounting: capacity_lines must be at least 1";
+  if (capacity > MPC_IMAGE_MAX_CAPACITY) return "image accounting: capacity_lines above " + std::to_string(MPC_IMAGE_MAX_CAPACITY) + " (2^28; the table takes 32 bytes per line of capacity)";
+  std::string why = pack_refusal(L, block_lines, sector_bytes, header_bits);
+  if (!why.empty()) why.replace(0, 4, "image");        // "pack accounting: ..." -> "image accounting: ..."
+  return why;
+}
+
+std::string image_values(u64 cap, u64 N, unsigned sb, unsigned hb) { return "capacity_lines " + std::to_string(cap) + ", " + pack_values(N, sb, hb); }
+
+u64 image_slots(u64 capacity)
+{
+  u64 slots = 2;
+  while (slots < 2 * capacity) slots <<= 1;
+  return slots;
+}
 // device table (mpc_pack.h) -> the ABI's table; open_lines / open_bits: the open block
 void pack_table_out(const std::vector<u64> &dev, u64 N, unsigned L, unsigned sb, unsigned hb, u64 open_lines, u64 open_bits, uint64_t *table)
 {
@@ -989,9 +1047,49 @@ int pack_pass(const Sink &k, const mpc_handle *grid_of, mpc_handle *const *hs, c
   return MPC_OK;
 }
 
-// a staged or in-place chunk of a handle: the stager has asked for the sizes of a handle that accounts
-int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, const uint8_t *d_classes, hipStream_t s)
+// ---- image accounting (mpc_image.h) ----
+// before a chunk is evaluated: a handle with the accounting on takes only lines that bring an address, and none once
+// its capacity was exceeded; a handle without it takes no addresses
+int image_refusal(mpc_handle *h, u64 n, const uint64_t *d_addrs)
 {
+  if (!h->img.on)
+    return d_addrs ? set_err(h, MPC_E_INVAL, "image accounting is not switched on for this handle (mpc_image_stats_enable): the call must not bring addresses") : MPC_OK;
+  if (h->img.over) return image_status(h);
+  if (n && !d_addrs)
+    return set_err(h, MPC_E_INVAL, "image accounting is on: every line needs an address (mpc_compress_batch_addressed, mpc_compress_batch_device_addressed or a "
+                                   "GPGPU-Sim .log); this call brings none, and a hole in the image is not counted silently");
+  return MPC_OK;
+}
+
+// the update pass behind the evaluator's launch of a chunk
+int image_pass(const Sink &k, mpc_handle *h, const uint16_t *d_sizes, const uint64_t *d_addrs, u64 n, hipStream_t s)
+{
+  auto &I = h->img;
+  MpcImageArgs A{};
+  A.addrs = d_addrs;
+  A.sizes = d_sizes;
+  A.keys = I.d_keys;
+  A.vals = I.d_vals;
+  A.ctl = I.d_ctl;
+  A.slot_mask = I.slots - 1;
+  A.hash_mask = I.hash_mask;
+  A.pos = I.seen;
+  A.capacity = I.capacity;
+  A.line_size = (unsigned)h->L;
+  A.line_shift = -1;
+  for (int b = 0; b < 31; b++)
+    if ((unsigned)h->L == (1u << b)) A.line_shift = b;
+  const hipError_t e = mpc_launch_image_update(&A, n, grid_for(h, n, 256, 8), s);
+  if (e != hipSuccess) return k.fail(k.ctx, MPC_E_HIP, std::string("kernel launch (image accounting): ") + hipGetErrorString(e));
+  I.seen += n;
+  return MPC_OK;
+}
+
+// a staged or in-place chunk of a handle: the stager has asked for the sizes of a handle that accounts
+int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_sizes, int8_t *d_sel, const uint8_t *d_classes, const uint64_t *d_addrs,
+                     hipStream_t s)
+{
+  if (const int irc = image_refusal(h, n, d_addrs)) return irc;
   int rc = launch(h, d_lines, n, d_sizes, d_sel, s);
   if (rc != MPC_OK || n == 0 || !needs_sizes(h)) return rc;
   if (!d_sizes) return set_err(h, MPC_E_INVAL, "size accounting: the chunk has no sizes array");
@@ -1006,10 +1104,13 @@ int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_size
     const hipError_t e = classes_pass(h, A, n, s);
     if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("kernel launch (class accounting): ") + hipGetErrorString(e));
   }
-  if (rc != MPC_OK || !h->pack.on) return rc;
-  mpc_handle *one[1] = {h};
-  const uint16_t *arr[1] = {d_sizes};
-  return pack_pass(sink_of(h), h, one, arr, 1, nullptr, n, s);
+  if (rc == MPC_OK && h->pack.on) {
+    mpc_handle *one[1] = {h};
+    const uint16_t *arr[1] = {d_sizes};
+    rc = pack_pass(sink_of(h), h, one, arr, 1, nullptr, n, s);
+  }
+  if (rc != MPC_OK || !h->img.on) return rc;
+  return image_pass(sink_of(h), h, d_sizes, d_addrs, n, s);
 }
 
 // The members' sizes of one chunk (one pointer per member, non-null for every member that group_accounts): first the
@@ -1164,9 +1265,34 @@ int group_pack_check(mpc_group *g)
   return MPC_OK;
 }
 
-int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes,
-                           hipStream_t s)
+// Before a group call feeds its members: with the group's image accounting on they stand at one common line.
+int group_image_check(mpc_group *g)
 {
+  if (!g->img.on) return MPC_OK;
+  const u64 at = g->m[0]->img.seen;
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const auto &I = g->m[i]->img;
+    if (!I.on || I.capacity != g->img.capacity || I.N != g->img.N || I.sector_bytes != g->img.sector_bytes || I.header_bits != g->img.header_bits)
+      return group_err(g, MPC_E_INVAL, "image accounting: member " + std::to_string(i) + " does not count with the group's values");
+    if (I.seen != at)
+      return group_err(g, MPC_E_INVAL, "image accounting: member " + std::to_string(i) + " (" + algorithm_name(g->m[i]->algorithm) + ") is at line " +
+                                           std::to_string(I.seen) + ", member 0 at line " + std::to_string(at) +
+                                           ": a member was fed outside the group, its positions no longer line up with the others' (reset the members to start over)");
+  }
+  return MPC_OK;
+}
+
+int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes,
+                           const uint64_t *d_addrs, hipStream_t s)
+{
+  bool images = false;
+  for (size_t i = 0; i < g->m.size(); i++) {
+    mpc_handle *h = g->m[i];
+    if (!h->img.on) continue;         // (a member without the accounting ignores the group's addresses)
+    images = true;
+    if (const int irc = image_refusal(h, n, d_addrs)) return group_err(g, irc, "member " + std::to_string(i) + " (" + algorithm_name(h->algorithm) + "): " + h->error);
+  }
+  if (d_addrs && !images) return group_err(g, MPC_E_INVAL, "image accounting is not switched on for any member of this group: the call must not bring addresses");
   int rc = group_launch(g, d_lines, n, d_sizes, d_sel, s);
   if (rc != MPC_OK || n == 0) return rc;
   bool any = false, sizes = false;
@@ -1179,7 +1305,10 @@ int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *c
   if (!any) return MPC_OK;
   if (sizes) rc = group_account(g, d_sizes, n, s);
   if (rc == MPC_OK) rc = group_class_account(g, d_sizes, d_sel, d_classes, n, s);
-  return rc == MPC_OK ? group_pack_account(g, d_sizes, n, s) : rc;
+  if (rc == MPC_OK) rc = group_pack_account(g, d_sizes, n, s);
+  for (size_t i = 0; rc == MPC_OK && images && i < g->m.size(); i++)
+    if (g->m[i]->img.on) rc = image_pass(sink_of(g), g->m[i], d_sizes[i], d_addrs, n, s);
+  return rc;
 }
 
 // VPC: the size histogram is the sum over the clusters of the histogram in the raw statistics, clipped into MPC_SIZE_BINS bins
@@ -1594,6 +1723,8 @@ void mpc_destroy(mpc_handle *h)
   if (h->pack.d_tab) (void)hipFree(h->pack.d_tab);
   if (h->pack.d_carry) (void)hipFree(h->pack.d_carry);
   if (h->pack.done) (void)hipEventDestroy(h->pack.done);
+  if (h->img.d_keys) (void)hipFree(h->img.d_keys);
+  if (h->img.d_ctl) (void)hipFree(h->img.d_ctl);
   delete h;
 }
 
@@ -1662,8 +1793,8 @@ const char *mpc_path_reason(const mpc_handle *h)
   return (h && h->algorithm == Algo::VPC) ? h->route.why_generic.c_str() : "";
 }
 
-// mpc_compress_batch_device and its classed twin (d_classes: null for class 0)
-static int batch_device(mpc_handle *h, const void *d_lines, uint64_t n, const uint8_t *d_classes, uint16_t *d_sizes, int8_t *d_sel,
+// mpc_compress_batch_device, its classed twin (d_classes: null for class 0) and its addressed twin (d_addrs: null for none)
+static int batch_device(mpc_handle *h, const void *d_lines, uint64_t n, const uint8_t *d_classes, const uint64_t *d_addrs, uint16_t *d_sizes, int8_t *d_sel,
                         void *hip_stream)
 {
   if (!h || (!d_lines && n)) return MPC_E_INVAL;
@@ -1671,7 +1802,8 @@ static int batch_device(mpc_handle *h, const void *d_lines, uint64_t n, const ui
   if (h->algorithm == Algo::Fit && (d_sizes || d_sel)) return set_err(h, MPC_E_INVAL, kFitNoPerLine);
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  if (!needs_sizes(h) || d_sizes) return launch_accounted(h, d_lines, n, d_sizes, d_sel, d_classes, s);
+  if (!needs_sizes(h) || d_sizes) return launch_accounted(h, d_lines, n, d_sizes, d_sel, d_classes, d_addrs, s);
+  if (const int irc = image_refusal(h, n, d_addrs)) return irc;      // (before the scratch array is made)
   // accounting without a sizes array of the caller's: pieces of kAccountLines lines over the handle's scratch array
   if (!h->acct.d_scratch) {
     HIPCHK(h, hipMalloc((void **)&h->acct.d_scratch, kAccountLines * sizeof(uint16_t)));
@@ -1681,7 +1813,7 @@ static int batch_device(mpc_handle *h, const void *d_lines, uint64_t n, const ui
   for (u64 at = 0; at < n; at += kAccountLines) {
     const u64 take = std::min<u64>(n - at, kAccountLines);
     const int rc = launch_accounted(h, static_cast<const uint8_t *>(d_lines) + at * (u64)h->L, take, h->acct.d_scratch, d_sel ? d_sel + at : nullptr,
-                                    d_classes ? d_classes + at : nullptr, s);
+                                    d_classes ? d_classes + at : nullptr, d_addrs ? d_addrs + at : nullptr, s);
     if (rc != MPC_OK) return rc;
   }
   HIPCHK(h, hipEventRecord(h->acct.scratch_done, s));
@@ -1692,7 +1824,7 @@ static int batch_device(mpc_handle *h, const void *d_lines, uint64_t n, const ui
 int mpc_compress_batch_device(mpc_handle *h, const void *d_lines, uint64_t n, uint16_t *d_sizes, int8_t *d_sel,
                               void *hip_stream)
 {
-  return batch_device(h, d_lines, n, nullptr, d_sizes, d_sel, hip_stream);
+  return batch_device(h, d_lines, n, nullptr, nullptr, d_sizes, d_sel, hip_stream);
 }
 
 int mpc_sync(mpc_handle *h)
@@ -1710,7 +1842,7 @@ int mpc_compress_batch(mpc_handle *h, const uint8_t *lines, uint64_t n, uint16_t
   if (!h || (!lines && n)) return MPC_E_INVAL;
   if (h->algorithm == Algo::Fit && (sizes || sel)) return set_err(h, MPC_E_INVAL, kFitNoPerLine);
   if (n == 0) return MPC_OK;
-  return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, nullptr, &sizes, &sel);   // (a group of one)
+  return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, nullptr, nullptr, &sizes, &sel);   // (a group of one)
 }
 
 int mpc_npy_shape(const char *path, uint64_t *rows, uint64_t *cols)
@@ -1821,11 +1953,13 @@ int mpc_group_compress_batch(mpc_group *g, const uint8_t *lines, uint64_t n, uin
   if (n == 0) return MPC_OK;
   group_refresh(g);
   if (const int prc = group_pack_check(g)) return prc;
-  return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, nullptr, sizes, sel);
+  if (const int irc = group_image_check(g)) return irc;
+  return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, nullptr, nullptr, sizes, sel);
 }
 
-// mpc_group_compress_batch_device and its classed twin (d_classes: null for class 0, or the classes come from a member)
-static int group_batch_device(mpc_group *g, const void *d_lines, uint64_t n, const uint8_t *d_classes, uint16_t *const *d_sizes,
+// mpc_group_compress_batch_device, its classed twin (d_classes: null for class 0, or the classes come from a member) and its
+// addressed twin (d_addrs: null for none)
+static int group_batch_device(mpc_group *g, const void *d_lines, uint64_t n, const uint8_t *d_classes, const uint64_t *d_addrs, uint16_t *const *d_sizes,
                               int8_t *const *d_sel, void *hip_stream)
 {
   if (!g || (!d_lines && n)) return MPC_E_INVAL;
@@ -1833,6 +1967,7 @@ static int group_batch_device(mpc_group *g, const void *d_lines, uint64_t n, con
   HIPCHK(g, hipSetDevice(g->stage.device));
   hipStream_t s = (hipStream_t)hip_stream;
   if (const int prc = group_pack_check(g)) return prc;
+  if (const int irc = group_image_check(g)) return irc;
   const size_t nm = g->m.size();
   bool any = false, scratch = false;
   for (size_t i = 0; i < nm; i++) {
@@ -1842,8 +1977,8 @@ static int group_batch_device(mpc_group *g, const void *d_lines, uint64_t n, con
   }
   const int fm = g->cls.from_member;       // its selected values are needed on the device, asked for or not
   const bool sel_scratch = fm >= 0 && !(d_sel && d_sel[fm]);
-  if (!any) return group_launch(g, d_lines, n, d_sizes, d_sel, s);
-  if (!scratch && !sel_scratch) return group_launch_accounted(g, d_lines, n, d_sizes, d_sel, d_classes, s);
+  if (!any && !d_addrs) return group_launch(g, d_lines, n, d_sizes, d_sel, s);
+  if (!scratch && !sel_scratch) return group_launch_accounted(g, d_lines, n, d_sizes, d_sel, d_classes, d_addrs, s);
   // accounting of a member without a sizes array of the caller's: pieces of kAccountLines lines, that member's sizes in a scratch array
   g->d_scratch.resize(nm, nullptr);
   g->piece_sizes.assign(nm, nullptr);
@@ -1861,7 +1996,7 @@ static int group_batch_device(mpc_group *g, const void *d_lines, uint64_t n, con
       g->piece_sel[i] = (d_sel && d_sel[i]) ? d_sel[i] + at : (sel_scratch && (int)i == fm) ? g->cls.d_scratch_sel : nullptr;
     }
     const int rc = group_launch_accounted(g, static_cast<const uint8_t *>(d_lines) + at * (u64)g->stage.L, take, g->piece_sizes.data(), g->piece_sel.data(),
-                                          d_classes ? d_classes + at : nullptr, s);
+                                          d_classes ? d_classes + at : nullptr, d_addrs ? d_addrs + at : nullptr, s);
     if (rc != MPC_OK) return rc;
   }
   HIPCHK(g, hipEventRecord(g->scratch_done, s));
@@ -1872,7 +2007,7 @@ static int group_batch_device(mpc_group *g, const void *d_lines, uint64_t n, con
 int mpc_group_compress_batch_device(mpc_group *g, const void *d_lines, uint64_t n, uint16_t *const *d_sizes, int8_t *const *d_sel,
                                     void *hip_stream)
 {
-  return group_batch_device(g, d_lines, n, nullptr, d_sizes, d_sel, hip_stream);
+  return group_batch_device(g, d_lines, n, nullptr, nullptr, d_sizes, d_sel, hip_stream);
 }
 
 int mpc_group_compress_npy(mpc_group *g, const char *path, uint64_t first_row, uint64_t n_rows, int skip_last_row, uint64_t *rows_done)
@@ -1880,6 +2015,7 @@ int mpc_group_compress_npy(mpc_group *g, const char *path, uint64_t first_row, u
   if (!g || !path) return MPC_E_INVAL;
   group_refresh(g);
   if (const int prc = group_pack_check(g)) return prc;
+  if (const int irc = group_image_check(g)) return irc;
   return mpcstage::compress_npy(g->stage, sink_of(g), nullptr, path, first_row, n_rows, skip_last_row, rows_done);
 }
 
@@ -1888,6 +2024,7 @@ int mpc_group_compress_gpgpusim_log(mpc_group *g, const char *log_path, uint64_t
   if (!g || !log_path) return MPC_E_INVAL;
   group_refresh(g);
   if (const int prc = group_pack_check(g)) return prc;
+  if (const int irc = group_image_check(g)) return irc;
   return mpcstage::compress_gpgpusim_log(g->stage, sink_of(g), nullptr, log_path, requests_read, lines_done);
 }
 
@@ -1972,6 +2109,12 @@ int mpc_stats_reset(mpc_handle *h)
   if (h->pack.d_tab) HIPCHK(h, hipMemset(h->pack.d_tab, 0, MPC_PACK_DEV_LEN * sizeof(u64)));
   h->pack.extra.assign(h->pack.extra.size(), 0);
   h->pack.seen = 0;                   // (the open block goes with the position: its carry is read only behind a launch that wrote it)
+  if (h->img.on) {                    // the image, the position and the table (a handle that ran into its capacity never gets here, as a Pattern one)
+    HIPCHK(h, hipMemset(h->img.d_keys, 0xff, h->img.slots * sizeof(u64)));
+    HIPCHK(h, hipMemset(h->img.d_vals, 0, h->img.slots * sizeof(u64)));
+    HIPCHK(h, hipMemset(h->img.d_ctl, 0, MPC_IMAGE_CTL_LEN * sizeof(u64)));
+    h->img.seen = 0;
+  }
   h->extra.assign(h->stats_len, 0);
   h->sc2.lines = h->sc2.warm = 0;     // SC2: the table and the line counter stay (C-Pack in blocks: the open block and the position in it)
   return MPC_OK;
@@ -2314,6 +2457,235 @@ int mpc_group_pack_stats_get(mpc_group *g, int member, uint64_t *table, size_t n
   return rc == MPC_OK ? rc : group_err(g, rc, "member " + std::to_string(member) + " (" + algorithm_name(h->algorithm) + "): " + h->error);
 }
 
+// ---- image accounting (include/mpc_hip_image.h) ----------------------------------
+namespace {
+const char *const kImageOff = "image accounting is not switched on for this handle (mpc_image_stats_enable)";
+const char *const kGroupImageOff = "image accounting is not switched on for this group (mpc_group_image_stats_enable)";
+const char *const kImageTableLen = "an image table has MPC_IMAGE_TABLE_LEN (16 + 1024 = 1040) entries";
+
+}  // namespace
+
+uint64_t mpc_image_hash(uint64_t key) { return mpc_image_mix(key); }
+
+int mpc_image_check_values(unsigned line_size, uint64_t capacity_lines, uint64_t block_lines, unsigned sector_bytes, unsigned header_bits)
+{
+  const std::string why = line_size == 0 ? std::string("image accounting: line_size must be at least 1")
+                                         : image_refusal_of(line_size, capacity_lines, block_lines, sector_bytes, header_bits);
+  return why.empty() ? MPC_OK : set_err(nullptr, MPC_E_INVAL, why);
+}
+
+int mpc_image_stats_enable(mpc_handle *h, uint64_t capacity_lines, uint64_t block_lines, unsigned sector_bytes, unsigned header_bits)
+{
+  if (!h) return MPC_E_INVAL;
+  if (h->algorithm == Algo::Fit) return set_err(h, MPC_E_INVAL, "Fit: an analysis has no per-line sizes to account");
+  const std::string why = image_refusal_of((unsigned)h->L, capacity_lines, block_lines, sector_bytes, header_bits);
+  if (!why.empty()) return set_err(h, MPC_E_INVAL, why);
+  auto &I = h->img;
+  if (I.on) {
+    if (I.capacity == capacity_lines && I.N == block_lines && I.sector_bytes == sector_bytes && I.header_bits == header_bits) return MPC_OK;
+    return set_err(h, MPC_E_INVAL, "image accounting is already on with " + image_values(I.capacity, I.N, I.sector_bytes, I.header_bits));
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  const u64 slots = image_slots(capacity_lines);
+  if (hipMalloc((void **)&I.d_keys, 2 * slots * sizeof(u64)) != hipSuccess) {        // keys | vals
+    I.d_keys = nullptr;
+    return set_err(h, MPC_E_NOMEM, "hipMalloc(image table, " + std::to_string(2 * slots * sizeof(u64)) + " bytes) failed");
+  }
+  // (the counters, then the 8 KiB table of a get's pass, which a handle that is polled then does not allocate per get)
+  if (!I.d_ctl && hipMalloc((void **)&I.d_ctl, (MPC_IMAGE_CTL_LEN + MPC_IMAGE_OUT_LEN) * sizeof(u64)) != hipSuccess) {
+    I.d_ctl = nullptr;
+    (void)hipFree(I.d_keys);
+    I.d_keys = nullptr;
+    return set_err(h, MPC_E_NOMEM, "hipMalloc(image counters) failed");
+  }
+  I.d_vals = I.d_keys + slots;
+  hipError_t e = hipMemset(I.d_keys, 0xff, slots * sizeof(u64));
+  if (e == hipSuccess) e = hipMemset(I.d_vals, 0, slots * sizeof(u64));
+  if (e == hipSuccess) e = hipMemset(I.d_ctl, 0, MPC_IMAGE_CTL_LEN * sizeof(u64));
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // (the kernels run on non-blocking streams)
+  if (e != hipSuccess) {               // the table does not stay behind a failed enable (mpc_destroy frees the counters)
+    (void)hipFree(I.d_keys);
+    I.d_keys = I.d_vals = nullptr;
+    return set_err(h, MPC_E_HIP, std::string("image accounting: clearing the table: ") + hipGetErrorString(e));
+  }
+  I.hash_mask = ~0ull;
+#if MPC_TESTING
+  // chains through most of the table at any capacity: keep only the low bits of the hash
+  if (const char *e = getenv("MPC_TEST_IMAGE_HASH_BITS")) {
+    const long bits = atol(e);
+    if (bits >= 0 && bits < 64) I.hash_mask = (1ull << bits) - 1ull;
+  }
+#endif
+  I.capacity = capacity_lines;
+  I.N = block_lines;
+  I.sector_bytes = sector_bytes;
+  I.header_bits = header_bits;
+  I.slots = slots;
+  I.seen = 0;
+  I.over = false;
+  h->stage.account[0] = 1;
+  h->stage.log_addrs = true;
+  I.on = true;
+  return MPC_OK;
+}
+
+int mpc_image_stats_get(mpc_handle *h, uint64_t *table, size_t n)
+{
+  if (!h) return MPC_E_INVAL;
+  if (!h->img.on) return set_err(h, MPC_E_INVAL, kImageOff);
+  if (!table || n != MPC_IMAGE_TABLE_LEN) return set_err(h, MPC_E_INVAL, kImageTableLen);
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = sync_all(h);
+  if (rc != MPC_OK) return rc;
+  HIPCHK(h, hipDeviceSynchronize());   // callers may have used their own streams
+  rc = pattern_status(h);
+  if (rc != MPC_OK) return rc;
+  const auto &I = h->img;
+  const u64 *ctl = I.ctl;              // (image_status has just read the counters, with the work complete)
+  std::vector<u64> out(MPC_IMAGE_OUT_LEN, 0);
+  const u64 D = ctl[MPC_IMAGE_CTL_KEYS];
+  const u64 S = (I.N * (u64)h->L + I.sector_bytes - 1) / I.sector_bytes;
+  if (D) {
+    // the block map lives for this get only: at most D blocks are touched
+    const u64 bslots = image_slots(D);
+    u64 *d_map = nullptr, *d_out = I.d_ctl + MPC_IMAGE_CTL_LEN;
+    if (hipMalloc((void **)&d_map, 2 * bslots * sizeof(u64)) != hipSuccess)
+      return set_err(h, MPC_E_NOMEM, "hipMalloc(image block map, " + std::to_string(2 * bslots * sizeof(u64)) + " bytes) failed");
+    MpcImageGetArgs A{};
+    A.keys = I.d_keys;
+    A.vals = I.d_vals;
+    A.slots = I.slots;
+    A.bkeys = d_map;
+    A.bvals = d_map + bslots;
+    A.bmask = bslots - 1;
+    A.hash_mask = I.hash_mask;
+    A.block_lines = I.N;
+    A.out = d_out;
+    A.line_size = (unsigned)h->L;
+    A.sector_bytes = I.sector_bytes;
+    A.header_bits = I.header_bits;
+    A.max_sectors = (unsigned)S;
+    hipError_t e = hipMemsetAsync(A.bkeys, 0xff, bslots * sizeof(u64), h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(A.bvals, 0, bslots * sizeof(u64), h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, MPC_IMAGE_OUT_LEN * sizeof(u64), h->stream);
+    if (e == hipSuccess) e = mpc_launch_image_get(&A, grid_for(h, I.slots, 256, 8), h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out.data(), d_out, MPC_IMAGE_OUT_LEN * sizeof(u64), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_map);
+    if (e != hipSuccess || e2 != hipSuccess)
+      return set_err(h, MPC_E_HIP, std::string("image accounting, get pass: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+    if (out[MPC_IMAGE_OUT_FULL]) return set_err(h, MPC_E_HIP, "image accounting: the block map of a get is full (internal error)");
+  }
+  std::fill(table, table + MPC_IMAGE_TABLE_LEN, 0);
+  table[0] = ctl[MPC_IMAGE_CTL_LINES];
+  table[1] = ctl[MPC_IMAGE_CTL_BITS];
+  table[2] = D;
+  table[3] = out[MPC_IMAGE_OUT_LATEST];
+  table[6] = out[MPC_IMAGE_OUT_CAPS];
+  table[7] = ctl[MPC_IMAGE_CTL_MISALIGNED];
+  table[8] = I.N;
+  table[9] = I.sector_bytes;
+  table[10] = I.header_bits;
+  table[11] = I.capacity;
+  for (u64 k = 1; k <= S; k++) {
+    const u64 v = out[MPC_IMAGE_OUT_HIST + k - 1];
+    table[16 + k - 1] = v;
+    table[4] += v;
+    table[5] += v * k;
+  }
+  return MPC_OK;
+}
+
+int mpc_compress_batch_addressed(mpc_handle *h, const uint8_t *lines, uint64_t n, const uint64_t *addresses, uint16_t *sizes, int8_t *sel)
+{
+  if (!h || (!lines && n) || (!addresses && n)) return MPC_E_INVAL;
+  if (!h->img.on) return set_err(h, MPC_E_INVAL, kImageOff);
+  if (n == 0) return MPC_OK;
+  return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, nullptr, addresses, &sizes, &sel);
+}
+
+int mpc_compress_batch_device_addressed(mpc_handle *h, const void *d_lines, uint64_t n, const uint64_t *d_addresses, uint16_t *d_sizes, int8_t *d_sel,
+                                        void *hip_stream)
+{
+  if (!h || (!d_addresses && n)) return MPC_E_INVAL;
+  if (!h->img.on) return set_err(h, MPC_E_INVAL, kImageOff);
+  if (((uintptr_t)d_addresses) & 7u) return set_err(h, MPC_E_INVAL, "device address buffer must be 8-byte aligned");
+  return batch_device(h, d_lines, n, nullptr, d_addresses, d_sizes, d_sel, hip_stream);
+}
+
+int mpc_group_image_stats_enable(mpc_group *g, uint64_t capacity_lines, uint64_t block_lines, unsigned sector_bytes, unsigned header_bits)
+{
+  if (!g) return MPC_E_INVAL;
+  const std::string why = image_refusal_of((unsigned)g->stage.L, capacity_lines, block_lines, sector_bytes, header_bits);
+  if (!why.empty()) return group_err(g, MPC_E_INVAL, why);
+  auto &G = g->img;
+  if (G.on) {
+    if (G.capacity == capacity_lines && G.N == block_lines && G.sector_bytes == sector_bytes && G.header_bits == header_bits) return MPC_OK;
+    return group_err(g, MPC_E_INVAL, "image accounting is already on with " + image_values(G.capacity, G.N, G.sector_bytes, G.header_bits));
+  }
+  // every member fresh (it starts at line 0), or on with the same values; then all at one line
+  bool first = true;
+  u64 at = 0;
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const auto &I = g->m[i]->img;
+    if (g->m[i]->algorithm == Algo::Fit) return group_err(g, MPC_E_INVAL, "Fit: an analysis has no per-line sizes to account");
+    if (I.on && (I.capacity != capacity_lines || I.N != block_lines || I.sector_bytes != sector_bytes || I.header_bits != header_bits))
+      return group_err(g, MPC_E_INVAL, "image accounting: member " + std::to_string(i) + " already counts with " + image_values(I.capacity, I.N, I.sector_bytes, I.header_bits));
+    const u64 seen = I.on ? I.seen : 0;
+    if (!first && seen != at)
+      return group_err(g, MPC_E_INVAL, "image accounting: member " + std::to_string(i) + " is at line " + std::to_string(seen) + ", the members before it at line " +
+                                           std::to_string(at) + " (reset the members first)");
+    at = seen;
+    first = false;
+  }
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const int rc = mpc_image_stats_enable(g->m[i], capacity_lines, block_lines, sector_bytes, header_bits);
+    if (rc != MPC_OK) return group_err(g, rc, "member " + std::to_string(i) + " (" + algorithm_name(g->m[i]->algorithm) + "): " + g->m[i]->error);
+  }
+  G.capacity = capacity_lines;
+  G.N = block_lines;
+  G.sector_bytes = sector_bytes;
+  G.header_bits = header_bits;
+  G.on = true;
+  return MPC_OK;
+}
+
+int mpc_group_image_stats_get(mpc_group *g, int member, uint64_t *table, size_t n)
+{
+  if (!g) return MPC_E_INVAL;
+  if (!g->img.on) return group_err(g, MPC_E_INVAL, kGroupImageOff);
+  if (!table || n != MPC_IMAGE_TABLE_LEN) return group_err(g, MPC_E_INVAL, kImageTableLen);
+  if (member < 0 || member >= (int)g->m.size())
+    return group_err(g, MPC_E_INVAL, "image accounting: member " + std::to_string(member) + " is not a member of the group");
+  int rc = mpc_group_sync(g);
+  if (rc != MPC_OK) return rc;
+  mpc_handle *h = g->m[(size_t)member];
+  rc = mpc_image_stats_get(h, table, n);
+  return rc == MPC_OK ? rc : group_err(g, rc, "member " + std::to_string(member) + " (" + algorithm_name(h->algorithm) + "): " + h->error);
+}
+
+int mpc_group_compress_batch_addressed(mpc_group *g, const uint8_t *lines, uint64_t n, const uint64_t *addresses, uint16_t *const *sizes,
+                                       int8_t *const *sel)
+{
+  if (!g || (!lines && n) || (!addresses && n)) return MPC_E_INVAL;
+  if (!g->img.on) return group_err(g, MPC_E_INVAL, kGroupImageOff);
+  if (n == 0) return MPC_OK;
+  group_refresh(g);
+  if (const int prc = group_pack_check(g)) return prc;
+  if (const int irc = group_image_check(g)) return irc;
+  return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, nullptr, addresses, sizes, sel);
+}
+
+int mpc_group_compress_batch_device_addressed(mpc_group *g, const void *d_lines, uint64_t n, const uint64_t *d_addresses, uint16_t *const *d_sizes,
+                                              int8_t *const *d_sel, void *hip_stream)
+{
+  if (!g || (!d_addresses && n)) return MPC_E_INVAL;
+  if (!g->img.on) return group_err(g, MPC_E_INVAL, kGroupImageOff);
+  if (((uintptr_t)d_addresses) & 7u) return group_err(g, MPC_E_INVAL, "device address buffer must be 8-byte aligned");
+  group_refresh(g);
+  return group_batch_device(g, d_lines, n, nullptr, d_addresses, d_sizes, d_sel, hip_stream);
+}
+
 // ---- per-class accounting (include/mpc_hip_classes.h) ----------------------------
 int mpc_class_stats_enable(mpc_handle *h, unsigned sector_bytes)
 {
@@ -2375,7 +2747,7 @@ int mpc_compress_batch_classed(mpc_handle *h, const uint8_t *lines, uint64_t n, 
   if (!h || (!lines && n)) return MPC_E_INVAL;
   if (!h->cls.on) return set_err(h, MPC_E_INVAL, kClassesOff);
   if (n == 0) return MPC_OK;
-  return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, classes, &sizes, &sel);
+  return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, classes, nullptr, &sizes, &sel);
 }
 
 int mpc_compress_batch_device_classed(mpc_handle *h, const void *d_lines, uint64_t n, const uint8_t *d_classes, uint16_t *d_sizes, int8_t *d_sel,
@@ -2383,7 +2755,7 @@ int mpc_compress_batch_device_classed(mpc_handle *h, const void *d_lines, uint64
 {
   if (!h) return MPC_E_INVAL;
   if (!h->cls.on) return set_err(h, MPC_E_INVAL, kClassesOff);
-  return batch_device(h, d_lines, n, d_classes, d_sizes, d_sel, hip_stream);
+  return batch_device(h, d_lines, n, d_classes, nullptr, d_sizes, d_sel, hip_stream);
 }
 
 int mpc_class_log_field(mpc_handle *h, int field)
@@ -2442,7 +2814,8 @@ int mpc_group_compress_batch_classed(mpc_group *g, const uint8_t *lines, uint64_
   if (n == 0) return MPC_OK;
   group_refresh(g);
   if (const int prc = group_pack_check(g)) return prc;
-  return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, classes, sizes, sel);
+  if (const int irc = group_image_check(g)) return irc;
+  return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, classes, nullptr, sizes, sel);
 }
 
 int mpc_group_compress_batch_device_classed(mpc_group *g, const void *d_lines, uint64_t n, const uint8_t *d_classes, uint16_t *const *d_sizes,
@@ -2452,7 +2825,7 @@ int mpc_group_compress_batch_device_classed(mpc_group *g, const void *d_lines, u
   if (!g->cls.on) return group_err(g, MPC_E_INVAL, kGroupClassesOff);
   if (d_classes && g->cls.from_member >= 0)
     return group_err(g, MPC_E_INVAL, "class accounting: the classes come from member " + std::to_string(g->cls.from_member) + ", the call must not bring its own");
-  return group_batch_device(g, d_lines, n, d_classes, d_sizes, d_sel, hip_stream);
+  return group_batch_device(g, d_lines, n, d_classes, nullptr, d_sizes, d_sel, hip_stream);
 }
 
 int mpc_group_class_log_field(mpc_group *g, int field)

@@ -2,12 +2,12 @@
 //
 // The launchers have C linkage, so a declaration that drifted from its definition would still link and then misbehave.
 // This header is therefore included by the callers (mpc_capi.hip, mpc_jit.h) AND by the units that define the
-// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_fit.hip, mpc_sizes.hip, mpc_classes.hip, mpc_pack.hip, the host section of mpc_vpc_lane.hip):
+// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_fit.hip, mpc_sizes.hip, mpc_classes.hip, mpc_pack.hip, mpc_image.hip, the host section of mpc_vpc_lane.hip):
 // the compiler sees declaration and definition together and refuses a mismatch.  Host code only -- the run-time
 // compiled source of mpc_jit.h (-DMPC_LANE_JIT) never sees it, and it is not one of the files that key the code
 // object cache.
 //
-// The parameter blocks are only named here (their definitions: mpc_device.h, mpc_sc2.h, mpc_pattern.h, mpc_sizes.h, mpc_classes.h, mpc_pack.h).
+// The parameter blocks are only named here (their definitions: mpc_device.h, mpc_sc2.h, mpc_pattern.h, mpc_sizes.h, mpc_classes.h, mpc_pack.h, mpc_image.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -21,6 +21,8 @@ struct MpcEvictSet;
 struct MpcSizesArgs;
 struct MpcClassArgs;
 struct MpcPackArgs;
+struct MpcImageArgs;
+struct MpcImageGetArgs;
 
 extern "C" {
 // mpc_kernels.hip
@@ -110,4 +112,10 @@ hipError_t mpc_launch_classes(const MpcClassArgs *A, unsigned long long n_lines,
 // `grid` bounds the workgroups; the launcher sizes them down to the blocks.  The name of the kernel form a block size takes.
 const char *mpc_pack_form_name(unsigned long long block_lines);
 hipError_t mpc_launch_pack(const MpcPackArgs *A, unsigned long long n_lines, int grid, hipStream_t stream);
+
+// mpc_image.hip: the latest size per line address of n_lines lines into the image's hash map (mpc_image.h); one launch, never cut.
+// The get pass: the image's live slots into the block map, then the touched blocks into the sector histogram (two launches).
+// `grid` bounds the workgroups; the launchers size them down to the work.
+hipError_t mpc_launch_image_update(const MpcImageArgs *A, unsigned long long n_lines, int grid, hipStream_t stream);
+hipError_t mpc_launch_image_get(const MpcImageGetArgs *A, int grid, hipStream_t stream);
 }

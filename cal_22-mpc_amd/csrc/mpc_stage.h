@@ -9,7 +9,9 @@
 // gets its device array of sizes whether or not the caller asked; the copy back and the pinned mirror stay tied to
 // "the caller asked".  The same holds for a member whose `selected` gives the classes of the lines (Stager::need_sel).
 // With per-class accounting on (mpc_classes.h) a chunk may carry one class byte per line: a pinned buffer per slot
-// beside the lines, with a device twin, both allocated when the first such chunk arrives.
+// beside the lines, with a device twin, both allocated when the first such chunk arrives.  With image accounting on
+// (mpc_image.h) a chunk carries one 64-bit address per line in the same way: a pinned buffer per slot with a device twin,
+// which exist only once a chunk has carried addresses.
 //
 // A handle is a group of one: the only difference between the two is "one output pointer" against "one output pointer
 // per member", so every function here takes arrays of `members` pointers.  What a stager feeds is told by a Sink:
@@ -37,8 +39,9 @@ constexpr size_t kMiniLines = 512;            // batches up to this many lines a
 struct Sink {
   void *ctx;
   // every member over the same device-visible lines on stream s; d_sizes / d_sel: one pointer per member (null: not asked for);
-  // d_classes: one device-visible class byte per line, or null (class 0)
-  int (*launch)(void *ctx, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes, hipStream_t s);
+  // d_classes: one device-visible class byte per line, or null (class 0); d_addrs: one device-visible address per line, or null
+  int (*launch)(void *ctx, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes, const uint64_t *d_addrs,
+                hipStream_t s);
   int (*fail)(void *ctx, int code, const std::string &msg);   // keeps the message, returns the code
   int (*status)(void *ctx);                                   // at a point where the work is complete (Pattern's capacity)
 };
@@ -61,6 +64,8 @@ struct Slot {
   uint8_t *d_in = nullptr;
   uint8_t *h_cls = nullptr;      // pinned, [stage_lines] class bytes; null until a chunk carries classes
   uint8_t *d_cls = nullptr;
+  uint64_t *h_adr = nullptr;     // pinned, [stage_lines] line addresses; null until a chunk carries addresses
+  uint64_t *d_adr = nullptr;
   // per member; the buffers are allocated when a call first asks for that member's per-line output
   std::vector<uint16_t *> d_sizes, h_sizes, user_sizes;   // user_*: where the pending results go
   std::vector<int8_t *> d_sel, h_sel, user_sel;
@@ -83,6 +88,8 @@ struct Stager {
   std::vector<char> need_sel;          // per member: the same for its `selected` (it gives the lines' classes)
   uint8_t *mini_cls = nullptr;         // [kMiniLines] pinned class bytes of an in-place call; null until one carries classes
   int log_field = 0;                   // MPC_CLASS_LOG_*: the class of a .log record's line (the owner keeps it 0 while accounting is off)
+  uint64_t *mini_adr = nullptr;        // [kMiniLines] pinned addresses of an in-place call; null until one carries addresses
+  bool log_addrs = false;              // a .log record's line carries its mem_addr (the owner keeps it false while image accounting is off)
 };
 
 inline void init(Stager &st, int device, int L, size_t members)
@@ -136,6 +143,14 @@ inline int ensure_classes(Stager &st, const Sink &k, Slot &s)
   return MPC_OK;
 }
 
+// the address buffers of a slot, when a walk carries addresses for the first time
+inline int ensure_addrs(Stager &st, const Sink &k, Slot &s)
+{
+  if (!s.h_adr) HIPCHK(k, hipHostMalloc((void **)&s.h_adr, st.stage_lines * sizeof(uint64_t), hipHostMallocDefault));
+  if (!s.d_adr) HIPCHK(k, hipMalloc((void **)&s.d_adr, st.stage_lines * sizeof(uint64_t)));
+  return MPC_OK;
+}
+
 // wait for a slot's in-flight chunk and hand its per-line results to the caller
 inline int retire(Stager &st, const Sink &k, Slot &s)
 {
@@ -149,10 +164,12 @@ inline int retire(Stager &st, const Sink &k, Slot &s)
   return MPC_OK;
 }
 
-// submit the chunk already sitting in s.h_in (with_classes: and its class bytes in s.h_cls): one copy, then the sink's
+// submit the chunk already sitting in s.h_in (with_classes: and its class bytes in s.h_cls; with_addrs: and its
+// addresses in s.h_adr): one copy, then the sink's
 // launch on the slot's stream.
 // sizes / sel: the caller's arrays of per-member pointers (or null), `first` the chunk's first line in them.
-inline int submit(Stager &st, const Sink &k, Slot &s, u64 lines, uint16_t *const *sizes, int8_t *const *sel, u64 first, bool with_classes)
+inline int submit(Stager &st, const Sink &k, Slot &s, u64 lines, uint16_t *const *sizes, int8_t *const *sel, u64 first, bool with_classes,
+                  bool with_addrs)
 {
   for (size_t i = 0; i < st.members; i++) {
     s.user_sizes[i] = (sizes && sizes[i]) ? sizes[i] + first : nullptr;
@@ -164,7 +181,9 @@ inline int submit(Stager &st, const Sink &k, Slot &s, u64 lines, uint16_t *const
   }
   HIPCHK(k, hipMemcpyAsync(s.d_in, s.h_in, lines * (u64)st.L, hipMemcpyHostToDevice, s.stream));
   if (with_classes) HIPCHK(k, hipMemcpyAsync(s.d_cls, s.h_cls, lines, hipMemcpyHostToDevice, s.stream));
-  const int rc = k.launch(k.ctx, s.d_in, lines, st.ask_sizes.data(), st.ask_sel.data(), with_classes ? s.d_cls : nullptr, s.stream);
+  if (with_addrs) HIPCHK(k, hipMemcpyAsync(s.d_adr, s.h_adr, lines * sizeof(uint64_t), hipMemcpyHostToDevice, s.stream));
+  const int rc = k.launch(k.ctx, s.d_in, lines, st.ask_sizes.data(), st.ask_sel.data(), with_classes ? s.d_cls : nullptr, with_addrs ? s.d_adr : nullptr,
+                          s.stream);
   if (rc != MPC_OK) return rc;
   for (size_t i = 0; i < st.members; i++) {
     if (s.user_sizes[i]) HIPCHK(k, hipMemcpyAsync(s.h_sizes[i], s.d_sizes[i], lines * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
@@ -217,8 +236,8 @@ inline int finish(Stager &st, const Sink &k, hipStream_t own)
 // n <= kMiniLines lines, evaluated in place from pinned host memory: the sink's launch on stream s, one synchronisation
 // (polling hipStreamQuery instead was slower: 46 k vs 58 k lines/s).  The stream is the caller's choice and differs on
 // purpose: a handle's own stream, a group's first slot stream (idle: every group call ends synchronised).
-inline int in_place(Stager &st, const Sink &k, hipStream_t s, const uint8_t *lines, u64 n, const uint8_t *classes, uint16_t *const *sizes,
-                    int8_t *const *sel)
+inline int in_place(Stager &st, const Sink &k, hipStream_t s, const uint8_t *lines, u64 n, const uint8_t *classes, const uint64_t *addrs,
+                    uint16_t *const *sizes, int8_t *const *sel)
 {
   const size_t nm = st.members;
   if (!st.mini) HIPCHK(k, hipHostMalloc((void **)&st.mini, kMiniLines * ((size_t)st.L + nm * (sizeof(uint16_t) + 1)), hipHostMallocDefault));
@@ -233,7 +252,11 @@ inline int in_place(Stager &st, const Sink &k, hipStream_t s, const uint8_t *lin
     if (!st.mini_cls) HIPCHK(k, hipHostMalloc((void **)&st.mini_cls, kMiniLines, hipHostMallocDefault));
     std::memcpy(st.mini_cls, classes, (size_t)n);
   }
-  const int rc = k.launch(k.ctx, st.mini, n, st.ask_sizes.data(), st.ask_sel.data(), classes ? st.mini_cls : nullptr, s);
+  if (addrs) {
+    if (!st.mini_adr) HIPCHK(k, hipHostMalloc((void **)&st.mini_adr, kMiniLines * sizeof(uint64_t), hipHostMallocDefault));
+    std::memcpy(st.mini_adr, addrs, (size_t)n * sizeof(uint64_t));
+  }
+  const int rc = k.launch(k.ctx, st.mini, n, st.ask_sizes.data(), st.ask_sel.data(), classes ? st.mini_cls : nullptr, addrs ? st.mini_adr : nullptr, s);
   if (rc != MPC_OK) { (void)hipStreamSynchronize(s); return rc; }   // (what was enqueued before the failure reads st.mini)
   HIPCHK(k, hipStreamSynchronize(s));
   for (size_t i = 0; i < nm; i++) {
@@ -244,10 +267,12 @@ inline int in_place(Stager &st, const Sink &k, hipStream_t s, const uint8_t *lin
 }
 
 // A walk over a trace: retire a slot, let `fill` put up to `room` lines into its pinned buffer (with_classes: and their
-// class bytes into the slot's class buffer, else that argument is null), submit them, take the other slot; until fill
+// class bytes into the slot's class buffer, with_addrs: and their addresses into the slot's address buffer, else that
+// argument is null), submit them, take the other slot; until fill
 // returns 0 lines or fails (< 0: the code, already reported).  Then finish, or abandon after a failure.
 template <class Fill>
-inline int pump(Stager &st, const Sink &k, hipStream_t own, uint16_t *const *sizes, int8_t *const *sel, u64 *lines_done, bool with_classes, Fill fill)
+inline int pump(Stager &st, const Sink &k, hipStream_t own, uint16_t *const *sizes, int8_t *const *sel, u64 *lines_done, bool with_classes,
+                bool with_addrs, Fill fill)
 {
   int rc = ensure(st, k);
   u64 done = 0;
@@ -256,11 +281,12 @@ inline int pump(Stager &st, const Sink &k, hipStream_t own, uint16_t *const *siz
     Slot &s = st.slots[which];
     rc = retire(st, k, s);   // the slot's previous chunk (overlapped with the other slot's work)
     if (rc == MPC_OK && with_classes) rc = ensure_classes(st, k, s);
+    if (rc == MPC_OK && with_addrs) rc = ensure_addrs(st, k, s);
     if (rc != MPC_OK) break;
-    const long long got = fill(s.h_in, with_classes ? s.h_cls : nullptr, (u64)st.stage_lines, done);
+    const long long got = fill(s.h_in, with_classes ? s.h_cls : nullptr, with_addrs ? s.h_adr : nullptr, (u64)st.stage_lines, done);
     if (got < 0) rc = (int)got;
     if (got <= 0) break;
-    rc = submit(st, k, s, (u64)got, sizes, sel, done, with_classes);
+    rc = submit(st, k, s, (u64)got, sizes, sel, done, with_classes, with_addrs);
     if (rc != MPC_OK) break;
     done += (u64)got;
     which ^= 1;
@@ -272,16 +298,17 @@ inline int pump(Stager &st, const Sink &k, hipStream_t own, uint16_t *const *siz
 }
 
 // n lines in the caller's memory.  sizes / sel: arrays of one pointer per member (the array or any entry may be null).
-// classes: one class byte per line in the caller's memory, or null.
-inline int compress_batch(Stager &st, const Sink &k, hipStream_t own, const uint8_t *lines, u64 n, const uint8_t *classes, uint16_t *const *sizes,
-                          int8_t *const *sel)
+// classes: one class byte per line in the caller's memory, or null; addrs: one address per line in the caller's memory, or null.
+inline int compress_batch(Stager &st, const Sink &k, hipStream_t own, const uint8_t *lines, u64 n, const uint8_t *classes, const uint64_t *addrs,
+                          uint16_t *const *sizes, int8_t *const *sel)
 {
   HIPCHK(k, hipSetDevice(st.device));
-  if (n <= kMiniLines) return in_place(st, k, own ? own : st.slots[0].stream, lines, n, classes, sizes, sel);
-  return pump(st, k, own, sizes, sel, nullptr, classes != nullptr, [&](uint8_t *buf, uint8_t *cls, u64 room, u64 done) -> long long {
+  if (n <= kMiniLines) return in_place(st, k, own ? own : st.slots[0].stream, lines, n, classes, addrs, sizes, sel);
+  return pump(st, k, own, sizes, sel, nullptr, classes != nullptr, addrs != nullptr, [&](uint8_t *buf, uint8_t *cls, uint64_t *adr, u64 room, u64 done) -> long long {
     const u64 take = (n - done) < room ? (n - done) : room;
     mpctrace::parallel_copy(buf, lines + done * (u64)st.L, (size_t)(take * (u64)st.L));
     if (cls) std::memcpy(cls, classes + done, (size_t)take);
+    if (adr) std::memcpy(adr, addrs + done, (size_t)take * sizeof(uint64_t));
     return (long long)take;
   });
 }
@@ -308,7 +335,7 @@ inline int compress_npy(Stager &st, const Sink &k, hipStream_t own, const char *
   if (hipSetDevice(st.device) != hipSuccess) { fclose(f); return k.fail(k.ctx, MPC_E_HIP, "hipSetDevice failed"); }
   const int fd = fileno(f);
   u64 done_rows = 0;
-  rc = pump(st, k, own, nullptr, nullptr, &done_rows, false, [&](uint8_t *buf, uint8_t *, u64 room, u64 done) -> long long {
+  rc = pump(st, k, own, nullptr, nullptr, &done_rows, false, false, [&](uint8_t *buf, uint8_t *, uint64_t *, u64 room, u64 done) -> long long {
     const u64 take = (end - begin - done) < room ? (end - begin - done) : room;
     if (take && !mpctrace::parallel_pread(fd, buf, (size_t)(take * cols), off + (begin + done) * cols))
       return k.fail(k.ctx, MPC_E_PARSE, "short read: .npy file is truncated");
@@ -333,7 +360,7 @@ inline int compress_gpgpusim_log(Stager &st, const Sink &k, hipStream_t own, con
   u64 requests = 0, lines = 0;
   bool first = true, ended = false;
   const int field = st.log_field;       // the class of a record's line: a byte of the record's header (mpc_hip_classes.h)
-  rc = pump(st, k, own, nullptr, nullptr, &lines, field != MPC_CLASS_LOG_NONE, [&](uint8_t *buf, uint8_t *cls, u64 room, u64) -> long long {
+  rc = pump(st, k, own, nullptr, nullptr, &lines, field != MPC_CLASS_LOG_NONE, st.log_addrs, [&](uint8_t *buf, uint8_t *cls, uint64_t *adr, u64 room, u64) -> long long {
     u64 fill = 0;
     uint32_t req_type, req_size;
     const unsigned char *payload;
@@ -351,6 +378,7 @@ inline int compress_gpgpusim_log(Stager &st, const Sink &k, hipStream_t own, con
           const unsigned char *rec = payload - mpctrace::kLogRecordHeader;
           cls[fill] = field == MPC_CLASS_LOG_KERNEL ? rec[0] : field == MPC_CLASS_LOG_MFTYPE ? rec[1] : (req_type == 4u ? 1 : 0);
         }
+        if (adr) std::memcpy(&adr[fill], payload - mpctrace::kLogRecordHeader + mpctrace::kLogRecordAddr, sizeof(uint64_t));   // mem_addr
         fill++;
       }
       requests++;
@@ -373,6 +401,8 @@ inline void destroy(Stager &st)
     if (s.d_in) (void)hipFree(s.d_in);
     if (s.h_cls) (void)hipHostFree(s.h_cls);
     if (s.d_cls) (void)hipFree(s.d_cls);
+    if (s.h_adr) (void)hipHostFree(s.h_adr);
+    if (s.d_adr) (void)hipFree(s.d_adr);
     for (uint16_t *p : s.d_sizes) if (p) (void)hipFree(p);
     for (uint16_t *p : s.h_sizes) if (p) (void)hipHostFree(p);
     for (int8_t *p : s.d_sel) if (p) (void)hipFree(p);
@@ -385,6 +415,8 @@ inline void destroy(Stager &st)
   st.mini = nullptr;
   if (st.mini_cls) (void)hipHostFree(st.mini_cls);
   st.mini_cls = nullptr;
+  if (st.mini_adr) (void)hipHostFree(st.mini_adr);
+  st.mini_adr = nullptr;
   st.slots_ready = false;
 }
 

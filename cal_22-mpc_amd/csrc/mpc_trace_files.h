@@ -80,6 +80,7 @@ inline int parse_npy_header(FILE *f, u64 *rows, u64 *cols, u64 *data_off, std::s
 // ---- GPGPU-Sim .log: a file header of 1 + 7 * 17 bytes, then records of a 62-byte header (request type at 38, payload
 // size at 58) and the payload (LoaderGPGPU.cpp:9-119) ----
 constexpr int kLogKeys = 17, kLogRecordHeader = 62;
+constexpr int kLogRecordAddr = 30;      // mem_addr, a u64 (LoaderGPGPU.cpp)
 constexpr u64 kLogFileHeader = 1 + 7 * kLogKeys;
 
 // validates the file header of a GPGPU-Sim trace (LoaderGPGPU.cpp:93-119)

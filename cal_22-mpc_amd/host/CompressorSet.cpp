@@ -104,6 +104,22 @@ PackReport CompressorSet::GetPackStats(size_t i)
   return report;
 }
 
+void CompressorSet::EnableImageStats(unsigned long long blockLines, unsigned sectorBytes, unsigned headerBits, unsigned long long capacityLines)
+{
+  Prepare();
+  int rc = mpc_group_image_stats_enable(m_Group, capacityLines, blockLines, sectorBytes, headerBits);
+  if (rc != MPC_OK) fail("CompressorSet::EnableImageStats", rc, mpc_group_last_error(m_Group));
+}
+
+ImageReport CompressorSet::GetImageStats(size_t i)
+{
+  Prepare();
+  ImageReport report(GetLineSize());
+  int rc = mpc_group_image_stats_get(m_Group, (int)i, report.Table.data(), report.Table.size());
+  if (rc != MPC_OK) fail("CompressorSet::GetImageStats", rc, mpc_group_last_error(m_Group));
+  return report;
+}
+
 void CompressorSet::SetLogClassField(int field)
 {
   int rc = mpc_group_class_log_field(m_Group, field);

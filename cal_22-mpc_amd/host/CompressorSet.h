@@ -11,6 +11,7 @@
 
 #include "Compressor.h"
 #include "ClassReport.h"
+#include "ImageReport.h"
 #include "PackReport.h"
 #include "SizeReport.h"
 
@@ -58,6 +59,12 @@ public:
   void EnablePackStats(unsigned long long blockLines, unsigned sectorBytes = ACCESS_GRAN, unsigned headerBits = 0);
   // member i's table, or with i == BestMember that of the per-line smallest size
   PackReport GetPackStats(size_t i);
+  // ADDITIVE: EnableImageStats for every member with the same values; a member's image is its own
+  // (mpc_group_image_stats_enable); off by default
+  void EnableImageStats(unsigned long long blockLines, unsigned sectorBytes = ACCESS_GRAN, unsigned headerBits = 0,
+                        unsigned long long capacityLines = 1ull << 24);
+  // member i's table
+  ImageReport GetImageStats(size_t i);
 
 private:
   void Prepare();      // members' buffered lines first

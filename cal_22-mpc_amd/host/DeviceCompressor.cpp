@@ -115,6 +115,22 @@ PackReport DeviceCompressor::GetPackStats()
   return report;
 }
 
+void DeviceCompressor::EnableImageStats(unsigned long long blockLines, unsigned sectorBytes, unsigned headerBits, unsigned long long capacityLines)
+{
+  FlushLines();
+  int rc = mpc_image_stats_enable(m_Handle, capacityLines, blockLines, sectorBytes, headerBits);
+  if (rc != MPC_OK) Fail(m_Tag + "::EnableImageStats", rc);
+}
+
+ImageReport DeviceCompressor::GetImageStats()
+{
+  FlushLines();
+  ImageReport report(m_LineSize);
+  int rc = mpc_image_stats_get(m_Handle, report.Table.data(), report.Table.size());
+  if (rc != MPC_OK) Fail(m_Tag + "::GetImageStats", rc);
+  return report;
+}
+
 void DeviceCompressor::SetLogClassField(int field)
 {
   int rc = mpc_class_log_field(m_Handle, field);

@@ -8,6 +8,7 @@
 
 #include "Compressor.h"
 #include "ClassReport.h"
+#include "ImageReport.h"
 #include "PackReport.h"
 #include "SizeReport.h"
 
@@ -46,6 +47,12 @@ public:
   void EnablePackStats(unsigned long long blockLines, unsigned sectorBytes = ACCESS_GRAN, unsigned headerBits = 0);
   // ... that table (mpc_pack_stats_get), buffered lines evaluated first; a failure (not enabled) exits like every other
   PackReport GetPackStats();
+  // ADDITIVE: keep, from now on, the size of the latest line per line address (a .log's mem_addr) for up to capacityLines
+  // distinct lines, and report the sectors of address-aligned blocks of blockLines lines (mpc_image_stats_enable); off by default
+  void EnableImageStats(unsigned long long blockLines, unsigned sectorBytes = ACCESS_GRAN, unsigned headerBits = 0,
+                        unsigned long long capacityLines = 1ull << 24);
+  // ... that table (mpc_image_stats_get; not destructive), buffered lines evaluated first; a failure exits like every other
+  ImageReport GetImageStats();
 
 protected:
   // tag: the short name in front of this class's messages ("BDI", "VPC", ...)

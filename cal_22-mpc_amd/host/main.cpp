@@ -20,6 +20,10 @@
 // sectors that blocks of N consecutive lines occupy when they are packed and rounded up once).  With a list every member
 // gets its file, and with --size-histogram the per-line best of the list BEST_results_pack.csv.  Next to --pack, --sector
 // does not imply --size-histogram.  Without --pack nothing changes.
+// ADDITIVE: --image N [--sector BYTES] [--image-header BITS] [--image-capacity LINES] also writes
+// OUTDIR/<stem>_results_image.csv (comp::ImageReport: the latest size per line address of a GPGPU-Sim .log trace's
+// mem_addr, and the sectors that address-aligned blocks of N lines of that image occupy).  With a list every member gets
+// its file.  It needs a .log input.  Next to --image, --sector does not imply --size-histogram.  Without --image nothing changes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -60,6 +64,12 @@ static const char *kHelp =
     "                       of that many consecutive lines occupy when packed; the\n"
     "                       sector size is --sector's (which then implies nothing).\n"
     "      --pack-header arg Bits added to every block of --pack. Default=0\n"
+    "      --image arg      Also write <stem>_results_image.csv: the latest size per\n"
+    "                       line address of a .log trace, and the sectors that aligned\n"
+    "                       blocks of that many lines occupy; the sector size is\n"
+    "                       --sector's (which then implies nothing).\n"
+    "      --image-header arg Bits added to every block of --image. Default=0\n"
+    "      --image-capacity arg Distinct lines the image can hold. Default=16777216\n"
     "      --by arg         Also write <stem>_results_classes.csv: lines, bits and\n"
     "                       sectors per class of a line [kernel/rw/mftype/cluster].\n"
     "                       kernel, rw, mftype: a field of a .log trace's records;\n"
@@ -79,6 +89,9 @@ struct Args {
   bool has_pack = false, has_pack_header = false;      // ADDITIVE --pack N [--pack-header BITS]: <stem>_results_pack.csv (PackReport.h)
   unsigned long long pack = 0;
   unsigned pack_header = 0;
+  bool has_image = false, has_image_header = false, has_image_capacity = false;      // ADDITIVE --image N [...]: <stem>_results_image.csv (ImageReport.h)
+  unsigned long long image = 0, image_capacity = 1ull << 24;
+  unsigned image_header = 0;
 };
 
 // the value of --pack / --pack-header: digits only, up to `most`
@@ -170,6 +183,26 @@ static void requirePack(const Args &a, unsigned traceLineSize)
     printf("--pack %llu with --sector %u: a block of %llu bytes has more than %zu sectors.\n", a.pack, a.sector, blockBytes, comp::PackReport::MaxSectors);
     exit(1);
   }
+}
+
+// --image against the trace: a sector is at most a block, a block at most 1024 sectors
+static void requireImage(const Args &a, unsigned traceLineSize)
+{
+  if (!a.has_image) return;
+  const unsigned long long blockBytes = a.image * traceLineSize;
+  if (a.sector > blockBytes) {
+    printf("--image %llu with --sector %u: a sector cannot be larger than a block of %llu bytes.\n", a.image, a.sector, blockBytes);
+    exit(1);
+  }
+  if ((blockBytes + a.sector - 1) / a.sector > comp::ImageReport::MaxSectors) {
+    printf("--image %llu with --sector %u: a block of %llu bytes has more than %zu sectors.\n", a.image, a.sector, blockBytes, comp::ImageReport::MaxSectors);
+    exit(1);
+  }
+}
+
+static void writeImage(comp::ImageReport report, const std::string &workloadName, const std::string &outputDirPath, const std::string &saveFileName)
+{
+  report.Print(workloadName, outputDirPath + "/" + saveFileName + "_results_image.csv");
 }
 
 static void writePack(comp::PackReport report, const std::string &workloadName, const std::string &outputDirPath, const std::string &saveFileName)
@@ -304,6 +337,47 @@ int main(int argc, char **argv)
       a.has_pack_header = true;
       continue;
     }
+    if (arg == "--image" || arg.compare(0, 8, "--image=") == 0) {
+      if (arg == "--image" && i + 1 >= argc) {
+        std::cout << "Option 'image' is missing an argument" << std::endl;
+        exit(1);
+      }
+      const std::string value = arg == "--image" ? argv[++i] : arg.substr(8);
+      if (!takeNumber(value, 1ull << 19, a.image) || a.image == 0) {
+        std::cout << "--image takes a number of lines from 1 to 524288, not \"" << value << "\"." << std::endl;
+        return 1;
+      }
+      a.has_image = true;
+      continue;
+    }
+    if (arg == "--image-header" || arg.compare(0, 15, "--image-header=") == 0) {
+      if (arg == "--image-header" && i + 1 >= argc) {
+        std::cout << "Option 'image-header' is missing an argument" << std::endl;
+        exit(1);
+      }
+      const std::string value = arg == "--image-header" ? argv[++i] : arg.substr(15);
+      unsigned long long bits = 0;
+      if (!takeNumber(value, 65535, bits)) {
+        std::cout << "--image-header takes a number of bits from 0 to 65535, not \"" << value << "\"." << std::endl;
+        return 1;
+      }
+      a.image_header = (unsigned)bits;
+      a.has_image_header = true;
+      continue;
+    }
+    if (arg == "--image-capacity" || arg.compare(0, 17, "--image-capacity=") == 0) {
+      if (arg == "--image-capacity" && i + 1 >= argc) {
+        std::cout << "Option 'image-capacity' is missing an argument" << std::endl;
+        exit(1);
+      }
+      const std::string value = arg == "--image-capacity" ? argv[++i] : arg.substr(17);
+      if (!takeNumber(value, 1ull << 28, a.image_capacity) || a.image_capacity == 0) {
+        std::cout << "--image-capacity takes a number of lines from 1 to 268435456, not \"" << value << "\"." << std::endl;
+        return 1;
+      }
+      a.has_image_capacity = true;
+      continue;
+    }
     if (arg == "--by" || arg.compare(0, 5, "--by=") == 0) {
       if (arg == "--by" && i + 1 >= argc) {
         std::cout << "Option 'by' is missing an argument" << std::endl;
@@ -320,7 +394,7 @@ int main(int argc, char **argv)
     std::cout << "Option '" << arg << "' does not exist" << std::endl;
     return 1;
   }
-  if (a.has_sector && !a.has_pack) a.size_histogram = true;      // (--sector implies --size-histogram, but not next to --pack)
+  if (a.has_sector && !a.has_pack && !a.has_image) a.size_histogram = true;      // (--sector implies --size-histogram, but not next to --pack or --image)
   std::string algorithm = a.has_algorithm ? a.algorithm : "VPC";
   bool help = a.help;
   if (!a.has_input) help = true;
@@ -380,6 +454,19 @@ int main(int argc, char **argv)
     std::cout << "--pack is evaluated in batches: it does not go with --per-line / --line-buffer." << std::endl;
     return 1;
   }
+  // --image: checked before anything is opened or written, one message each
+  if ((a.has_image_header || a.has_image_capacity) && !a.has_image) {
+    std::cout << "--image-header and --image-capacity belong to --image: give --image N too." << std::endl;
+    return 1;
+  }
+  if (a.has_image && !trace::IsGpgpuSimLog(a.input)) {
+    std::cout << "--image takes the line addresses from the records of a GPGPU-Sim .log trace: \"" << a.input << "\" is not one." << std::endl;
+    return 1;
+  }
+  if (a.has_image && a.per_line) {
+    std::cout << "--image is evaluated in batches: it does not go with --per-line / --line-buffer." << std::endl;
+    return 1;
+  }
   const std::string tracePath = a.input, configPath = a.config, outputDirPath = a.has_output ? a.output : "";
   if (!list.empty()) return runList(list, tracePath, configPath, outputDirPath, a);
 
@@ -387,6 +474,7 @@ int main(int argc, char **argv)
   trace::Loader *loader = openTrace(tracePath, &memReq);
   requireSector(a, loader->GetCachelineSize());
   requirePack(a, loader->GetCachelineSize());
+  requireImage(a, loader->GetCachelineSize());
 
   comp::DeviceCompressor *compressor = makeEvaluator(algorithm, configPath, loader->GetCachelineSize());
   if (!compressor) {
@@ -406,6 +494,7 @@ int main(int argc, char **argv)
     compressor->SetLogClassField(logFieldOf(a.by));
   }
   if (a.has_pack) compressor->EnablePackStats(a.pack, a.sector, a.pack_header);
+  if (a.has_image) compressor->EnableImageStats(a.image, a.sector, a.image_header, a.image_capacity);
   if (!a.per_line && (loader->SupportsBatch() || !loader->GetStreamablePath().empty()))
     compressBatches(compressor, loader);
   else
@@ -419,6 +508,7 @@ int main(int argc, char **argv)
   if (a.size_histogram) writeSizes(compressor->GetSizeHistogram(a.sector), workloadName, outputDirPath, saveFileName);
   if (a.has_by) writeClasses(compressor->GetClassStats(), workloadName, outputDirPath, saveFileName);
   if (a.has_pack) writePack(compressor->GetPackStats(), workloadName, outputDirPath, saveFileName);
+  if (a.has_image) writeImage(compressor->GetImageStats(), workloadName, outputDirPath, saveFileName);
 
   delete memReq;      // (the reference leaks its request object)
   delete loader;
@@ -440,6 +530,7 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
   const unsigned lineSize = loader->GetCachelineSize();
   requireSector(a, lineSize);
   requirePack(a, lineSize);
+  requireImage(a, lineSize);
   std::vector<comp::DeviceCompressor *> evaluators;
   std::vector<comp::Compressor *> members;
   for (const std::string &n : names) {
@@ -462,6 +553,7 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
       }
     }
     if (a.has_pack) set.EnablePackStats(a.pack, a.sector, a.pack_header);      // (behind EnableBest: the best of the list gets its table)
+    if (a.has_image) set.EnableImageStats(a.image, a.sector, a.image_header, a.image_capacity);
     compressBatches(&set, loader);
     for (size_t i = 0; i < names.size(); i++) {
       comp::CompResult *compStat = set.GetResult(i);
@@ -471,6 +563,7 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
       if (a.size_histogram) writeSizes(evaluators[i]->GetSizeHistogram(a.sector), workloadName, outputDirPath, saveFileName);
       if (a.has_by) writeClasses(set.GetClassStats(i), workloadName, outputDirPath, saveFileName);
       if (a.has_pack) writePack(set.GetPackStats(i), workloadName, outputDirPath, saveFileName);
+      if (a.has_image) writeImage(set.GetImageStats(i), workloadName, outputDirPath, saveFileName);
     }
     if (a.size_histogram) {
       const comp::BestReport best = set.GetBest(a.sector);

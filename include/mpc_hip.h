@@ -383,6 +383,9 @@ int mpc_group_sync(mpc_group *g);
 /* ---- pack accounting: the sectors that blocks of N consecutive lines occupy when they are packed and rounded once ----
  * Additive and off by default as well, in a header of its own for the same reason.                                  */
 #include "mpc_hip_pack.h"
+/* ---- image accounting: the latest size per line address, and the sectors that address-aligned blocks of it occupy ----
+ * Additive and off by default as well, in a header of its own for the same reason.                                  */
+#include "mpc_hip_image.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

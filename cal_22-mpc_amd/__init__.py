@@ -33,6 +33,9 @@ MPC_PACK_BEST = -1            # mpc_group_pack_stats_get: the table of the per-l
 MPC_IMAGE_MAX_SECTORS = 1024  # an image table is uint64[16 + 1024] (include/mpc_hip_image.h)
 MPC_IMAGE_TABLE_LEN = 16 + MPC_IMAGE_MAX_SECTORS
 MPC_IMAGE_MAX_CAPACITY = 1 << 28
+MPC_SNAPSHOT_MAX_CAPACITY = 1 << 28   # include/mpc_hip_snapshot.h
+MPC_SNAPSHOT_TABLE_LEN = 8            # a snapshot's stats and plan vectors
+SNAPSHOT_PARTIAL = {"skip": 0, "zero": 1}      # MPC_SNAPSHOT_PARTIAL_*
 CLASS_LOG_FIELDS = {None: 0, "kernel": 1, "rw": 2, "mftype": 3}      # MPC_CLASS_LOG_*
 MPC_PATH_VPC_FAST, MPC_PATH_VPC_GENERIC, MPC_PATH_BDI, MPC_PATH_FPC, MPC_PATH_BPC, MPC_PATH_SC2, MPC_PATH_PATTERN = 1, 2, 3, 4, 5, 6, 7
 MPC_PATH_PATTERN_EVICTING = 9
@@ -177,6 +180,20 @@ def lib() -> C.CDLL:
             "mpc_group_image_stats_get": ([H, C.c_int, C.c_void_p, C.c_size_t], C.c_int),
             "mpc_group_compress_batch_addressed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
             "mpc_group_compress_batch_device_addressed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "mpc_snapshot_check_values": ([C.c_uint, C.c_uint64, C.c_uint], C.c_int),
+            "mpc_snapshot_create": ([C.c_uint, C.c_uint64, C.c_int, C.POINTER(H)], C.c_int),
+            "mpc_snapshot_destroy": ([H], None),
+            "mpc_snapshot_reset": ([H], C.c_int),
+            "mpc_snapshot_last_error": ([H], C.c_char_p),
+            "mpc_snapshot_add": ([H, C.c_void_p, C.c_uint64, C.c_void_p], C.c_int),
+            "mpc_snapshot_add_device": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p], C.c_int),
+            "mpc_snapshot_add_gpgpusim_log": ([H, C.c_char_p, C.POINTER(C.c_uint64)], C.c_int),
+            "mpc_snapshot_stats": ([H, C.c_void_p], C.c_int),
+            "mpc_snapshot_plan": ([H, C.c_uint, C.c_int, C.c_void_p], C.c_int),
+            "mpc_snapshot_write_lines": ([H, C.c_uint, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "mpc_snapshot_read_lines": ([H, C.c_uint, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "mpc_snapshot_evaluate": ([H, H, C.c_uint, C.c_int, C.c_int], C.c_int),
+            "mpc_snapshot_evaluate_group": ([H, H, C.c_uint, C.c_int, C.c_int], C.c_int),
         }
         for name, (args, res) in sigs.items():
             fn = getattr(L, name)
@@ -217,6 +234,10 @@ EXPORTED_PACK_SYMBOLS = ["mpc_pack_stats_enable", "mpc_pack_check_values", "mpc_
 EXPORTED_IMAGE_SYMBOLS = ["mpc_image_stats_enable", "mpc_image_check_values", "mpc_image_stats_get", "mpc_compress_batch_addressed",
                           "mpc_compress_batch_device_addressed", "mpc_image_hash", "mpc_group_image_stats_enable", "mpc_group_image_stats_get",
                           "mpc_group_compress_batch_addressed", "mpc_group_compress_batch_device_addressed"]
+# The snapshot entry points, declared in include/mpc_hip_snapshot.h (which mpc_hip.h includes).
+EXPORTED_SNAPSHOT_SYMBOLS = ["mpc_snapshot_check_values", "mpc_snapshot_create", "mpc_snapshot_destroy", "mpc_snapshot_reset", "mpc_snapshot_last_error",
+                             "mpc_snapshot_add", "mpc_snapshot_add_device", "mpc_snapshot_add_gpgpusim_log", "mpc_snapshot_stats", "mpc_snapshot_plan",
+                             "mpc_snapshot_write_lines", "mpc_snapshot_read_lines", "mpc_snapshot_evaluate", "mpc_snapshot_evaluate_group"]
 
 
 def gpgpusim_log_line_size(path: str) -> int:
@@ -1066,6 +1087,123 @@ class EvaluatorSet:
         """The class of a line is member ``member``'s ``selected`` + 1 (``mpc_group_class_from_member``): for a VPC
         member 0 = uncompressed, k + 1 = module k's cluster; for a BDI member the state + 1.  ``None`` switches it off."""
         self._check(lib().mpc_group_class_from_member(self._g, -1 if member is None else int(member)))
+
+
+def _snapshot_partial(partial) -> int:
+    if partial not in SNAPSHOT_PARTIAL:
+        raise ValueError(f"partial: 'skip' or 'zero', not {partial!r}")
+    return SNAPSHOT_PARTIAL[partial]
+
+
+def _snapshot_values(fn: str, unit_bytes, capacity, line_size):
+    """The three values of a snapshot as the C ABI takes them (unsigned)."""
+    unit_bytes, capacity, line_size = int(unit_bytes), int(capacity), int(line_size)
+    if not (0 <= unit_bytes < 1 << 32 and 0 <= capacity < 1 << 64 and 0 <= line_size < 1 << 32):
+        raise MpcError(-22, f"{fn}: unit_bytes, capacity and line_size are unsigned")
+    return unit_bytes, capacity, line_size
+
+
+def snapshot_check_values(unit_bytes: int = 32, capacity: int = 1 << 24, line_size: int = 0) -> None:
+    """Raises ``MpcError`` with the message a ``Snapshot`` of these values, or its ``plan`` at ``line_size`` (0: none),
+    would give (``mpc_snapshot_check_values``; no device)."""
+    rc = lib().mpc_snapshot_check_values(*_snapshot_values("mpc_snapshot_check_values", unit_bytes, capacity, line_size))
+    if rc != 0:
+        raise MpcError(rc, (lib().mpc_snapshot_last_error(None) or b"").decode())
+
+
+class Snapshot:
+    """The memory image of a trace as data (``mpc_snapshot``, ``include/mpc_hip_snapshot.h``): per distinct unit
+    address (``unit_bytes`` of 32, 64 or 128) the bytes of the latest unit added there, written out as address-aligned
+    lines of ``line_size`` = 1, 2, 4 or 8 units in ascending address order and evaluated by any evaluator or set.
+    ``partial="skip"`` emits the complete lines only, ``"zero"`` every touched line with its missing units as zeros.
+    Device memory: 2 x (16 + ``unit_bytes``) bytes per unit of ``capacity`` rounded up to a power of two."""
+
+    def __init__(self, unit_bytes: int = 32, capacity: int = 1 << 24, device: int = -1):
+        self._s = C.c_void_p()
+        u, cap, _ = _snapshot_values("mpc_snapshot_create", unit_bytes, capacity, 0)
+        rc = lib().mpc_snapshot_create(u, cap, int(device), C.byref(self._s))
+        if rc != 0:
+            raise MpcError(rc, (lib().mpc_snapshot_last_error(None) or b"").decode())
+        self.unit_bytes, self.capacity = u, cap
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise MpcError(rc, (lib().mpc_snapshot_last_error(self._s if self._s else None) or b"").decode())
+
+    def close(self) -> None:
+        if self._s:
+            lib().mpc_snapshot_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """Empties the snapshot; one that ran into its capacity takes units again."""
+        self._check(lib().mpc_snapshot_reset(self._s))
+
+    def add(self, units, addresses) -> None:
+        """Host buffer [n, unit_bytes] uint8 with one uint64 address per unit; returns when the units are in."""
+        units = _as_lines(units, self.unit_bytes)
+        adr = _as_addresses(addresses, units.shape[0])
+        self._check(lib().mpc_snapshot_add(self._s, units.ctypes.data, units.shape[0], adr.ctypes.data))
+
+    def add_device(self, d_units: int, n: int, d_addresses: int, stream: int = 0) -> None:
+        """Device-resident units and addresses (raw pointers); asynchronous on ``stream``."""
+        self._check(lib().mpc_snapshot_add_device(self._s, d_units or None, int(n), d_addresses or None, stream or None))
+
+    def add_gpgpusim_log(self, path: str) -> int:
+        """Every evaluated record of a GPGPU-Sim ``.log`` at its ``mem_addr``, in file order; returns the units added."""
+        done = C.c_uint64()
+        self._check(lib().mpc_snapshot_add_gpgpusim_log(self._s, path.encode(), C.byref(done)))
+        return int(done.value)
+
+    def stats(self) -> Dict:
+        t = np.zeros(MPC_SNAPSHOT_TABLE_LEN, dtype=np.uint64)
+        self._check(lib().mpc_snapshot_stats(self._s, t.ctypes.data))
+        v = [int(x) for x in t]
+        return {"units": v[0], "distinct_units": v[1], "misaligned": v[2], "capacity": v[3], "unit_bytes": v[4]}
+
+    def plan(self, line_size: int, partial: str = "skip") -> Dict:
+        """What the snapshot holds at ``line_size``: ``touched``, ``complete`` and ``partial`` lines, the
+        ``partial_units`` present in partial lines, the ``missing_units`` and ``n_out``, the lines that are emitted."""
+        p = np.zeros(MPC_SNAPSHOT_TABLE_LEN, dtype=np.uint64)
+        self._check(lib().mpc_snapshot_plan(self._s, int(line_size), _snapshot_partial(partial), p.ctypes.data))
+        v = [int(x) for x in p]
+        return {"touched": v[0], "complete": v[1], "partial": v[2], "partial_units": v[3], "missing_units": v[4], "n_out": v[5]}
+
+    def write_lines(self, line_size: int, partial: str, first: int, n: int, d_lines: int, d_addresses: int = 0, d_presence: int = 0,
+                    stream: int = 0) -> None:
+        """Emitted lines [first, first + n) into caller-owned device memory (raw pointers, like ``compress_device``)."""
+        self._check(lib().mpc_snapshot_write_lines(self._s, int(line_size), _snapshot_partial(partial), int(first), int(n), d_lines or None,
+                                                   d_addresses or None, d_presence or None, stream or None))
+
+    def read_lines(self, line_size: int, partial: str = "skip"):
+        """``(lines uint8[n_out, line_size], addresses uint64[n_out], presence uint8[n_out])`` of all emitted lines."""
+        n = self.plan(line_size, partial)["n_out"]
+        lines = np.zeros((n, int(line_size)), dtype=np.uint8)
+        adr = np.zeros(n, dtype=np.uint64)
+        pres = np.zeros(n, dtype=np.uint8)
+        self._check(lib().mpc_snapshot_read_lines(self._s, int(line_size), _snapshot_partial(partial), 0, n, lines.ctypes.data, adr.ctypes.data,
+                                                  pres.ctypes.data))
+        return lines, adr, pres
+
+    def evaluate(self, evaluator_or_set, line_size: int, partial: str = "skip", by_presence: bool = False) -> int:
+        """Feeds the emitted lines to an evaluator or an ``EvaluatorSet`` of ``line_size``-byte lines: with their addresses
+        when image accounting is on there, with their presence masks as classes when ``by_presence`` is set and class
+        accounting is on; waits.  Returns the number of lines fed."""
+        e = evaluator_or_set
+        if isinstance(e, EvaluatorSet):
+            rc = lib().mpc_snapshot_evaluate_group(self._s, e._g, int(line_size), _snapshot_partial(partial), 1 if by_presence else 0)
+        elif isinstance(e, _Evaluator):
+            rc = lib().mpc_snapshot_evaluate(self._s, e._h, int(line_size), _snapshot_partial(partial), 1 if by_presence else 0)
+        else:
+            raise ValueError("evaluate takes an evaluator or an EvaluatorSet")
+        self._check(rc)
+        return self.plan(line_size, partial)["n_out"]
 
 
 def size_sectors(bins, line_size: int, sector_bytes: int = 32) -> Dict:

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -22,6 +23,7 @@
 #include "mpc_classes.h"
 #include "mpc_pack.h"
 #include "mpc_image.h"
+#include "mpc_snapshot.h"
 #include "mpc_fit.h"
 #include "mpc_launch.h"
 
@@ -2851,6 +2853,68 @@ int mpc_group_class_from_member(mpc_group *g, int member)
   }
   g->cls.from_member = member;
   return MPC_OK;
+}
+
+// ---- snapshots (include/mpc_hip_snapshot.h): the two calls that need a handle's or a group's insides; the snapshot object
+// and its kernels are mpc_snapshot.hip ----
+namespace {
+
+// the emitted lines of (L, partial), piece by piece through the snapshot's scratch buffer into `feed`, on the snapshot's stream
+typedef std::function<int(const void *, u64, const uint64_t *, const uint8_t *, void *)> SnapshotFeed;
+int snapshot_pieces(mpc_snapshot *s, unsigned L, int partial, const SnapshotFeed &feed)
+{
+  uint64_t plan[MPC_SNAPSHOT_TABLE_LEN];
+  if (const int rc = mpc_snapshot_plan(s, L, partial, plan)) return rc;
+  const u64 n_out = plan[5], piece = (u64)mpc_snapshot_piece_lines();
+  for (u64 at = 0; at < n_out; at += piece) {
+    const u64 take = std::min<u64>(n_out - at, piece);
+    const void *d_lines;
+    const uint64_t *d_addrs;
+    const uint8_t *d_presence;
+    void *stream;
+    if (const int rc = mpc_snapshot_piece(s, L, partial, at, take, &d_lines, &d_addrs, &d_presence, &stream)) return rc;
+    if (const int rc = feed(d_lines, take, d_addrs, d_presence, stream)) return rc;
+  }
+  return MPC_OK;
+}
+
+}  // namespace
+
+int mpc_snapshot_evaluate(mpc_snapshot *s, mpc_handle *h, unsigned line_size, int partial, int by_presence)
+{
+  if (!s || !h) return MPC_E_INVAL;
+  if ((unsigned)h->L != line_size)
+    return mpc_snapshot_fail(s, MPC_E_INVAL, ("snapshot: the evaluator's line size " + std::to_string(h->L) + " differs from the snapshot's lines of " +
+                                              std::to_string(line_size) + " bytes").c_str());
+  if (h->device != mpc_snapshot_device_of(s)) return mpc_snapshot_fail(s, MPC_E_INVAL, "snapshot: the evaluator is on another device");
+  const bool classed = by_presence && h->cls.on;
+  int rc = snapshot_pieces(s, line_size, partial, [&](const void *d, u64 n, const uint64_t *da, const uint8_t *dp, void *stream) {
+    const int frc = batch_device(h, d, n, classed ? dp : nullptr, h->img.on ? da : nullptr, nullptr, nullptr, stream);
+    return frc == MPC_OK ? frc : mpc_snapshot_fail(s, frc, h->error.c_str());
+  });
+  if (rc != MPC_OK) return rc;
+  rc = mpc_sync(h);
+  return rc == MPC_OK ? rc : mpc_snapshot_fail(s, rc, h->error.c_str());
+}
+
+int mpc_snapshot_evaluate_group(mpc_snapshot *s, mpc_group *g, unsigned line_size, int partial, int by_presence)
+{
+  if (!s || !g) return MPC_E_INVAL;
+  if ((unsigned)g->stage.L != line_size)
+    return mpc_snapshot_fail(s, MPC_E_INVAL, ("snapshot: the group's line size " + std::to_string(g->stage.L) + " differs from the snapshot's lines of " +
+                                              std::to_string(line_size) + " bytes").c_str());
+  if (g->stage.device != mpc_snapshot_device_of(s)) return mpc_snapshot_fail(s, MPC_E_INVAL, "snapshot: the group is on another device");
+  const bool classed = by_presence && g->cls.on;
+  if (classed && g->cls.from_member >= 0)
+    return mpc_snapshot_fail(s, MPC_E_INVAL, ("class accounting: the classes come from member " + std::to_string(g->cls.from_member) + ", by_presence cannot bring its own").c_str());
+  group_refresh(g);
+  int rc = snapshot_pieces(s, line_size, partial, [&](const void *d, u64 n, const uint64_t *da, const uint8_t *dp, void *stream) {
+    const int frc = group_batch_device(g, d, n, classed ? dp : nullptr, g->img.on ? da : nullptr, nullptr, nullptr, stream);
+    return frc == MPC_OK ? frc : mpc_snapshot_fail(s, frc, g->error.c_str());
+  });
+  if (rc != MPC_OK) return rc;
+  rc = mpc_group_sync(g);
+  return rc == MPC_OK ? rc : mpc_snapshot_fail(s, rc, g->error.c_str());
 }
 
 int mpc_config_describe(const char *json_text, char *out, size_t cap)

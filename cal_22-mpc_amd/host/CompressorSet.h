@@ -65,6 +65,9 @@ public:
                         unsigned long long capacityLines = 1ull << 24);
   // member i's table
   ImageReport GetImageStats(size_t i);
+  // ADDITIVE: the group itself, for what feeds it from the device (Snapshot::Evaluate); the members' buffered lines go
+  // first and every member counts as fed
+  mpc_group *DeviceGroup() { Prepare(); return m_Group; }
 
 private:
   void Prepare();      // members' buffered lines first

@@ -24,6 +24,10 @@
 // OUTDIR/<stem>_results_image.csv (comp::ImageReport: the latest size per line address of a GPGPU-Sim .log trace's
 // mem_addr, and the sectors that address-aligned blocks of N lines of that image occupy).  With a list every member gets
 // its file.  It needs a .log input.  Next to --image, --sector does not imply --size-histogram.  Without --image nothing changes.
+// ADDITIVE: --snapshot L [--snapshot-partial skip|zero] [--snapshot-capacity UNITS] evaluates, instead of the requests of a
+// GPGPU-Sim .log trace, the memory they touched: the latest bytes per request address (comp::Snapshot), written out as
+// address-aligned lines of L bytes in ascending address order.  The usual files are written with the workload named
+// <name>@snapshot<L>, and OUTDIR/<stem>_results_snapshot.csv (comp::SnapshotReport) as well.  Without --snapshot nothing changes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,6 +39,7 @@
 #include "BPC.h"
 #include "CompressorSet.h"
 #include "FPC.h"
+#include "Snapshot.h"
 #include "TraceFile.h"
 #include "VPC.h"
 
@@ -70,6 +75,14 @@ static const char *kHelp =
     "                       --sector's (which then implies nothing).\n"
     "      --image-header arg Bits added to every block of --image. Default=0\n"
     "      --image-capacity arg Distinct lines the image can hold. Default=16777216\n"
+    "      --snapshot arg   Evaluate, instead of the requests of a .log trace, the\n"
+    "                       memory they touched: the latest bytes per address as\n"
+    "                       aligned lines of that many bytes (1, 2, 4 or 8 requests,\n"
+    "                       at most 256); also writes <stem>_results_snapshot.csv\n"
+    "      --snapshot-partial arg Lines with requests missing: skip them or fill\n"
+    "                       the gaps with zero bytes [skip/zero]. Default=skip\n"
+    "      --snapshot-capacity arg Distinct request addresses the snapshot can\n"
+    "                       hold. Default=16777216\n"
     "      --by arg         Also write <stem>_results_classes.csv: lines, bits and\n"
     "                       sectors per class of a line [kernel/rw/mftype/cluster].\n"
     "                       kernel, rw, mftype: a field of a .log trace's records;\n"
@@ -92,6 +105,9 @@ struct Args {
   bool has_image = false, has_image_header = false, has_image_capacity = false;      // ADDITIVE --image N [...]: <stem>_results_image.csv (ImageReport.h)
   unsigned long long image = 0, image_capacity = 1ull << 24;
   unsigned image_header = 0;
+  bool has_snapshot = false, has_snapshot_partial = false, has_snapshot_capacity = false;      // ADDITIVE --snapshot L [...]: Snapshot.h
+  unsigned long long snapshot = 0, snapshot_capacity = 1ull << 24;
+  std::string snapshot_partial = "skip";
 };
 
 // the value of --pack / --pack-header: digits only, up to `most`
@@ -200,6 +216,32 @@ static void requireImage(const Args &a, unsigned traceLineSize)
   }
 }
 
+// --snapshot against the trace: a line is 1, 2, 4 or 8 of the trace's requests and at most 256 bytes
+static void requireSnapshot(const Args &a, unsigned traceLineSize)
+{
+  if (!a.has_snapshot) return;
+  std::string why;
+  if (comp::Snapshot::CheckValues(traceLineSize, a.snapshot_capacity, (unsigned)a.snapshot, why)) return;
+  printf("--snapshot %llu over a trace of %u-byte requests: %s.\n", a.snapshot, traceLineSize, why.c_str());
+  exit(1);
+}
+
+// the snapshot of the trace, evaluated by the evaluator or the set at --snapshot's line size; its own file
+template <class Sink>
+static comp::SnapshotReport compressSnapshot(Sink &sink, const std::string &tracePath, unsigned unitBytes, const Args &a)
+{
+  const bool zeroFill = a.snapshot_partial == "zero";
+  comp::Snapshot snapshot(unitBytes, a.snapshot_capacity);
+  snapshot.AddFile(tracePath);
+  snapshot.Evaluate(sink, (unsigned)a.snapshot, zeroFill);
+  return snapshot.GetReport((unsigned)a.snapshot, zeroFill);
+}
+
+static void writeSnapshot(comp::SnapshotReport report, const std::string &workloadName, const std::string &outputDirPath, const std::string &saveFileName)
+{
+  report.Print(workloadName, outputDirPath + "/" + saveFileName + "_results_snapshot.csv");
+}
+
 static void writeImage(comp::ImageReport report, const std::string &workloadName, const std::string &outputDirPath, const std::string &saveFileName)
 {
   report.Print(workloadName, outputDirPath + "/" + saveFileName + "_results_image.csv");
@@ -225,9 +267,13 @@ static void writeSizes(comp::SizeReport report, const std::string &workloadName,
   report.Print(workloadName, outputDirPath + "/" + saveFileName + "_results_sizes.csv");
 }
 
-static void requireLineSize(unsigned traceLineSize, unsigned evaluatorLineSize)
+static void requireLineSize(unsigned traceLineSize, unsigned evaluatorLineSize, bool snapshot = false)
 {
   if (evaluatorLineSize == traceLineSize) return;
+  if (snapshot) {
+    printf("--snapshot %u writes %u-byte lines but the evaluator is configured for %u-byte lines.\n", traceLineSize, traceLineSize, evaluatorLineSize);
+    exit(1);
+  }
   printf("The trace has %u-byte lines but the evaluator is configured for %u-byte lines.\n", traceLineSize, evaluatorLineSize);
   exit(1);
 }
@@ -378,6 +424,45 @@ int main(int argc, char **argv)
       a.has_image_capacity = true;
       continue;
     }
+    if (arg == "--snapshot" || arg.compare(0, 11, "--snapshot=") == 0) {
+      if (arg == "--snapshot" && i + 1 >= argc) {
+        std::cout << "Option 'snapshot' is missing an argument" << std::endl;
+        exit(1);
+      }
+      const std::string value = arg == "--snapshot" ? argv[++i] : arg.substr(11);
+      if (!takeNumber(value, 256, a.snapshot) || a.snapshot == 0) {
+        std::cout << "--snapshot takes a line size in bytes, 1, 2, 4 or 8 of the trace's requests and at most 256, not \"" << value << "\"." << std::endl;
+        return 1;
+      }
+      a.has_snapshot = true;
+      continue;
+    }
+    if (arg == "--snapshot-partial" || arg.compare(0, 19, "--snapshot-partial=") == 0) {
+      if (arg == "--snapshot-partial" && i + 1 >= argc) {
+        std::cout << "Option 'snapshot-partial' is missing an argument" << std::endl;
+        exit(1);
+      }
+      a.snapshot_partial = arg == "--snapshot-partial" ? argv[++i] : arg.substr(19);
+      if (a.snapshot_partial != "skip" && a.snapshot_partial != "zero") {
+        std::cout << "--snapshot-partial takes skip or zero, not \"" << a.snapshot_partial << "\"." << std::endl;
+        return 1;
+      }
+      a.has_snapshot_partial = true;
+      continue;
+    }
+    if (arg == "--snapshot-capacity" || arg.compare(0, 20, "--snapshot-capacity=") == 0) {
+      if (arg == "--snapshot-capacity" && i + 1 >= argc) {
+        std::cout << "Option 'snapshot-capacity' is missing an argument" << std::endl;
+        exit(1);
+      }
+      const std::string value = arg == "--snapshot-capacity" ? argv[++i] : arg.substr(20);
+      if (!takeNumber(value, 1ull << 28, a.snapshot_capacity) || a.snapshot_capacity == 0) {
+        std::cout << "--snapshot-capacity takes a number of requests from 1 to 268435456, not \"" << value << "\"." << std::endl;
+        return 1;
+      }
+      a.has_snapshot_capacity = true;
+      continue;
+    }
     if (arg == "--by" || arg.compare(0, 5, "--by=") == 0) {
       if (arg == "--by" && i + 1 >= argc) {
         std::cout << "Option 'by' is missing an argument" << std::endl;
@@ -467,16 +552,36 @@ int main(int argc, char **argv)
     std::cout << "--image is evaluated in batches: it does not go with --per-line / --line-buffer." << std::endl;
     return 1;
   }
+  // --snapshot: checked before anything is opened or written, one message each
+  if ((a.has_snapshot_partial || a.has_snapshot_capacity) && !a.has_snapshot) {
+    std::cout << "--snapshot-partial and --snapshot-capacity belong to --snapshot: give --snapshot L too." << std::endl;
+    return 1;
+  }
+  if (a.has_snapshot && !trace::IsGpgpuSimLog(a.input)) {
+    std::cout << "--snapshot takes the addresses from the records of a GPGPU-Sim .log trace: \"" << a.input << "\" is not one." << std::endl;
+    return 1;
+  }
+  if (a.has_snapshot && a.has_by && a.by != "cluster") {
+    std::cout << "--by " << a.by << " does not go with --snapshot: a line assembled from several records has no single record to take the class from." << std::endl;
+    return 1;
+  }
+  if (a.has_snapshot && a.per_line) {
+    std::cout << "--snapshot is evaluated in batches: it does not go with --per-line / --line-buffer." << std::endl;
+    return 1;
+  }
   const std::string tracePath = a.input, configPath = a.config, outputDirPath = a.has_output ? a.output : "";
   if (!list.empty()) return runList(list, tracePath, configPath, outputDirPath, a);
 
   trace::MemReq_t *memReq = nullptr;
   trace::Loader *loader = openTrace(tracePath, &memReq);
-  requireSector(a, loader->GetCachelineSize());
-  requirePack(a, loader->GetCachelineSize());
-  requireImage(a, loader->GetCachelineSize());
+  requireSnapshot(a, loader->GetCachelineSize());
+  // the lines that are evaluated: the trace's requests, or with --snapshot the lines assembled from them
+  const unsigned lineSize = a.has_snapshot ? (unsigned)a.snapshot : loader->GetCachelineSize();
+  requireSector(a, lineSize);
+  requirePack(a, lineSize);
+  requireImage(a, lineSize);
 
-  comp::DeviceCompressor *compressor = makeEvaluator(algorithm, configPath, loader->GetCachelineSize());
+  comp::DeviceCompressor *compressor = makeEvaluator(algorithm, configPath, lineSize);
   if (!compressor) {
     if (refusedAsNotBuilt(algorithm)) return 1;
     std::cerr << "Invalid name of algorithm." << std::endl;
@@ -487,7 +592,7 @@ int main(int argc, char **argv)
   // The reference's per-line loop (main.cpp:208-248) as a batch loop, unless --per-line / --line-buffer ask for that
   // loop itself or the loader hands out single lines only.
   if (a.line_buffer) compressor->SetLineBuffering(a.line_buffer);
-  requireLineSize(loader->GetCachelineSize(), compressor->GetLineSize());
+  requireLineSize(lineSize, compressor->GetLineSize(), a.has_snapshot);
   if (a.size_histogram) compressor->EnableSizeHistogram();
   if (a.has_by) {
     compressor->EnableClassStats(a.sector);
@@ -495,7 +600,10 @@ int main(int argc, char **argv)
   }
   if (a.has_pack) compressor->EnablePackStats(a.pack, a.sector, a.pack_header);
   if (a.has_image) compressor->EnableImageStats(a.image, a.sector, a.image_header, a.image_capacity);
-  if (!a.per_line && (loader->SupportsBatch() || !loader->GetStreamablePath().empty()))
+  comp::SnapshotReport snapshotReport(lineSize, false);
+  if (a.has_snapshot)
+    snapshotReport = compressSnapshot(*compressor, tracePath, loader->GetCachelineSize(), a);
+  else if (!a.per_line && (loader->SupportsBatch() || !loader->GetStreamablePath().empty()))
     compressBatches(compressor, loader);
   else
     trace::CompressPerLine(compressor, loader, memReq);
@@ -503,12 +611,14 @@ int main(int argc, char **argv)
 
   std::string workloadName;
   if (!workloadNameOf(tracePath, workloadName)) return 1;
+  if (a.has_snapshot) workloadName += "@snapshot" + std::to_string(a.snapshot);
   std::cout << "comp.ratio: " << mpctext::num(compStat->CompRatio) << std::endl;
   writeResults(compStat, workloadName, outputDirPath, saveFileName);
   if (a.size_histogram) writeSizes(compressor->GetSizeHistogram(a.sector), workloadName, outputDirPath, saveFileName);
   if (a.has_by) writeClasses(compressor->GetClassStats(), workloadName, outputDirPath, saveFileName);
   if (a.has_pack) writePack(compressor->GetPackStats(), workloadName, outputDirPath, saveFileName);
   if (a.has_image) writeImage(compressor->GetImageStats(), workloadName, outputDirPath, saveFileName);
+  if (a.has_snapshot) writeSnapshot(snapshotReport, workloadName, outputDirPath, saveFileName);
 
   delete memReq;      // (the reference leaks its request object)
   delete loader;
@@ -524,10 +634,12 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
 {
   std::string workloadName;
   if (!workloadNameOf(tracePath, workloadName)) return 1;
+  if (a.has_snapshot) workloadName += "@snapshot" + std::to_string(a.snapshot);
 
   trace::MemReq_t *memReq = nullptr;
   trace::Loader *loader = openTrace(tracePath, &memReq);
-  const unsigned lineSize = loader->GetCachelineSize();
+  requireSnapshot(a, loader->GetCachelineSize());
+  const unsigned lineSize = a.has_snapshot ? (unsigned)a.snapshot : loader->GetCachelineSize();
   requireSector(a, lineSize);
   requirePack(a, lineSize);
   requireImage(a, lineSize);
@@ -536,7 +648,7 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
   for (const std::string &n : names) {
     evaluators.push_back(makeEvaluator(n, configPath, lineSize));      // (main() has checked the names)
     members.push_back(evaluators.back());
-    requireLineSize(lineSize, members.back()->GetLineSize());
+    requireLineSize(lineSize, members.back()->GetLineSize(), a.has_snapshot);
     if (a.size_histogram) evaluators.back()->EnableSizeHistogram();
   }
   {
@@ -554,7 +666,11 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
     }
     if (a.has_pack) set.EnablePackStats(a.pack, a.sector, a.pack_header);      // (behind EnableBest: the best of the list gets its table)
     if (a.has_image) set.EnableImageStats(a.image, a.sector, a.image_header, a.image_capacity);
-    compressBatches(&set, loader);
+    comp::SnapshotReport snapshotReport(lineSize, false);
+    if (a.has_snapshot)
+      snapshotReport = compressSnapshot(set, tracePath, loader->GetCachelineSize(), a);
+    else
+      compressBatches(&set, loader);
     for (size_t i = 0; i < names.size(); i++) {
       comp::CompResult *compStat = set.GetResult(i);
       const std::string saveFileName = (names[i] == "VPC") ? parseConfig(configPath) : names[i];
@@ -564,6 +680,7 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
       if (a.has_by) writeClasses(set.GetClassStats(i), workloadName, outputDirPath, saveFileName);
       if (a.has_pack) writePack(set.GetPackStats(i), workloadName, outputDirPath, saveFileName);
       if (a.has_image) writeImage(set.GetImageStats(i), workloadName, outputDirPath, saveFileName);
+      if (a.has_snapshot) writeSnapshot(snapshotReport, workloadName, outputDirPath, saveFileName);
     }
     if (a.size_histogram) {
       const comp::BestReport best = set.GetBest(a.sector);

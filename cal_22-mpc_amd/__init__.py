@@ -33,6 +33,9 @@ MPC_PACK_BEST = -1            # mpc_group_pack_stats_get: the table of the per-l
 MPC_IMAGE_MAX_SECTORS = 1024  # an image table is uint64[16 + 1024] (include/mpc_hip_image.h)
 MPC_IMAGE_TABLE_LEN = 16 + MPC_IMAGE_MAX_SECTORS
 MPC_IMAGE_MAX_CAPACITY = 1 << 28
+MPC_REWRITE_MAX_CLASSES = 32  # a rewrite table is uint64[144 + 32 * 32] (include/mpc_hip_rewrite.h)
+MPC_REWRITE_TABLE_LEN = 144 + MPC_REWRITE_MAX_CLASSES * MPC_REWRITE_MAX_CLASSES
+MPC_REWRITE_MAX_CAPACITY = 1 << 28
 MPC_SNAPSHOT_MAX_CAPACITY = 1 << 28   # include/mpc_hip_snapshot.h
 MPC_SNAPSHOT_TABLE_LEN = 8            # a snapshot's stats and plan vectors
 SNAPSHOT_PARTIAL = {"skip": 0, "zero": 1}      # MPC_SNAPSHOT_PARTIAL_*
@@ -180,6 +183,11 @@ def lib() -> C.CDLL:
             "mpc_group_image_stats_get": ([H, C.c_int, C.c_void_p, C.c_size_t], C.c_int),
             "mpc_group_compress_batch_addressed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
             "mpc_group_compress_batch_device_addressed": ([H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "mpc_rewrite_stats_enable": ([H, C.c_uint64, C.c_uint], C.c_int),
+            "mpc_rewrite_check_values": ([C.c_uint, C.c_uint64, C.c_uint], C.c_int),
+            "mpc_rewrite_stats_get": ([H, C.c_void_p, C.c_size_t], C.c_int),
+            "mpc_group_rewrite_stats_enable": ([H, C.c_uint64, C.c_uint], C.c_int),
+            "mpc_group_rewrite_stats_get": ([H, C.c_int, C.c_void_p, C.c_size_t], C.c_int),
             "mpc_snapshot_check_values": ([C.c_uint, C.c_uint64, C.c_uint], C.c_int),
             "mpc_snapshot_create": ([C.c_uint, C.c_uint64, C.c_int, C.POINTER(H)], C.c_int),
             "mpc_snapshot_destroy": ([H], None),
@@ -234,6 +242,9 @@ EXPORTED_PACK_SYMBOLS = ["mpc_pack_stats_enable", "mpc_pack_check_values", "mpc_
 EXPORTED_IMAGE_SYMBOLS = ["mpc_image_stats_enable", "mpc_image_check_values", "mpc_image_stats_get", "mpc_compress_batch_addressed",
                           "mpc_compress_batch_device_addressed", "mpc_image_hash", "mpc_group_image_stats_enable", "mpc_group_image_stats_get",
                           "mpc_group_compress_batch_addressed", "mpc_group_compress_batch_device_addressed"]
+# The rewrite accounting entry points, declared in include/mpc_hip_rewrite.h (which mpc_hip.h includes).
+EXPORTED_REWRITE_SYMBOLS = ["mpc_rewrite_stats_enable", "mpc_rewrite_check_values", "mpc_rewrite_stats_get", "mpc_group_rewrite_stats_enable",
+                            "mpc_group_rewrite_stats_get"]
 # The snapshot entry points, declared in include/mpc_hip_snapshot.h (which mpc_hip.h includes).
 EXPORTED_SNAPSHOT_SYMBOLS = ["mpc_snapshot_check_values", "mpc_snapshot_create", "mpc_snapshot_destroy", "mpc_snapshot_reset", "mpc_snapshot_last_error",
                              "mpc_snapshot_add", "mpc_snapshot_add_device", "mpc_snapshot_add_gpgpusim_log", "mpc_snapshot_stats", "mpc_snapshot_plan",
@@ -397,6 +408,47 @@ def image_table_view(table: np.ndarray, line_size: int) -> Dict:
             "traffic_ratio": v[0] * 8 * L / v[1] if v[1] else 0.0,
             "image_ratio": v[2] * 8 * L / v[3] if v[3] else 0.0,
             "image_sector_ratio": v[6] / v[5] if v[5] else 0.0}
+
+
+def _rewrite_values(fn: str, capacity, granule_bytes):
+    """The two values of ``enable_rewrite_stats`` as the C ABI takes them (unsigned), capacity first."""
+    capacity, granule_bytes = int(capacity), int(granule_bytes)
+    if not 0 <= capacity < 1 << 64:
+        raise MpcError(-22, f"{fn}: capacity is unsigned")
+    if not 0 <= granule_bytes < 1 << 32:
+        raise MpcError(-22, f"{fn}: granule_bytes is an unsigned 32-bit value")
+    return capacity, granule_bytes
+
+
+def rewrite_check_values(line_size: int, granule_bytes: int = 32, capacity: int = 1 << 24) -> None:
+    """Raises ``MpcError`` with the message ``enable_rewrite_stats`` would give for these values
+    (``mpc_rewrite_check_values``; no device)."""
+    rc = lib().mpc_rewrite_check_values(int(line_size), *_rewrite_values("mpc_rewrite_check_values", capacity, granule_bytes))
+    if rc != 0:
+        raise MpcError(rc, (lib().mpc_last_error(None) or b"").decode())
+
+
+def rewrite_table_view(table: np.ndarray, line_size: int) -> Dict:
+    """A rewrite table ``uint64[MPC_REWRITE_TABLE_LEN]`` as a dict of its named sums, the four histograms ``first``,
+    ``latest_classes``, ``peak_classes`` (entry c - 1: class c) and ``count_log2`` (entry b: keys with floor(log2(count))
+    == b), ``trans`` as a ``[G + 1, G]`` array whose row 0 is the first touches and whose row c_old, column c_new - 1 is a
+    transition, and the ratios ``overflow_rate`` = grows / rewrites, ``image_granule_ratio`` = D G / latest_granules,
+    ``peak_granule_ratio`` = D G / peak_granules and ``traffic_ratio`` = lines x 8 L / bits (each 0.0 where its divisor is 0)."""
+    t = np.asarray(table, dtype=np.uint64).reshape(MPC_REWRITE_TABLE_LEN)
+    v = [int(x) for x in t[:16]]
+    L, G, M = int(line_size), int(t[14]), MPC_REWRITE_MAX_CLASSES
+    trans = np.zeros((G + 1, G), dtype=np.uint64)
+    trans[0] = t[16:16 + G]
+    trans[1:] = t[144:144 + M * M].reshape(M, M)[:G, :G]
+    return {"lines": v[0], "bits": v[1], "distinct_lines": v[2], "misaligned": v[3], "rewrites": v[4], "grows": v[5], "shrinks": v[6],
+            "equal_bits": v[7], "latest_granules": v[8], "peak_granules": v[9], "latest_bits": v[10], "peak_bits": v[11],
+            "granule_bytes": v[12], "capacity": v[13], "classes": G,
+            "first": t[16:16 + G].copy(), "latest_classes": t[48:48 + G].copy(), "peak_classes": t[80:80 + G].copy(),
+            "count_log2": t[112:144].copy(), "trans": trans,
+            "overflow_rate": v[5] / v[4] if v[4] else 0.0,
+            "image_granule_ratio": v[2] * G / v[8] if v[8] else 0.0,
+            "peak_granule_ratio": v[2] * G / v[9] if v[9] else 0.0,
+            "traffic_ratio": v[0] * 8 * L / v[1] if v[1] else 0.0}
 
 
 def _ratio(original, compressed, lines) -> float:
@@ -645,6 +697,23 @@ class _Evaluator:
     def image_stats(self) -> Dict:
         """``image_table_view`` of the image since accounting was switched on or the last ``reset()``."""
         return image_table_view(self.image_table(), self.line_size)
+
+    # -- rewrite accounting -----------------------------------------------------
+    def enable_rewrite_stats(self, granule_bytes: int = 32, capacity: int = 1 << 24) -> None:
+        """Follow, from now on, the sequence of sizes per line address (``addresses=``, or a ``.log``'s ``mem_addr``),
+        for up to ``capacity`` distinct lines (32 bytes of device memory each, and the scratch of a sub-batch), in
+        size classes of ``granule_bytes`` bytes (``mpc_rewrite_stats_enable``); idempotent for the same values."""
+        self._check(lib().mpc_rewrite_stats_enable(self._h, *_rewrite_values("mpc_rewrite_stats_enable", capacity, granule_bytes)))
+
+    def rewrite_table(self) -> np.ndarray:
+        """The raw table ``uint64[MPC_REWRITE_TABLE_LEN]`` (``mpc_rewrite_stats_get``); not destructive."""
+        t = np.zeros(MPC_REWRITE_TABLE_LEN, dtype=np.uint64)
+        self._check(lib().mpc_rewrite_stats_get(self._h, t.ctypes.data, t.size))
+        return t
+
+    def rewrite_stats(self) -> Dict:
+        """``rewrite_table_view`` of the lines since accounting was switched on or the last ``reset()``."""
+        return rewrite_table_view(self.rewrite_table(), self.line_size)
 
 
 class VPC(_Evaluator):
@@ -1078,6 +1147,21 @@ class EvaluatorSet:
     def image_stats(self) -> Dict:
         """``{0: ..., 1: ...}``: one entry per member, in member order, each as ``_Evaluator.image_stats()`` returns it."""
         return {i: image_table_view(self.image_table(i), self.line_size) for i in range(len(self.members))}
+
+    # -- rewrite accounting --------------------------------------------------------
+    def enable_rewrite_stats(self, granule_bytes: int = 32, capacity: int = 1 << 24) -> None:
+        """``enable_rewrite_stats`` for every member with the same values; a member's map is its own."""
+        self._check(lib().mpc_group_rewrite_stats_enable(self._g, *_rewrite_values("mpc_group_rewrite_stats_enable", capacity, granule_bytes)))
+
+    def rewrite_table(self, member: int) -> np.ndarray:
+        """The raw table of member ``member``."""
+        t = np.zeros(MPC_REWRITE_TABLE_LEN, dtype=np.uint64)
+        self._check(lib().mpc_group_rewrite_stats_get(self._g, int(member), t.ctypes.data, t.size))
+        return t
+
+    def rewrite_stats(self) -> Dict:
+        """``{0: ..., 1: ...}``: one entry per member, in member order, each as ``_Evaluator.rewrite_stats()`` returns it."""
+        return {i: rewrite_table_view(self.rewrite_table(i), self.line_size) for i in range(len(self.members))}
 
     def class_log_field(self, field) -> None:
         """``_Evaluator.class_log_field`` for ``compress_gpgpusim_log`` of the set."""

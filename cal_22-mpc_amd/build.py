@@ -57,6 +57,7 @@ def lib_units(csrc: str = CSRC):
               (os.path.join(csrc, "mpc_classes.hip"), "classes.o", []),          # per-class tables of the sizes
               (os.path.join(csrc, "mpc_pack.hip"), "pack.o", []),                # sectors of blocks of N packed lines
               (os.path.join(csrc, "mpc_image.hip"), "image.o", []),              # the latest size per line address, closed into blocks
+              (os.path.join(csrc, "mpc_rewrite.hip"), "rewrite.o", []),          # the sequence of sizes per line address: transitions, latest, peak
               (os.path.join(csrc, "mpc_snapshot.hip"), "snapshot.o", []),        # the latest bytes per unit address, written out as lines
               (os.path.join(csrc, "mpc_capi.hip"), "capi.o", [])]
     return units
@@ -67,7 +68,7 @@ def build_lib(force: bool = False, verbose: bool = False, test: bool = False) ->
     are compiled in parallel: the lane kernel file once per line size (-DMPC_LANE_W=8/16/32) plus its dispatcher
     (-DMPC_LANE_W=0), every other source once; then linked."""
     LIB = TEST_LIB if test else globals()["LIB"]
-    deps = _sources(CSRC) + [os.path.join(ROOT, "include", f) for f in ("mpc_hip.h", "mpc_hip_sizes.h", "mpc_hip_classes.h", "mpc_hip_pack.h", "mpc_hip_image.h", "mpc_hip_snapshot.h")]
+    deps = _sources(CSRC) + [os.path.join(ROOT, "include", f) for f in ("mpc_hip.h", "mpc_hip_sizes.h", "mpc_hip_classes.h", "mpc_hip_pack.h", "mpc_hip_image.h", "mpc_hip_rewrite.h", "mpc_hip_snapshot.h")]
     if not force and _newer(LIB, deps):
         return LIB
     objdir = os.path.join(HERE, "obj_test" if test else "obj")

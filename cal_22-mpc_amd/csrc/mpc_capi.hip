@@ -23,6 +23,7 @@
 #include "mpc_classes.h"
 #include "mpc_pack.h"
 #include "mpc_image.h"
+#include "mpc_rewrite.h"
 #include "mpc_snapshot.h"
 #include "mpc_fit.h"
 #include "mpc_launch.h"
@@ -190,6 +191,26 @@ struct mpc_handle {
     u64 ctl[MPC_IMAGE_CTL_LEN] = {};   // what image_status last read of it
     bool over = false;                 // a key beyond the capacity arrived: the handle takes no more lines
   } img;
+  // rewrite accounting (mpc_rewrite.h): nothing of it exists before mpc_rewrite_stats_enable.  Its passes depend on
+  // order: every pass waits, on its own stream, for the event the pass before it recorded -- whichever stream that was
+  // (the stager's two slot streams run one handle's chunks side by side).
+  struct {
+    bool on = false;
+    u64 capacity = 0;
+    unsigned granule = 0, G = 0;
+    u64 seen = 0;                      // lines evaluated since accounting was switched on or last reset: the next line's position
+    u64 slots = 0;                     // the smallest power of two >= 2 x capacity
+    u64 hash_mask = ~0ull;             // (the test library: MPC_TEST_REWRITE_HASH_BITS)
+    u64 batch = MPC_REWRITE_BATCH;     // lines of a sub-batch (the test library: MPC_TEST_REWRITE_BATCH)
+    u64 *d_keys = nullptr, *d_vals = nullptr;   // [slots]
+    u64 *d_dev = nullptr;              // [MPC_REWRITE_DEV_LEN]
+    void *d_scratch = nullptr;         // the arrays of a sub-batch
+    MpcRewriteScratch scratch{};
+    hipEvent_t done = nullptr;
+    bool recorded = false;
+    u64 ctl[MPC_REWRITE_CTL_LEN] = {}; // what rewrite_status last read of the counters
+    bool over = false;                 // a key beyond the capacity arrived: the handle takes no more lines
+  } rw;
   std::string error;
 };
 
@@ -234,6 +255,12 @@ struct mpc_group {
     u64 capacity = 0, N = 0;
     unsigned sector_bytes = 0, header_bits = 0;
   } img;
+  // rewrite accounting of the group (mpc_rewrite.h): the members' maps are their handles'
+  struct {
+    bool on = false;
+    u64 capacity = 0;
+    unsigned granule = 0;
+  } rw;
   hipEvent_t scratch_done = nullptr;
   bool recorded = false;
   std::string form, error;
@@ -646,11 +673,26 @@ int image_status(mpc_handle *h)
                      : MPC_OK;
 }
 
-// Pattern, at a point where the handle's work is complete: has a line beyond the capacity arrived?  (Image accounting's
-// capacity is checked at the same points, for every kind of handle.)
+// rewrite accounting, at a point where the handle's work is complete: has a key beyond the capacity arrived?
+int rewrite_status(mpc_handle *h)
+{
+  if (!h->rw.on) return MPC_OK;
+  if (!h->rw.over) {
+    u64 *ctl = h->rw.ctl;
+    HIPCHK(h, hipMemcpy(ctl, h->rw.d_dev, sizeof(h->rw.ctl), hipMemcpyDeviceToHost));
+    h->rw.over = ctl[MPC_REWRITE_CTL_KEYS] > h->rw.capacity || ctl[MPC_REWRITE_CTL_OVERFLOW] != 0;
+  }
+  return h->rw.over ? set_err(h, MPC_E_INVAL, "rewrite accounting: more than " + std::to_string(h->rw.capacity) +
+                                                  " distinct line addresses (capacity_lines of mpc_rewrite_stats_enable): the map is incomplete, the handle takes no more lines")
+                    : MPC_OK;
+}
+
+// Pattern, at a point where the handle's work is complete: has a line beyond the capacity arrived?  (Image and rewrite
+// accounting's capacities are checked at the same points, for every kind of handle.)
 int pattern_status(mpc_handle *h)
 {
   if (const int rc = image_status(h)) return rc;
+  if (const int rc = rewrite_status(h)) return rc;
   if (h->algorithm != Algo::Pattern) return MPC_OK;
   if (h->pat.evicting) {       // nothing to run into: the flag says that a probe went round a whole table, which its sizing excludes
     u64 flag = 0;
@@ -882,7 +924,7 @@ bool accounts(const mpc_handle *h) { return h->acct.on && h->algorithm != Algo::
 bool in_best(const mpc_group *g, int i) { return g->best.on && std::find(g->best.set.begin(), g->best.set.end(), i) != g->best.set.end(); }
 
 // a handle whose sizes are wanted on the device, asked for by the caller or not
-bool needs_sizes(const mpc_handle *h) { return accounts(h) || h->cls.on || h->pack.on || h->img.on; }
+bool needs_sizes(const mpc_handle *h) { return accounts(h) || h->cls.on || h->pack.on || h->img.on || h->rw.on; }
 
 // ... a member whose sizes a group needs on the device, asked for by the caller or not
 bool group_accounts(const mpc_group *g, int i) { return needs_sizes(g->m[(size_t)i]) || in_best(g, i); }
@@ -895,7 +937,7 @@ void group_refresh(mpc_group *g)
     g->stage.need_sel[(size_t)i] = g->cls.from_member == i ? 1 : 0;
   }
   g->stage.log_field = (g->cls.on && g->cls.from_member < 0) ? g->cls.log_field : MPC_CLASS_LOG_NONE;
-  g->stage.log_addrs = g->img.on;
+  g->stage.log_addrs = g->img.on || g->rw.on;
 }
 
 hipError_t sizes_pass(const mpc_handle *h, const MpcSizesArgs &A, u64 n, hipStream_t s)
@@ -975,6 +1017,22 @@ u64 image_slots(u64 capacity)
   while (slots < 2 * capacity) slots <<= 1;
   return slots;
 }
+
+// ---- rewrite accounting (mpc_rewrite.h): its values ----
+// the refusals of mpc_rewrite_stats_enable that need no device
+std::string rewrite_refusal_of(unsigned L, u64 capacity, unsigned granule)
+{
+  if (capacity == 0) return "rewrite accounting: capacity_lines must be at least 1";
+  if (capacity > MPC_REWRITE_MAX_CAPACITY) return "rewrite accounting: capacity_lines above " + std::to_string(MPC_REWRITE_MAX_CAPACITY) + " (2^28; the map takes 32 bytes per line of capacity)";
+  if (granule == 0) return "rewrite accounting: granule_bytes must be at least 1";
+  if (granule > L) return "rewrite accounting: granule_bytes " + std::to_string(granule) + " above the line size " + std::to_string(L);
+  if ((L + granule - 1) / granule > MPC_REWRITE_MAX_CLASSES)
+    return "rewrite accounting: granule_bytes " + std::to_string(granule) + " gives " + std::to_string((L + granule - 1) / granule) + " size classes for lines of " +
+           std::to_string(L) + " bytes, more than " + std::to_string(MPC_REWRITE_MAX_CLASSES);
+  return "";
+}
+
+std::string rewrite_values(u64 cap, unsigned granule) { return "capacity_lines " + std::to_string(cap) + ", granule_bytes " + std::to_string(granule); }
 // device table (mpc_pack.h) -> the ABI's table; open_lines / open_bits: the open block
 void pack_table_out(const std::vector<u64> &dev, u64 N, unsigned L, unsigned sb, unsigned hb, u64 open_lines, u64 open_bits, uint64_t *table)
 {
@@ -1054,12 +1112,61 @@ int pack_pass(const Sink &k, const mpc_handle *grid_of, mpc_handle *const *hs, c
 // its capacity was exceeded; a handle without it takes no addresses
 int image_refusal(mpc_handle *h, u64 n, const uint64_t *d_addrs)
 {
-  if (!h->img.on)
+  if (!h->img.on && !h->rw.on)
     return d_addrs ? set_err(h, MPC_E_INVAL, "image accounting is not switched on for this handle (mpc_image_stats_enable): the call must not bring addresses") : MPC_OK;
-  if (h->img.over) return image_status(h);
+  if (h->img.on && h->img.over) return image_status(h);
+  if (h->rw.on && h->rw.over) return rewrite_status(h);
   if (n && !d_addrs)
-    return set_err(h, MPC_E_INVAL, "image accounting is on: every line needs an address (mpc_compress_batch_addressed, mpc_compress_batch_device_addressed or a "
-                                   "GPGPU-Sim .log); this call brings none, and a hole in the image is not counted silently");
+    return h->img.on ? set_err(h, MPC_E_INVAL, "image accounting is on: every line needs an address (mpc_compress_batch_addressed, mpc_compress_batch_device_addressed or a "
+                                               "GPGPU-Sim .log); this call brings none, and a hole in the image is not counted silently")
+                     : set_err(h, MPC_E_INVAL, "rewrite accounting is on: every line needs an address (mpc_compress_batch_addressed, mpc_compress_batch_device_addressed or a "
+                                               "GPGPU-Sim .log); this call brings none, and a hole in the sequences is not counted silently");
+  return MPC_OK;
+}
+
+// ---- rewrite accounting (mpc_rewrite.h) ----
+MpcRewriteMap rewrite_map(const mpc_handle *h)
+{
+  const auto &R = h->rw;
+  MpcRewriteMap M{};
+  M.keys = R.d_keys;
+  M.vals = R.d_vals;
+  M.dev = R.d_dev;
+  M.slot_mask = R.slots - 1;
+  M.hash_mask = R.hash_mask;
+  M.capacity = R.capacity;
+  M.granule_bits = 8u * R.granule;
+  M.classes = R.G;
+  return M;
+}
+
+// The passes behind the evaluators' launches of a chunk for the `m` handles that account (all at one line; a handle alone:
+// m == 1).  The chunk's keys are sorted once, in the first handle's scratch, and applied to each handle's map with its own
+// sizes.  Every pass of a handle is chained to the one before it: stream s waits for the event recorded behind it, and
+// the event is recorded again behind this one.
+int rewrite_pass(const Sink &k, mpc_handle *const *hs, const uint16_t *const *d_sizes, int m, const uint64_t *d_addrs, u64 n, hipStream_t s)
+{
+  mpc_handle *h0 = hs[0];
+  const MpcRewriteScratch &S = h0->rw.scratch;
+  for (int i = 0; i < m; i++)
+    if (hs[i]->rw.recorded) HIPCHK(k, hipStreamWaitEvent(s, hs[i]->rw.done, 0));
+  for (u64 at = 0; at < n; at += h0->rw.batch) {
+    const u64 take = std::min<u64>(n - at, h0->rw.batch);
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < m && e == hipSuccess; i++)
+      e = mpc_launch_rewrite_keys(&S, d_addrs + at, d_sizes[i] + at, take, (unsigned)h0->L, hs[i]->rw.d_dev, i == 0, grid_for(h0, take, 256, 8), s);
+    if (e == hipSuccess) e = mpc_launch_rewrite_sort(&S, take, s);
+    for (int i = 0; i < m && e == hipSuccess; i++) {
+      const MpcRewriteMap M = rewrite_map(hs[i]);
+      e = mpc_launch_rewrite_apply(&S, &M, d_sizes[i] + at, take, s);
+    }
+    if (e != hipSuccess) return k.fail(k.ctx, MPC_E_HIP, std::string("kernel launch (rewrite accounting): ") + hipGetErrorString(e));
+  }
+  for (int i = 0; i < m; i++) {
+    HIPCHK(k, hipEventRecord(hs[i]->rw.done, s));
+    hs[i]->rw.recorded = true;
+    hs[i]->rw.seen += n;
+  }
   return MPC_OK;
 }
 
@@ -1111,8 +1218,11 @@ int launch_accounted(mpc_handle *h, const void *d_lines, u64 n, uint16_t *d_size
     const uint16_t *arr[1] = {d_sizes};
     rc = pack_pass(sink_of(h), h, one, arr, 1, nullptr, n, s);
   }
-  if (rc != MPC_OK || !h->img.on) return rc;
-  return image_pass(sink_of(h), h, d_sizes, d_addrs, n, s);
+  if (rc == MPC_OK && h->img.on) rc = image_pass(sink_of(h), h, d_sizes, d_addrs, n, s);
+  if (rc != MPC_OK || !h->rw.on) return rc;
+  mpc_handle *one[1] = {h};
+  const uint16_t *arr[1] = {d_sizes};
+  return rewrite_pass(sink_of(h), one, arr, 1, d_addrs, n, s);
 }
 
 // The members' sizes of one chunk (one pointer per member, non-null for every member that group_accounts): first the
@@ -1284,13 +1394,30 @@ int group_image_check(mpc_group *g)
   return MPC_OK;
 }
 
+// Before a group call feeds its members: with the group's rewrite accounting on they stand at one common line.
+int group_rewrite_check(mpc_group *g)
+{
+  if (!g->rw.on) return MPC_OK;
+  const u64 at = g->m[0]->rw.seen;
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const auto &R = g->m[i]->rw;
+    if (!R.on || R.capacity != g->rw.capacity || R.granule != g->rw.granule)
+      return group_err(g, MPC_E_INVAL, "rewrite accounting: member " + std::to_string(i) + " does not count with the group's values");
+    if (R.seen != at)
+      return group_err(g, MPC_E_INVAL, "rewrite accounting: member " + std::to_string(i) + " (" + algorithm_name(g->m[i]->algorithm) + ") is at line " +
+                                           std::to_string(R.seen) + ", member 0 at line " + std::to_string(at) +
+                                           ": a member was fed outside the group, its positions no longer line up with the others' (reset the members to start over)");
+  }
+  return MPC_OK;
+}
+
 int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *const *d_sizes, int8_t *const *d_sel, const uint8_t *d_classes,
                            const uint64_t *d_addrs, hipStream_t s)
 {
   bool images = false;
   for (size_t i = 0; i < g->m.size(); i++) {
     mpc_handle *h = g->m[i];
-    if (!h->img.on) continue;         // (a member without the accounting ignores the group's addresses)
+    if (!h->img.on && !h->rw.on) continue;   // (a member without the accountings ignores the group's addresses)
     images = true;
     if (const int irc = image_refusal(h, n, d_addrs)) return group_err(g, irc, "member " + std::to_string(i) + " (" + algorithm_name(h->algorithm) + "): " + h->error);
   }
@@ -1310,7 +1437,18 @@ int group_launch_accounted(mpc_group *g, const void *d_lines, u64 n, uint16_t *c
   if (rc == MPC_OK) rc = group_pack_account(g, d_sizes, n, s);
   for (size_t i = 0; rc == MPC_OK && images && i < g->m.size(); i++)
     if (g->m[i]->img.on) rc = image_pass(sink_of(g), g->m[i], d_sizes[i], d_addrs, n, s);
-  return rc;
+  if (rc != MPC_OK || !images) return rc;
+  // the members with rewrite accounting on: one sort of the chunk's keys, applied to each member's map
+  std::vector<mpc_handle *> hs;
+  std::vector<const uint16_t *> arr;
+  for (size_t i = 0; i < g->m.size(); i++)
+    if (g->m[i]->rw.on) {
+      if (!hs.empty() && (g->m[i]->rw.seen != hs[0]->rw.seen || g->m[i]->rw.batch != hs[0]->rw.batch))
+        return group_err(g, MPC_E_INVAL, "rewrite accounting: member " + std::to_string(i) + " is not at the line of the members before it (reset the members to start over)");
+      hs.push_back(g->m[i]);
+      arr.push_back(d_sizes[i]);
+    }
+  return hs.empty() ? rc : rewrite_pass(sink_of(g), hs.data(), arr.data(), (int)hs.size(), d_addrs, n, s);
 }
 
 // VPC: the size histogram is the sum over the clusters of the histogram in the raw statistics, clipped into MPC_SIZE_BINS bins
@@ -1727,6 +1865,10 @@ void mpc_destroy(mpc_handle *h)
   if (h->pack.done) (void)hipEventDestroy(h->pack.done);
   if (h->img.d_keys) (void)hipFree(h->img.d_keys);
   if (h->img.d_ctl) (void)hipFree(h->img.d_ctl);
+  if (h->rw.d_keys) (void)hipFree(h->rw.d_keys);
+  if (h->rw.d_dev) (void)hipFree(h->rw.d_dev);
+  if (h->rw.d_scratch) (void)hipFree(h->rw.d_scratch);
+  if (h->rw.done) (void)hipEventDestroy(h->rw.done);
   delete h;
 }
 
@@ -1956,6 +2098,7 @@ int mpc_group_compress_batch(mpc_group *g, const uint8_t *lines, uint64_t n, uin
   group_refresh(g);
   if (const int prc = group_pack_check(g)) return prc;
   if (const int irc = group_image_check(g)) return irc;
+  if (const int wrc = group_rewrite_check(g)) return wrc;
   return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, nullptr, nullptr, sizes, sel);
 }
 
@@ -1970,6 +2113,7 @@ static int group_batch_device(mpc_group *g, const void *d_lines, uint64_t n, con
   hipStream_t s = (hipStream_t)hip_stream;
   if (const int prc = group_pack_check(g)) return prc;
   if (const int irc = group_image_check(g)) return irc;
+  if (const int wrc = group_rewrite_check(g)) return wrc;
   const size_t nm = g->m.size();
   bool any = false, scratch = false;
   for (size_t i = 0; i < nm; i++) {
@@ -2018,6 +2162,7 @@ int mpc_group_compress_npy(mpc_group *g, const char *path, uint64_t first_row, u
   group_refresh(g);
   if (const int prc = group_pack_check(g)) return prc;
   if (const int irc = group_image_check(g)) return irc;
+  if (const int wrc = group_rewrite_check(g)) return wrc;
   return mpcstage::compress_npy(g->stage, sink_of(g), nullptr, path, first_row, n_rows, skip_last_row, rows_done);
 }
 
@@ -2027,6 +2172,7 @@ int mpc_group_compress_gpgpusim_log(mpc_group *g, const char *log_path, uint64_t
   group_refresh(g);
   if (const int prc = group_pack_check(g)) return prc;
   if (const int irc = group_image_check(g)) return irc;
+  if (const int wrc = group_rewrite_check(g)) return wrc;
   return mpcstage::compress_gpgpusim_log(g->stage, sink_of(g), nullptr, log_path, requests_read, lines_done);
 }
 
@@ -2116,6 +2262,12 @@ int mpc_stats_reset(mpc_handle *h)
     HIPCHK(h, hipMemset(h->img.d_vals, 0, h->img.slots * sizeof(u64)));
     HIPCHK(h, hipMemset(h->img.d_ctl, 0, MPC_IMAGE_CTL_LEN * sizeof(u64)));
     h->img.seen = 0;
+  }
+  if (h->rw.on) {                     // the map, the position and the table
+    HIPCHK(h, hipMemset(h->rw.d_keys, 0xff, h->rw.slots * sizeof(u64)));
+    HIPCHK(h, hipMemset(h->rw.d_vals, 0, h->rw.slots * sizeof(u64)));
+    HIPCHK(h, hipMemset(h->rw.d_dev, 0, MPC_REWRITE_DEV_LEN * sizeof(u64)));
+    h->rw.seen = 0;
   }
   h->extra.assign(h->stats_len, 0);
   h->sc2.lines = h->sc2.warm = 0;     // SC2: the table and the line counter stay (C-Pack in blocks: the open block and the position in it)
@@ -2601,7 +2753,7 @@ int mpc_image_stats_get(mpc_handle *h, uint64_t *table, size_t n)
 int mpc_compress_batch_addressed(mpc_handle *h, const uint8_t *lines, uint64_t n, const uint64_t *addresses, uint16_t *sizes, int8_t *sel)
 {
   if (!h || (!lines && n) || (!addresses && n)) return MPC_E_INVAL;
-  if (!h->img.on) return set_err(h, MPC_E_INVAL, kImageOff);
+  if (!h->img.on && !h->rw.on) return set_err(h, MPC_E_INVAL, kImageOff);
   if (n == 0) return MPC_OK;
   return mpcstage::compress_batch(h->stage, sink_of(h), h->stream, lines, n, nullptr, addresses, &sizes, &sel);
 }
@@ -2610,7 +2762,7 @@ int mpc_compress_batch_device_addressed(mpc_handle *h, const void *d_lines, uint
                                         void *hip_stream)
 {
   if (!h || (!d_addresses && n)) return MPC_E_INVAL;
-  if (!h->img.on) return set_err(h, MPC_E_INVAL, kImageOff);
+  if (!h->img.on && !h->rw.on) return set_err(h, MPC_E_INVAL, kImageOff);
   if (((uintptr_t)d_addresses) & 7u) return set_err(h, MPC_E_INVAL, "device address buffer must be 8-byte aligned");
   return batch_device(h, d_lines, n, nullptr, d_addresses, d_sizes, d_sel, hip_stream);
 }
@@ -2670,11 +2822,12 @@ int mpc_group_compress_batch_addressed(mpc_group *g, const uint8_t *lines, uint6
                                        int8_t *const *sel)
 {
   if (!g || (!lines && n) || (!addresses && n)) return MPC_E_INVAL;
-  if (!g->img.on) return group_err(g, MPC_E_INVAL, kGroupImageOff);
+  if (!g->img.on && !g->rw.on) return group_err(g, MPC_E_INVAL, kGroupImageOff);
   if (n == 0) return MPC_OK;
   group_refresh(g);
   if (const int prc = group_pack_check(g)) return prc;
   if (const int irc = group_image_check(g)) return irc;
+  if (const int wrc = group_rewrite_check(g)) return wrc;
   return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, nullptr, addresses, sizes, sel);
 }
 
@@ -2682,10 +2835,198 @@ int mpc_group_compress_batch_device_addressed(mpc_group *g, const void *d_lines,
                                               int8_t *const *d_sel, void *hip_stream)
 {
   if (!g || (!d_addresses && n)) return MPC_E_INVAL;
-  if (!g->img.on) return group_err(g, MPC_E_INVAL, kGroupImageOff);
+  if (!g->img.on && !g->rw.on) return group_err(g, MPC_E_INVAL, kGroupImageOff);
   if (((uintptr_t)d_addresses) & 7u) return group_err(g, MPC_E_INVAL, "device address buffer must be 8-byte aligned");
   group_refresh(g);
   return group_batch_device(g, d_lines, n, nullptr, d_addresses, d_sizes, d_sel, hip_stream);
+}
+
+// ---- rewrite accounting (include/mpc_hip_rewrite.h) --------------------------------
+namespace {
+const char *const kRewriteOff = "rewrite accounting is not switched on for this handle (mpc_rewrite_stats_enable)";
+const char *const kGroupRewriteOff = "rewrite accounting is not switched on for this group (mpc_group_rewrite_stats_enable)";
+const char *const kRewriteTableLen = "a rewrite table has MPC_REWRITE_TABLE_LEN (144 + 32 x 32 = 1168) entries";
+
+}  // namespace
+
+int mpc_rewrite_check_values(unsigned line_size, uint64_t capacity_lines, unsigned granule_bytes)
+{
+  const std::string why = line_size == 0 ? std::string("rewrite accounting: line_size must be at least 1") : rewrite_refusal_of(line_size, capacity_lines, granule_bytes);
+  return why.empty() ? MPC_OK : set_err(nullptr, MPC_E_INVAL, why);
+}
+
+int mpc_rewrite_stats_enable(mpc_handle *h, uint64_t capacity_lines, unsigned granule_bytes)
+{
+  if (!h) return MPC_E_INVAL;
+  if (h->algorithm == Algo::Fit) return set_err(h, MPC_E_INVAL, "Fit: an analysis has no per-line sizes to account");
+  const std::string why = rewrite_refusal_of((unsigned)h->L, capacity_lines, granule_bytes);
+  if (!why.empty()) return set_err(h, MPC_E_INVAL, why);
+  auto &R = h->rw;
+  if (R.on) {
+    if (R.capacity == capacity_lines && R.granule == granule_bytes) return MPC_OK;
+    return set_err(h, MPC_E_INVAL, "rewrite accounting is already on with " + rewrite_values(R.capacity, R.granule));
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  u64 batch = MPC_REWRITE_BATCH;
+  R.hash_mask = ~0ull;
+#if MPC_TESTING
+  // chains through most of the table at any capacity: keep only the low bits of the hash; sub-batch seams inside small calls
+  if (const char *e = getenv("MPC_TEST_REWRITE_HASH_BITS")) {
+    const long bits = atol(e);
+    if (bits >= 0 && bits < 64) R.hash_mask = (1ull << bits) - 1ull;
+  }
+  if (const char *e = getenv("MPC_TEST_REWRITE_BATCH")) {
+    const long long v = atoll(e);
+    if (v >= 1 && (u64)v <= MPC_REWRITE_BATCH) batch = (u64)v;
+  }
+#endif
+  const u64 slots = image_slots(capacity_lines);
+  size_t scratch_bytes = 0;
+  hipError_t e = mpc_rewrite_scratch_bytes(batch, &scratch_bytes);
+  if (e != hipSuccess) return set_err(h, MPC_E_HIP, std::string("rewrite accounting: sizing the scratch of a sub-batch: ") + hipGetErrorString(e));
+  auto give_up = [&](int code, const std::string &msg) {       // nothing stays behind a failed enable
+    if (R.d_keys) (void)hipFree(R.d_keys);
+    if (R.d_dev) (void)hipFree(R.d_dev);
+    if (R.d_scratch) (void)hipFree(R.d_scratch);
+    if (R.done) (void)hipEventDestroy(R.done);
+    R.d_keys = R.d_vals = R.d_dev = nullptr;
+    R.d_scratch = nullptr;
+    R.done = nullptr;
+    return set_err(h, code, msg);
+  };
+  if (hipMalloc((void **)&R.d_keys, 2 * slots * sizeof(u64)) != hipSuccess) {        // keys | vals
+    R.d_keys = nullptr;
+    return give_up(MPC_E_NOMEM, "hipMalloc(rewrite map, " + std::to_string(2 * slots * sizeof(u64)) + " bytes) failed");
+  }
+  if (hipMalloc((void **)&R.d_dev, MPC_REWRITE_DEV_LEN * sizeof(u64)) != hipSuccess) {
+    R.d_dev = nullptr;
+    return give_up(MPC_E_NOMEM, "hipMalloc(rewrite counters) failed");
+  }
+  if (hipMalloc(&R.d_scratch, scratch_bytes) != hipSuccess) {
+    R.d_scratch = nullptr;
+    return give_up(MPC_E_NOMEM, "hipMalloc(rewrite scratch, " + std::to_string(scratch_bytes) + " bytes) failed");
+  }
+  R.d_vals = R.d_keys + slots;
+  e = mpc_rewrite_scratch_carve(R.d_scratch, batch, &R.scratch);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&R.done, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipMemset(R.d_keys, 0xff, slots * sizeof(u64));
+  if (e == hipSuccess) e = hipMemset(R.d_vals, 0, slots * sizeof(u64));
+  if (e == hipSuccess) e = hipMemset(R.d_dev, 0, MPC_REWRITE_DEV_LEN * sizeof(u64));
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // (the kernels run on non-blocking streams)
+  if (e != hipSuccess) return give_up(MPC_E_HIP, std::string("rewrite accounting: clearing the map: ") + hipGetErrorString(e));
+  R.capacity = capacity_lines;
+  R.granule = granule_bytes;
+  R.G = ((unsigned)h->L + granule_bytes - 1) / granule_bytes;
+  R.slots = slots;
+  R.batch = batch;
+  R.seen = 0;
+  R.over = false;
+  R.recorded = false;
+  h->stage.account[0] = 1;
+  h->stage.log_addrs = true;
+  R.on = true;
+  return MPC_OK;
+}
+
+int mpc_rewrite_stats_get(mpc_handle *h, uint64_t *table, size_t n)
+{
+  if (!h) return MPC_E_INVAL;
+  if (!h->rw.on) return set_err(h, MPC_E_INVAL, kRewriteOff);
+  if (!table || n != MPC_REWRITE_TABLE_LEN) return set_err(h, MPC_E_INVAL, kRewriteTableLen);
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = sync_all(h);
+  if (rc != MPC_OK) return rc;
+  HIPCHK(h, hipDeviceSynchronize());   // callers may have used their own streams
+  rc = pattern_status(h);
+  if (rc != MPC_OK) return rc;
+  const auto &R = h->rw;
+  std::vector<u64> dev(MPC_REWRITE_DEV_LEN, 0);
+  {
+    const MpcRewriteMap M = rewrite_map(h);
+    hipError_t e = hipMemsetAsync(R.d_dev + MPC_REWRITE_DEV_OUT, 0, MPC_REWRITE_OUT_LEN * sizeof(u64), h->stream);
+    if (e == hipSuccess) e = mpc_launch_rewrite_get(&M, grid_for(h, R.slots, 256, 8), h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dev.data(), R.d_dev, MPC_REWRITE_DEV_LEN * sizeof(u64), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess || e2 != hipSuccess)
+      return set_err(h, MPC_E_HIP, std::string("rewrite accounting, get pass: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+  }
+  const u64 *out = dev.data() + MPC_REWRITE_DEV_OUT;
+  std::fill(table, table + MPC_REWRITE_TABLE_LEN, 0);
+  table[0] = dev[MPC_REWRITE_CTL_LINES];
+  table[1] = dev[MPC_REWRITE_CTL_BITS];
+  table[2] = dev[MPC_REWRITE_CTL_KEYS];
+  table[3] = dev[MPC_REWRITE_CTL_MISALIGNED];
+  table[7] = dev[MPC_REWRITE_CTL_EQUAL];
+  table[8] = out[MPC_REWRITE_OUT_LATEST_CLASSES];
+  table[9] = out[MPC_REWRITE_OUT_PEAK_CLASSES];
+  table[10] = out[MPC_REWRITE_OUT_LATEST_BITS];
+  table[11] = out[MPC_REWRITE_OUT_PEAK_BITS];
+  table[12] = R.granule;
+  table[13] = R.capacity;
+  table[14] = R.G;
+  for (unsigned c = 0; c < MPC_REWRITE_MAX_CLASSES; c++) {
+    table[16 + c] = dev[MPC_REWRITE_DEV_FIRST + c];
+    table[48 + c] = out[MPC_REWRITE_OUT_HIST_LATEST + c];
+    table[80 + c] = out[MPC_REWRITE_OUT_HIST_PEAK + c];
+    table[112 + c] = out[MPC_REWRITE_OUT_HIST_COUNT + c];
+    for (unsigned d = 0; d < MPC_REWRITE_MAX_CLASSES; d++) {
+      const u64 v = dev[MPC_REWRITE_DEV_TRANS + c * MPC_REWRITE_MAX_CLASSES + d];
+      table[144 + c * MPC_REWRITE_MAX_CLASSES + d] = v;
+      table[4] += v;
+      if (d > c) table[5] += v;
+      if (d < c) table[6] += v;
+    }
+  }
+  return MPC_OK;
+}
+
+int mpc_group_rewrite_stats_enable(mpc_group *g, uint64_t capacity_lines, unsigned granule_bytes)
+{
+  if (!g) return MPC_E_INVAL;
+  const std::string why = rewrite_refusal_of((unsigned)g->stage.L, capacity_lines, granule_bytes);
+  if (!why.empty()) return group_err(g, MPC_E_INVAL, why);
+  auto &G = g->rw;
+  if (G.on) {
+    if (G.capacity == capacity_lines && G.granule == granule_bytes) return MPC_OK;
+    return group_err(g, MPC_E_INVAL, "rewrite accounting is already on with " + rewrite_values(G.capacity, G.granule));
+  }
+  // every member fresh (it starts at line 0), or on with the same values; then all at one line
+  bool first = true;
+  u64 at = 0;
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const auto &R = g->m[i]->rw;
+    if (g->m[i]->algorithm == Algo::Fit) return group_err(g, MPC_E_INVAL, "Fit: an analysis has no per-line sizes to account");
+    if (R.on && (R.capacity != capacity_lines || R.granule != granule_bytes))
+      return group_err(g, MPC_E_INVAL, "rewrite accounting: member " + std::to_string(i) + " already counts with " + rewrite_values(R.capacity, R.granule));
+    const u64 seen = R.on ? R.seen : 0;
+    if (!first && seen != at)
+      return group_err(g, MPC_E_INVAL, "rewrite accounting: member " + std::to_string(i) + " is at line " + std::to_string(seen) + ", the members before it at line " +
+                                           std::to_string(at) + " (reset the members first)");
+    at = seen;
+    first = false;
+  }
+  for (size_t i = 0; i < g->m.size(); i++) {
+    const int rc = mpc_rewrite_stats_enable(g->m[i], capacity_lines, granule_bytes);
+    if (rc != MPC_OK) return group_err(g, rc, "member " + std::to_string(i) + " (" + algorithm_name(g->m[i]->algorithm) + "): " + g->m[i]->error);
+  }
+  G.capacity = capacity_lines;
+  G.granule = granule_bytes;
+  G.on = true;
+  return MPC_OK;
+}
+
+int mpc_group_rewrite_stats_get(mpc_group *g, int member, uint64_t *table, size_t n)
+{
+  if (!g) return MPC_E_INVAL;
+  if (!g->rw.on) return group_err(g, MPC_E_INVAL, kGroupRewriteOff);
+  if (!table || n != MPC_REWRITE_TABLE_LEN) return group_err(g, MPC_E_INVAL, kRewriteTableLen);
+  if (member < 0 || member >= (int)g->m.size())
+    return group_err(g, MPC_E_INVAL, "rewrite accounting: member " + std::to_string(member) + " is not a member of the group");
+  int rc = mpc_group_sync(g);
+  if (rc != MPC_OK) return rc;
+  mpc_handle *h = g->m[(size_t)member];
+  rc = mpc_rewrite_stats_get(h, table, n);
+  return rc == MPC_OK ? rc : group_err(g, rc, "member " + std::to_string(member) + " (" + algorithm_name(h->algorithm) + "): " + h->error);
 }
 
 // ---- per-class accounting (include/mpc_hip_classes.h) ----------------------------
@@ -2817,6 +3158,7 @@ int mpc_group_compress_batch_classed(mpc_group *g, const uint8_t *lines, uint64_
   group_refresh(g);
   if (const int prc = group_pack_check(g)) return prc;
   if (const int irc = group_image_check(g)) return irc;
+  if (const int wrc = group_rewrite_check(g)) return wrc;
   return mpcstage::compress_batch(g->stage, sink_of(g), nullptr, lines, n, classes, nullptr, sizes, sel);
 }
 
@@ -2889,7 +3231,7 @@ int mpc_snapshot_evaluate(mpc_snapshot *s, mpc_handle *h, unsigned line_size, in
   if (h->device != mpc_snapshot_device_of(s)) return mpc_snapshot_fail(s, MPC_E_INVAL, "snapshot: the evaluator is on another device");
   const bool classed = by_presence && h->cls.on;
   int rc = snapshot_pieces(s, line_size, partial, [&](const void *d, u64 n, const uint64_t *da, const uint8_t *dp, void *stream) {
-    const int frc = batch_device(h, d, n, classed ? dp : nullptr, h->img.on ? da : nullptr, nullptr, nullptr, stream);
+    const int frc = batch_device(h, d, n, classed ? dp : nullptr, (h->img.on || h->rw.on) ? da : nullptr, nullptr, nullptr, stream);
     return frc == MPC_OK ? frc : mpc_snapshot_fail(s, frc, h->error.c_str());
   });
   if (rc != MPC_OK) return rc;
@@ -2909,7 +3251,7 @@ int mpc_snapshot_evaluate_group(mpc_snapshot *s, mpc_group *g, unsigned line_siz
     return mpc_snapshot_fail(s, MPC_E_INVAL, ("class accounting: the classes come from member " + std::to_string(g->cls.from_member) + ", by_presence cannot bring its own").c_str());
   group_refresh(g);
   int rc = snapshot_pieces(s, line_size, partial, [&](const void *d, u64 n, const uint64_t *da, const uint8_t *dp, void *stream) {
-    const int frc = group_batch_device(g, d, n, classed ? dp : nullptr, g->img.on ? da : nullptr, nullptr, nullptr, stream);
+    const int frc = group_batch_device(g, d, n, classed ? dp : nullptr, (g->img.on || g->rw.on) ? da : nullptr, nullptr, nullptr, stream);
     return frc == MPC_OK ? frc : mpc_snapshot_fail(s, frc, g->error.c_str());
   });
   if (rc != MPC_OK) return rc;

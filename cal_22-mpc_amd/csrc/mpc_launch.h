@@ -2,12 +2,12 @@
 //
 // The launchers have C linkage, so a declaration that drifted from its definition would still link and then misbehave.
 // This header is therefore included by the callers (mpc_capi.hip, mpc_jit.h) AND by the units that define the
-// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_fit.hip, mpc_sizes.hip, mpc_classes.hip, mpc_pack.hip, mpc_image.hip, the host section of mpc_vpc_lane.hip):
+// launchers (mpc_kernels.hip, mpc_baselines.hip, mpc_sc2.hip, mpc_pattern.hip, mpc_pattern_evict.hip, mpc_cpack.hip, mpc_cpack_blocks.hip, mpc_fit.hip, mpc_sizes.hip, mpc_classes.hip, mpc_pack.hip, mpc_image.hip, mpc_rewrite.hip, the host section of mpc_vpc_lane.hip):
 // the compiler sees declaration and definition together and refuses a mismatch.  Host code only -- the run-time
 // compiled source of mpc_jit.h (-DMPC_LANE_JIT) never sees it, and it is not one of the files that key the code
 // object cache.
 //
-// The parameter blocks are only named here (their definitions: mpc_device.h, mpc_sc2.h, mpc_pattern.h, mpc_sizes.h, mpc_classes.h, mpc_pack.h, mpc_image.h).
+// The parameter blocks are only named here (their definitions: mpc_device.h, mpc_sc2.h, mpc_pattern.h, mpc_sizes.h, mpc_classes.h, mpc_pack.h, mpc_image.h, mpc_rewrite.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -23,6 +23,8 @@ struct MpcClassArgs;
 struct MpcPackArgs;
 struct MpcImageArgs;
 struct MpcImageGetArgs;
+struct MpcRewriteScratch;
+struct MpcRewriteMap;
 
 extern "C" {
 // mpc_kernels.hip
@@ -118,4 +120,16 @@ hipError_t mpc_launch_pack(const MpcPackArgs *A, unsigned long long n_lines, int
 // `grid` bounds the workgroups; the launchers size them down to the work.
 hipError_t mpc_launch_image_update(const MpcImageArgs *A, unsigned long long n_lines, int grid, hipStream_t stream);
 hipError_t mpc_launch_image_get(const MpcImageGetArgs *A, int grid, hipStream_t stream);
+
+// mpc_rewrite.hip: the scratch of a sub-batch of at most `lines` lines (its bytes; its arrays carved out of one allocation),
+// and the passes of a sub-batch of n_lines <= S->lines (mpc_rewrite.h): keys (keys == 0: only the sums of a further member
+// of a group into its dev), the sort, and the sorted sub-batch applied to one map with its handle's sizes (three launches
+// and a keyed reduction).  The get pass: one launch over the slots.  `grid` bounds the workgroups.
+hipError_t mpc_rewrite_scratch_bytes(unsigned long long lines, size_t *bytes);
+hipError_t mpc_rewrite_scratch_carve(void *base, unsigned long long lines, MpcRewriteScratch *S);
+hipError_t mpc_launch_rewrite_keys(const MpcRewriteScratch *S, const uint64_t *addrs, const uint16_t *sizes, unsigned long long n_lines, unsigned line_size,
+                                   unsigned long long *dev, int keys, int grid, hipStream_t stream);
+hipError_t mpc_launch_rewrite_sort(const MpcRewriteScratch *S, unsigned long long n_lines, hipStream_t stream);
+hipError_t mpc_launch_rewrite_apply(const MpcRewriteScratch *S, const MpcRewriteMap *M, const uint16_t *sizes, unsigned long long n_lines, hipStream_t stream);
+hipError_t mpc_launch_rewrite_get(const MpcRewriteMap *M, int grid, hipStream_t stream);
 }

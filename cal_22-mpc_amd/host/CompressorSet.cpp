@@ -120,6 +120,22 @@ ImageReport CompressorSet::GetImageStats(size_t i)
   return report;
 }
 
+void CompressorSet::EnableRewriteStats(unsigned granuleBytes, unsigned long long capacityLines)
+{
+  Prepare();
+  int rc = mpc_group_rewrite_stats_enable(m_Group, capacityLines, granuleBytes);
+  if (rc != MPC_OK) fail("CompressorSet::EnableRewriteStats", rc, mpc_group_last_error(m_Group));
+}
+
+RewriteReport CompressorSet::GetRewriteStats(size_t i)
+{
+  Prepare();
+  RewriteReport report(GetLineSize());
+  int rc = mpc_group_rewrite_stats_get(m_Group, (int)i, report.Table.data(), report.Table.size());
+  if (rc != MPC_OK) fail("CompressorSet::GetRewriteStats", rc, mpc_group_last_error(m_Group));
+  return report;
+}
+
 void CompressorSet::SetLogClassField(int field)
 {
   int rc = mpc_group_class_log_field(m_Group, field);

@@ -13,6 +13,7 @@
 #include "ClassReport.h"
 #include "ImageReport.h"
 #include "PackReport.h"
+#include "RewriteReport.h"
 #include "SizeReport.h"
 
 struct mpc_group;
@@ -65,6 +66,11 @@ public:
                         unsigned long long capacityLines = 1ull << 24);
   // member i's table
   ImageReport GetImageStats(size_t i);
+  // ADDITIVE: EnableRewriteStats for every member with the same values; a member's map is its own
+  // (mpc_group_rewrite_stats_enable); off by default
+  void EnableRewriteStats(unsigned granuleBytes = ACCESS_GRAN, unsigned long long capacityLines = 1ull << 24);
+  // member i's table
+  RewriteReport GetRewriteStats(size_t i);
   // ADDITIVE: the group itself, for what feeds it from the device (Snapshot::Evaluate); the members' buffered lines go
   // first and every member counts as fed
   mpc_group *DeviceGroup() { Prepare(); return m_Group; }

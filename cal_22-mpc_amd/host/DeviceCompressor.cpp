@@ -131,6 +131,29 @@ ImageReport DeviceCompressor::GetImageStats()
   return report;
 }
 
+void DeviceCompressor::EnableRewriteStats(unsigned granuleBytes, unsigned long long capacityLines)
+{
+  FlushLines();
+  int rc = mpc_rewrite_stats_enable(m_Handle, capacityLines, granuleBytes);
+  if (rc != MPC_OK) Fail(m_Tag + "::EnableRewriteStats", rc);
+}
+
+bool DeviceCompressor::CheckRewriteValues(unsigned lineSize, unsigned granuleBytes, unsigned long long capacityLines, std::string &why)
+{
+  if (mpc_rewrite_check_values(lineSize, capacityLines, granuleBytes) == MPC_OK) return true;
+  why = mpc_last_error(nullptr);
+  return false;
+}
+
+RewriteReport DeviceCompressor::GetRewriteStats()
+{
+  FlushLines();
+  RewriteReport report(m_LineSize);
+  int rc = mpc_rewrite_stats_get(m_Handle, report.Table.data(), report.Table.size());
+  if (rc != MPC_OK) Fail(m_Tag + "::GetRewriteStats", rc);
+  return report;
+}
+
 void DeviceCompressor::SetLogClassField(int field)
 {
   int rc = mpc_class_log_field(m_Handle, field);

@@ -10,6 +10,7 @@
 #include "ClassReport.h"
 #include "ImageReport.h"
 #include "PackReport.h"
+#include "RewriteReport.h"
 #include "SizeReport.h"
 
 namespace comp
@@ -53,6 +54,13 @@ public:
                         unsigned long long capacityLines = 1ull << 24);
   // ... that table (mpc_image_stats_get; not destructive), buffered lines evaluated first; a failure exits like every other
   ImageReport GetImageStats();
+  // ADDITIVE: follow, from now on, the sequence of sizes per line address (a .log's mem_addr) for up to capacityLines
+  // distinct lines, in size classes of granuleBytes bytes (mpc_rewrite_stats_enable); off by default
+  void EnableRewriteStats(unsigned granuleBytes = ACCESS_GRAN, unsigned long long capacityLines = 1ull << 24);
+  // ... that table (mpc_rewrite_stats_get; not destructive), buffered lines evaluated first; a failure exits like every other
+  RewriteReport GetRewriteStats();
+  // whether EnableRewriteStats takes these values for lines of lineSize bytes (mpc_rewrite_check_values; no device); why: the refusal
+  static bool CheckRewriteValues(unsigned lineSize, unsigned granuleBytes, unsigned long long capacityLines, std::string &why);
 
 protected:
   // tag: the short name in front of this class's messages ("BDI", "VPC", ...)

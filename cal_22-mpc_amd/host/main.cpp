@@ -24,6 +24,10 @@
 // OUTDIR/<stem>_results_image.csv (comp::ImageReport: the latest size per line address of a GPGPU-Sim .log trace's
 // mem_addr, and the sectors that address-aligned blocks of N lines of that image occupy).  With a list every member gets
 // its file.  It needs a .log input.  Next to --image, --sector does not imply --size-histogram.  Without --image nothing changes.
+// ADDITIVE: --rewrites GRANULE [--rewrite-capacity LINES] also writes OUTDIR/<stem>_results_rewrites.csv
+// (comp::RewriteReport: per line address of a GPGPU-Sim .log trace's mem_addr the sequence of sizes, as transitions
+// between size classes of GRANULE bytes, with the latest and the peak granules).  With a list every member gets its file.
+// It needs a .log input and is refused next to --snapshot, where every address occurs once.  Without --rewrites nothing changes.
 // ADDITIVE: --snapshot L [--snapshot-partial skip|zero] [--snapshot-capacity UNITS] evaluates, instead of the requests of a
 // GPGPU-Sim .log trace, the memory they touched: the latest bytes per request address (comp::Snapshot), written out as
 // address-aligned lines of L bytes in ascending address order.  The usual files are written with the workload named
@@ -75,6 +79,11 @@ static const char *kHelp =
     "                       --sector's (which then implies nothing).\n"
     "      --image-header arg Bits added to every block of --image. Default=0\n"
     "      --image-capacity arg Distinct lines the image can hold. Default=16777216\n"
+    "      --rewrites arg   Also write <stem>_results_rewrites.csv: how the size of a\n"
+    "                       line of a .log trace changes when its address comes again,\n"
+    "                       in size classes of that many bytes\n"
+    "      --rewrite-capacity arg Distinct lines --rewrites can follow.\n"
+    "                       Default=16777216\n"
     "      --snapshot arg   Evaluate, instead of the requests of a .log trace, the\n"
     "                       memory they touched: the latest bytes per address as\n"
     "                       aligned lines of that many bytes (1, 2, 4 or 8 requests,\n"
@@ -105,6 +114,8 @@ struct Args {
   bool has_image = false, has_image_header = false, has_image_capacity = false;      // ADDITIVE --image N [...]: <stem>_results_image.csv (ImageReport.h)
   unsigned long long image = 0, image_capacity = 1ull << 24;
   unsigned image_header = 0;
+  bool has_rewrites = false, has_rewrite_capacity = false;      // ADDITIVE --rewrites GRANULE [--rewrite-capacity LINES]: <stem>_results_rewrites.csv (RewriteReport.h)
+  unsigned long long rewrites = 0, rewrite_capacity = 1ull << 24;
   bool has_snapshot = false, has_snapshot_partial = false, has_snapshot_capacity = false;      // ADDITIVE --snapshot L [...]: Snapshot.h
   unsigned long long snapshot = 0, snapshot_capacity = 1ull << 24;
   std::string snapshot_partial = "skip";
@@ -214,6 +225,21 @@ static void requireImage(const Args &a, unsigned traceLineSize)
     printf("--image %llu with --sector %u: a block of %llu bytes has more than %zu sectors.\n", a.image, a.sector, blockBytes, comp::ImageReport::MaxSectors);
     exit(1);
   }
+}
+
+// --rewrites against the trace: a granule is at most a line, a line at most 32 granules
+static void requireRewrites(const Args &a, unsigned traceLineSize)
+{
+  if (!a.has_rewrites) return;
+  std::string why;
+  if (comp::DeviceCompressor::CheckRewriteValues(traceLineSize, (unsigned)a.rewrites, a.rewrite_capacity, why)) return;
+  printf("--rewrites %llu over a trace of %u-byte lines: %s.\n", a.rewrites, traceLineSize, why.c_str());
+  exit(1);
+}
+
+static void writeRewrites(comp::RewriteReport report, const std::string &workloadName, const std::string &outputDirPath, const std::string &saveFileName)
+{
+  report.Print(workloadName, outputDirPath + "/" + saveFileName + "_results_rewrites.csv");
 }
 
 // --snapshot against the trace: a line is 1, 2, 4 or 8 of the trace's requests and at most 256 bytes
@@ -424,6 +450,32 @@ int main(int argc, char **argv)
       a.has_image_capacity = true;
       continue;
     }
+    if (arg == "--rewrites" || arg.compare(0, 11, "--rewrites=") == 0) {
+      if (arg == "--rewrites" && i + 1 >= argc) {
+        std::cout << "Option 'rewrites' is missing an argument" << std::endl;
+        exit(1);
+      }
+      const std::string value = arg == "--rewrites" ? argv[++i] : arg.substr(11);
+      if (!takeNumber(value, 65536, a.rewrites) || a.rewrites == 0) {
+        std::cout << "--rewrites takes a granule size in bytes from 1 to the line size, not \"" << value << "\"." << std::endl;
+        return 1;
+      }
+      a.has_rewrites = true;
+      continue;
+    }
+    if (arg == "--rewrite-capacity" || arg.compare(0, 19, "--rewrite-capacity=") == 0) {
+      if (arg == "--rewrite-capacity" && i + 1 >= argc) {
+        std::cout << "Option 'rewrite-capacity' is missing an argument" << std::endl;
+        exit(1);
+      }
+      const std::string value = arg == "--rewrite-capacity" ? argv[++i] : arg.substr(19);
+      if (!takeNumber(value, 1ull << 28, a.rewrite_capacity) || a.rewrite_capacity == 0) {
+        std::cout << "--rewrite-capacity takes a number of lines from 1 to 268435456, not \"" << value << "\"." << std::endl;
+        return 1;
+      }
+      a.has_rewrite_capacity = true;
+      continue;
+    }
     if (arg == "--snapshot" || arg.compare(0, 11, "--snapshot=") == 0) {
       if (arg == "--snapshot" && i + 1 >= argc) {
         std::cout << "Option 'snapshot' is missing an argument" << std::endl;
@@ -552,6 +604,23 @@ int main(int argc, char **argv)
     std::cout << "--image is evaluated in batches: it does not go with --per-line / --line-buffer." << std::endl;
     return 1;
   }
+  // --rewrites: checked before anything is opened or written, one message each
+  if (a.has_rewrite_capacity && !a.has_rewrites) {
+    std::cout << "--rewrite-capacity belongs to --rewrites: give --rewrites GRANULE too." << std::endl;
+    return 1;
+  }
+  if (a.has_rewrites && !trace::IsGpgpuSimLog(a.input)) {
+    std::cout << "--rewrites takes the line addresses from the records of a GPGPU-Sim .log trace: \"" << a.input << "\" is not one." << std::endl;
+    return 1;
+  }
+  if (a.has_rewrites && a.has_snapshot) {
+    std::cout << "--rewrites does not go with --snapshot: every address occurs once in a snapshot, nothing is written again." << std::endl;
+    return 1;
+  }
+  if (a.has_rewrites && a.per_line) {
+    std::cout << "--rewrites is evaluated in batches: it does not go with --per-line / --line-buffer." << std::endl;
+    return 1;
+  }
   // --snapshot: checked before anything is opened or written, one message each
   if ((a.has_snapshot_partial || a.has_snapshot_capacity) && !a.has_snapshot) {
     std::cout << "--snapshot-partial and --snapshot-capacity belong to --snapshot: give --snapshot L too." << std::endl;
@@ -580,6 +649,7 @@ int main(int argc, char **argv)
   requireSector(a, lineSize);
   requirePack(a, lineSize);
   requireImage(a, lineSize);
+  requireRewrites(a, lineSize);
 
   comp::DeviceCompressor *compressor = makeEvaluator(algorithm, configPath, lineSize);
   if (!compressor) {
@@ -600,6 +670,7 @@ int main(int argc, char **argv)
   }
   if (a.has_pack) compressor->EnablePackStats(a.pack, a.sector, a.pack_header);
   if (a.has_image) compressor->EnableImageStats(a.image, a.sector, a.image_header, a.image_capacity);
+  if (a.has_rewrites) compressor->EnableRewriteStats((unsigned)a.rewrites, a.rewrite_capacity);
   comp::SnapshotReport snapshotReport(lineSize, false);
   if (a.has_snapshot)
     snapshotReport = compressSnapshot(*compressor, tracePath, loader->GetCachelineSize(), a);
@@ -618,6 +689,7 @@ int main(int argc, char **argv)
   if (a.has_by) writeClasses(compressor->GetClassStats(), workloadName, outputDirPath, saveFileName);
   if (a.has_pack) writePack(compressor->GetPackStats(), workloadName, outputDirPath, saveFileName);
   if (a.has_image) writeImage(compressor->GetImageStats(), workloadName, outputDirPath, saveFileName);
+  if (a.has_rewrites) writeRewrites(compressor->GetRewriteStats(), workloadName, outputDirPath, saveFileName);
   if (a.has_snapshot) writeSnapshot(snapshotReport, workloadName, outputDirPath, saveFileName);
 
   delete memReq;      // (the reference leaks its request object)
@@ -643,6 +715,7 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
   requireSector(a, lineSize);
   requirePack(a, lineSize);
   requireImage(a, lineSize);
+  requireRewrites(a, lineSize);
   std::vector<comp::DeviceCompressor *> evaluators;
   std::vector<comp::Compressor *> members;
   for (const std::string &n : names) {
@@ -666,6 +739,7 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
     }
     if (a.has_pack) set.EnablePackStats(a.pack, a.sector, a.pack_header);      // (behind EnableBest: the best of the list gets its table)
     if (a.has_image) set.EnableImageStats(a.image, a.sector, a.image_header, a.image_capacity);
+    if (a.has_rewrites) set.EnableRewriteStats((unsigned)a.rewrites, a.rewrite_capacity);
     comp::SnapshotReport snapshotReport(lineSize, false);
     if (a.has_snapshot)
       snapshotReport = compressSnapshot(set, tracePath, loader->GetCachelineSize(), a);
@@ -680,6 +754,7 @@ static int runList(const std::vector<std::string> &names, const std::string &tra
       if (a.has_by) writeClasses(set.GetClassStats(i), workloadName, outputDirPath, saveFileName);
       if (a.has_pack) writePack(set.GetPackStats(i), workloadName, outputDirPath, saveFileName);
       if (a.has_image) writeImage(set.GetImageStats(i), workloadName, outputDirPath, saveFileName);
+      if (a.has_rewrites) writeRewrites(set.GetRewriteStats(i), workloadName, outputDirPath, saveFileName);
       if (a.has_snapshot) writeSnapshot(snapshotReport, workloadName, outputDirPath, saveFileName);
     }
     if (a.size_histogram) {

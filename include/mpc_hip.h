@@ -386,6 +386,9 @@ int mpc_group_sync(mpc_group *g);
 /* ---- image accounting: the latest size per line address, and the sectors that address-aligned blocks of it occupy ----
  * Additive and off by default as well, in a header of its own for the same reason.                                  */
 #include "mpc_hip_image.h"
+/* ---- rewrite accounting: the sequence of sizes per line address -- transitions between size classes, latest and peak ----
+ * Additive and off by default as well, in a header of its own for the same reason.                                  */
+#include "mpc_hip_rewrite.h"
 /* ---- snapshots: the bytes of the latest unit per address, written out as address-aligned lines of any line size ----
  * An object of its own next to handles and groups, in a header of its own for the same reason.                      */
 #include "mpc_hip_snapshot.h"
